@@ -10,10 +10,20 @@ Workload (BASELINE.json configs[2] = configs[1] + the correlation head; SURVEY.m
   `--batch 4` is config 2's batch), data parallel over N GPUs (one process per GPU, gradient all-reduce over
   RCCL, weak scaling).  The image backbone and render CNN are outside the path (left to MIOpen) and are not run.
 
-Prints ONE JSON line (rank 0).  `python bench.py --gpus N --steps K --warmup W`.  For N > 1 either launch it under
-`python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...` (one rank per GPU; RANK / LOCAL_RANK /
-WORLD_SIZE / MASTER_* read from the environment) or run it bare: with no WORLD_SIZE in the environment it starts
-that launcher itself as a child process -- before anything touches the GPU -- and exits with the child's code.
+Prints ONE JSON line (rank 0).  `python bench.py --gpus N --steps K --warmup W`: set up, W warm-up steps, K timed steps,
+the line (`value` samples/s and `ms_per_step` over the K timed steps).  `--full` adds the secondary figures to the line:
+per-kernel HIP-event times and the MFMA / HBM / LDS rooflines of the timed steps, the same workload in the bf16x3 and
+exact-f32 modes (`--f32-steps`) and the host-CPU baseline with the GPU on its workloads (`--no-cpu-baseline` skips it).
+`--dump-outputs DIR` writes what the last timed step computed (loss and parameter gradients, dump_outputs) as .npy.
+Every step, warm-up and timed, starts from the same seeded weights on the same seeded inputs (the attention key
+biases, whose gradient is identically zero, stay fixed: LiftBlock), so runs with the same arguments compute the same
+thing -- the loss bit for bit, gradients up to the rounding of the kernels' float atomics -- and two builds can be
+compared output for output.
+
+For N > 1 either launch it under `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...` (one
+rank per GPU; RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* read from the environment) or run it bare: with no WORLD_SIZE in
+the environment it starts that launcher itself as a child process -- before anything touches the GPU -- and exits with
+the child's code.
 """
 import argparse
 import json
@@ -85,6 +95,13 @@ class LiftBlock(nn.Module):
         # parameters the reference constructs but never uses get no gradient: keep them out of the all-reduce
         from bevrender_amd.parallel import freeze_unused_parameters
         freeze_unused_parameters(self, n_views=V)
+        # the attention key biases get an identically zero gradient: adding b to every key adds the same q . b to all
+        # logits of a query, which softmax ignores.  The backward's value for them is the rounding noise of its float
+        # atomics, different in every run, on which AdamW would random-walk them: they keep their zero init.  The fused
+        # K | V projection still runs as before (proj_v's bias trains); autograd only drops the proj_k half.
+        for name, p in self.named_parameters():
+            if name.endswith("proj_k.bias"):
+                p.requires_grad_(False)
 
     def encode(self, feats, prev_bev):
         B = feats.shape[0] // self.layers[0].spatial_cross_attn.num_views
@@ -289,6 +306,137 @@ def gpu_same_workloads(dev):
     return res
 
 
+def roofline_figures(ktimes, args, B, S, world, samples_per_s):
+    """`--full`: the timed steps' per-kernel HIP-event times (ktimes, ops.KERNEL_TIMER) against the MFMA, LDS and HBM
+    peaks -- the `roofline`, `roofline_hbm`, `roofline_lds` and `roofline_hbm_block` fields of the line."""
+    from bevrender_amd import ops
+    # dominant kernel by accumulated device time inside the timed region (HIP events on its stream)
+    attn = {k: v for k, v in ktimes.items() if k.startswith("bevr_attn")}
+    dom = max(attn, key=lambda k: attn[k]["ms"]) if attn else None
+    roof = None
+    # HBM bytes per launch: measured with rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE on this very command (separate
+    # passes, gfx950 correction applied) by tools/measure_traffic.sh, which writes profiles/r05_traffic.json together
+    # with the kernel sources' sha; only attached when that file was measured at this batch / BEV side / precision
+    # AND on these very kernel sources (a stale file is not reported as measured traffic: ADVICE r02)
+    traffic_db, traffic_note = {}, "no profiles/r05_traffic.json for this batch / BEV side / precision"
+    tpath = os.path.join(ROOT, "profiles", "r05_traffic.json")
+    if os.path.exists(tpath):
+        with open(tpath) as fh:
+            tj = json.load(fh)
+        if tj.get("batch") == B and tj.get("bev") == S and tj.get("precision") == args.precision:
+            if tj.get("csrc_sha") == csrc_sha():
+                traffic_db, traffic_note = tj["kernels"], f"measured at csrc_sha {tj.get('csrc_sha')}"
+            else:
+                traffic_note = (f"profiles/r05_traffic.json was measured at csrc_sha {tj.get('csrc_sha')}, the kernels "
+                                f"are at {csrc_sha()}: not attached")
+    if dom:
+        rec = attn[dom]
+        avg_ms = rec["ms"] / rec["n"]
+        flops = rec["flops"] / rec["n"]
+        ach = flops / (avg_ms * 1e-3) / 1e12
+        peak = MFMA_PEAK_TFLOPS[args.precision]
+        pairs = rec["flops"] / rec["n"] / (2.0 * 32 * N_MATMUL[dom])
+        roof = {"bound": "mfma", "kernel": dom, "achieved": round(ach, 3), "peak": peak, "unit": "TFLOP/s",
+                "frac": round(ach / peak, 5), "traffic": traffic_db.get(dom, {}).get("hbm_bytes_per_launch"),
+                "traffic_note": traffic_note, "avg_ms": round(avg_ms, 3), "launches": rec["n"],
+                "pair_ops_per_s": round(pairs / (avg_ms * 1e-3), 0),
+                "kernel_ms_per_step": {k: round(v["ms"] / args.steps, 2) for k, v in sorted(ktimes.items())},
+                "all_attention": {k: {"avg_ms": round(v["ms"] / v["n"], 3),
+                                      "frac": round(v["flops"] / (v["ms"] * 1e-3) / 1e12 / peak, 5)}
+                                  for k, v in sorted(attn.items())}}
+        # every attention launch of the timed region together, on SURVEY 8d's accounting (7 products per pair forward +
+        # backward); `executed`: the 9 products the two-sided backward runs (S and dP on both sides)
+        tot_ms = sum(v["ms"] for v in attn.values())
+        tot_exec = sum(v["flops"] for v in attn.values())
+        tot_alg = sum(v["flops"] / N_MATMUL[k] * ALG_MATMUL[k] for k, v in attn.items())
+        roof["all_attention_aggregate"] = {"achieved": round(tot_alg / (tot_ms * 1e-3) / 1e12, 3), "unit": "TFLOP/s",
+                                           "frac": round(tot_alg / (tot_ms * 1e-3) / 1e12 / peak, 5),
+                                           "accounting": "SURVEY 8d: 2 products per pair forward, 5 backward",
+                                           "executed": {"achieved": round(tot_exec / (tot_ms * 1e-3) / 1e12, 3),
+                                                        "frac": round(tot_exec / (tot_ms * 1e-3) / 1e12 / peak, 5)},
+                                           "ms_per_step": round(tot_ms / args.steps, 2)}
+        # per call: TSA (square table) and SCA (the scattered keys on the region kernels, the pinned ones on the tap
+        # kernels) separately -- kernel_ms_per_step lumps them
+        roof["kernel_ms_per_step_by_call"] = {k: {"ms_per_step": round(v["ms"] / args.steps, 2), "launches": v["n"],
+                                                  "avg_ms": round(v["ms"] / v["n"], 3),
+                                                  "Tpairs_per_s": round(v["flops"] / (2.0 * 32 * N_MATMUL[k.split("[")[0]]) / (v["ms"] * 1e-3) / 1e12, 3)}
+                                              for k, v in sorted(ops.KERNEL_TIMER.by_tag.items()) if k.startswith("bevr_attn")}
+    # What actually paces the attention kernels is per-pair work on the LDS pipe (bias taps, per-key constants, the
+    # table-gradient atomics), not the matrix cores (DESIGN.md section 5).  Secondary, clearly separate from
+    # `roofline`: the pair rate against the rate at which one CU's LDS pipe could issue each kernel's LDS
+    # instructions back to back (clk per wave and key row = per 64 pairs, from the measured instruction costs in
+    # profiles/r02_lds_*.txt; bf16 mode).
+    LDS_CLK_PER_KEYROW = {"bevr_attn_fwd": 10.0,     # taps 4.8 + constants (b64 + b32 broadcast) 5.2
+                          "bevr_attn_bwd_q": 22.6,   # + two ds_add_u64 12.6
+                          "bevr_attn_slab_bwd_q": 22.6,   # the same five instructions per key row and half (no window moves)
+                          "bevr_attn_bwd_k": 6.0}    # per-lane tap gathers: 3 reads per 4 rows and table column
+    roof_lds = []
+    if args.precision == "bf16":
+        for k, v in sorted(attn.items()):
+            if k not in LDS_CLK_PER_KEYROW:      # the cell kernels are not paced by per-pair LDS work
+                continue
+            prs = v["flops"] / (2.0 * 32 * N_MATMUL[k]) / (v["ms"] * 1e-3)
+            peak_prs = N_CU * CLOCK_HZ * 64.0 / LDS_CLK_PER_KEYROW[k]
+            roof_lds.append({"bound": "lds", "kernel": k, "achieved": round(prs, 0), "peak": round(peak_prs, 0),
+                             "unit": "pairs/s", "frac": round(prs / peak_prs, 4),
+                             "lds_clk_per_wave_keyrow": LDS_CLK_PER_KEYROW[k]})
+    # the HBM-bound kernels of the path (SURVEY 8d): bilinear feature sampling, forward and backward scatter.
+    # achieved = algorithmic (compulsory) bytes / launch time: feature map once + one row and one position per key
+    # (forward); + the map's gradient once (backward).  `traffic` = what the PMC counters saw (the backward's
+    # scatter is memory-side float atomics, 4 taps per key)
+    roof_hbm = []
+    # bevr_kv_project: sampling + K | V projection + operand packing in one pass (feature map in, packed operands out)
+    # bevr_corr_fwd / _bwd: the ground <-> aerial correlation of the retrieval losses (train.py:551-572,
+    # loss/contrastive_loss.py:10-19): at B = 8 a (16 x 2.56 M) embedding matrix against itself -- the Gram on the f32
+    # matrix cores, HBM-bound (SURVEY 8d: 82 MB per operand set read once; the backward reads it again and writes the
+    # gradient once)
+    # bevr_merge_views_fwd / _bwd: the attention output into proj_out's layout (+ the two segments' softmax merge)
+    for k in ("bevr_kv_project", "bevr_sample_fwd", "bevr_sample_bwd", "bevr_corr_fwd", "bevr_corr_bwd",
+              "bevr_merge_views_fwd", "bevr_merge_views_bwd"):
+        if k in ktimes and ktimes[k]["ms"] > 0:
+            v = ktimes[k]
+            gbs = v["bytes"] / (v["ms"] * 1e-3) / 1e9
+            roof_hbm.append({"bound": "hbm", "kernel": k, "achieved": round(gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": round(gbs / HBM_PEAK_GBS, 4), "traffic": traffic_db.get(k, {}).get("hbm_bytes_per_launch"),
+                             "avg_ms": round(v["ms"] / v["n"], 3), "max_ms": round(v["max_ms"], 3), "launches": v["n"],
+                             "algorithmic_bytes_per_launch": round(v["bytes"] / v["n"])})
+    out = {"roofline": roof, "roofline_hbm": roof_hbm, "roofline_lds": roof_lds}
+    if (S, args.frames, args.img) == (200, 2, "704x256") and B in BLOCK_HBM_BYTES_PER_SAMPLE:
+        # the block as a whole against HBM (north_star / SURVEY 8d): algorithmic bytes per sample x samples/s.  Small by
+        # construction: the block is compute-bound (arithmetic intensity ~1.6e5 flop/B)
+        gbs = BLOCK_HBM_BYTES_PER_SAMPLE[B] * samples_per_s / world / 1e9
+        out["roofline_hbm_block"] = {"bound": "hbm", "achieved": round(gbs, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                     "frac": round(gbs / HBM_PEAK_GBS, 6),
+                                     "bytes_per_sample": BLOCK_HBM_BYTES_PER_SAMPLE[B],
+                                     "note": "whole block per GPU, SURVEY 8d's algorithmic bytes; compute-bound, so small"}
+    return out
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, loss, model):
+    """What the timed path hands its caller after the last timed step, one float .npy file per array under `path`: the
+    loss (loss.npy, float64) and the gradient of every trained parameter (grad.<parameter name>.npy, float32).  At most
+    DUMP_LIMIT_BYTES in all: the budget is shared out smallest array first, and an array larger than its share is
+    stored as a fixed sample of its entries (flat indices drawn with seed 0, ascending), the same in every run with the
+    same arguments.  At the default shape every array is stored whole (25 MB)."""
+    arrays = {"loss": loss.detach().double().reshape(1).cpu().numpy()}
+    for name, p in model.named_parameters():
+        if p.grad is not None:
+            arrays["grad." + name] = p.grad.detach().float().cpu().numpy()
+    os.makedirs(path, exist_ok=True)
+    budget = DUMP_LIMIT_BYTES
+    items = sorted(arrays.items(), key=lambda kv: kv[1].nbytes)
+    for i, (name, a) in enumerate(items):
+        share = budget // (len(items) - i)
+        if a.nbytes > share:
+            idx = np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(path, name + ".npy"), a)
+        budget -= a.nbytes
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -296,14 +444,20 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--batch", type=int, default=8, help="samples per GPU (8 = BASELINE config 3, 4 = config 2)")
     ap.add_argument("--f32-steps", type=int, default=5,
-                    help="also time this many steps in the fp32-tolerance mode (split-bf16 products, bf16x3) and one in the "
+                    help="with --full: also time this many steps in the fp32-tolerance mode (split-bf16 products, bf16x3) and one in the "
                          "exact-f32 MFMA mode (rank 0, N=1; 0 = skip)")
     ap.add_argument("--bev", type=int, default=200, help="BEV side (200 = BASELINE config; smaller for debugging)")
     ap.add_argument("--frames", type=int, default=2, help="temporal frames T: T - 1 no-grad history frames + the current one")
     ap.add_argument("--img", default="704x256", help="camera image WxH (features are 1/4 of it); config 5: 1408x512")
     ap.add_argument("--precision", default="bf16", choices=["bf16", "f32", "f16", "bf16x3"])
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary figures: per-kernel times and rooflines, the bf16x3 / exact-f32 modes and the "
+                         "CPU baseline (a plain run times the headline steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's loss and gradients to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # bare `python bench.py --gpus N`: become the launcher.  Nothing has touched the GPU yet (importing torch does
@@ -338,7 +492,13 @@ def main():
     # identical initial weights on every rank (DDP broadcasts rank 0's); gradient buckets of a quarter of the gradient
     # volume (parallel.wrap_data_parallel): the all-reduces of the late layers run under the early layers' backward
     net = parallel.wrap_data_parallel(model, dev_index)
-    opt = torch.optim.AdamW([p for p in model.parameters() if p.requires_grad], lr=1e-4)
+    params = [p for p in model.parameters() if p.requires_grad]
+    opt = torch.optim.AdamW(params, lr=1e-4)
+    # every step, warm-up and timed, starts from these seeded weights (one multi-tensor device copy, ~26 MB): the
+    # backward's float atomics reorder sums from run to run, and AdamW's first updates (~ lr * sign(g)) turn rounding
+    # noise in near-zero gradient entries into +-lr weight changes -- a chain of steps would hand every later step
+    # inputs that differ from run to run.  This way each step is the same unit of work on the same inputs.
+    initial = [p.detach().clone() for p in params]
 
     gen = torch.Generator(device=dev).manual_seed(15213 + rank)
     # backbone features as the backbone hands them over: channels-last (the sampler's layout, no copy)
@@ -348,6 +508,8 @@ def main():
     map_emb = torch.nn.functional.normalize(torch.randn(B, C * S * S, device=dev, generator=gen), dim=1)
 
     def step():
+        with torch.no_grad():
+            torch._foreach_copy_(params, initial)
         opt.zero_grad(set_to_none=True)
         loss = net(feats[0], feats[1], map_emb, args.frames - 1)
         loss.backward()
@@ -362,111 +524,24 @@ def main():
     for _ in range(args.warmup):
         step()
     fence()
-    ops.KERNEL_TIMER.start()
+    if args.full:
+        ops.KERNEL_TIMER.start()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         loss = step()
     fence()
     dt = time.perf_counter() - t0
-    ktimes = ops.KERNEL_TIMER.stop()
+    ktimes = ops.KERNEL_TIMER.stop() if args.full else {}
     if world > 1:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
     assert math.isfinite(loss.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, loss, model)
 
     if rank == 0:
         total_samples = B * world * args.steps
-        # dominant kernel by accumulated device time inside the timed region (HIP events on its stream)
-        attn = {k: v for k, v in ktimes.items() if k.startswith("bevr_attn")}
-        dom = max(attn, key=lambda k: attn[k]["ms"]) if attn else None
-        roof = None
-        # HBM bytes per launch: measured with rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE on this very command (separate
-        # passes, gfx950 correction applied) by tools/measure_traffic.sh, which writes profiles/r05_traffic.json together
-        # with the kernel sources' sha; only attached when that file was measured at this batch / BEV side / precision
-        # AND on these very kernel sources (a stale file is not reported as measured traffic: ADVICE r02)
-        traffic_db, traffic_note = {}, "no profiles/r05_traffic.json for this batch / BEV side / precision"
-        tpath = os.path.join(ROOT, "profiles", "r05_traffic.json")
-        if os.path.exists(tpath):
-            with open(tpath) as fh:
-                tj = json.load(fh)
-            if tj.get("batch") == B and tj.get("bev") == S and tj.get("precision") == args.precision:
-                if tj.get("csrc_sha") == csrc_sha():
-                    traffic_db, traffic_note = tj["kernels"], f"measured at csrc_sha {tj.get('csrc_sha')}"
-                else:
-                    traffic_note = (f"profiles/r05_traffic.json was measured at csrc_sha {tj.get('csrc_sha')}, the kernels "
-                                    f"are at {csrc_sha()}: not attached")
-        if dom:
-            rec = attn[dom]
-            avg_ms = rec["ms"] / rec["n"]
-            flops = rec["flops"] / rec["n"]
-            ach = flops / (avg_ms * 1e-3) / 1e12
-            peak = MFMA_PEAK_TFLOPS[args.precision]
-            pairs = rec["flops"] / rec["n"] / (2.0 * 32 * N_MATMUL[dom])
-            roof = {"bound": "mfma", "kernel": dom, "achieved": round(ach, 3), "peak": peak, "unit": "TFLOP/s",
-                    "frac": round(ach / peak, 5), "traffic": traffic_db.get(dom, {}).get("hbm_bytes_per_launch"),
-                    "traffic_note": traffic_note, "avg_ms": round(avg_ms, 3), "launches": rec["n"],
-                    "pair_ops_per_s": round(pairs / (avg_ms * 1e-3), 0),
-                    "kernel_ms_per_step": {k: round(v["ms"] / args.steps, 2) for k, v in sorted(ktimes.items())},
-                    "all_attention": {k: {"avg_ms": round(v["ms"] / v["n"], 3),
-                                          "frac": round(v["flops"] / (v["ms"] * 1e-3) / 1e12 / peak, 5)}
-                                      for k, v in sorted(attn.items())}}
-            # every attention launch of the timed region together, on SURVEY 8d's accounting (7 products per pair forward +
-            # backward); `executed`: the 9 products the two-sided backward runs (S and dP on both sides)
-            tot_ms = sum(v["ms"] for v in attn.values())
-            tot_exec = sum(v["flops"] for v in attn.values())
-            tot_alg = sum(v["flops"] / N_MATMUL[k] * ALG_MATMUL[k] for k, v in attn.items())
-            roof["all_attention_aggregate"] = {"achieved": round(tot_alg / (tot_ms * 1e-3) / 1e12, 3), "unit": "TFLOP/s",
-                                               "frac": round(tot_alg / (tot_ms * 1e-3) / 1e12 / peak, 5),
-                                               "accounting": "SURVEY 8d: 2 products per pair forward, 5 backward",
-                                               "executed": {"achieved": round(tot_exec / (tot_ms * 1e-3) / 1e12, 3),
-                                                            "frac": round(tot_exec / (tot_ms * 1e-3) / 1e12 / peak, 5)},
-                                               "ms_per_step": round(tot_ms / args.steps, 2)}
-            # per call: TSA (square table) and SCA (the scattered keys on the region kernels, the pinned ones on the tap
-            # kernels) separately -- kernel_ms_per_step lumps them
-            roof["kernel_ms_per_step_by_call"] = {k: {"ms_per_step": round(v["ms"] / args.steps, 2), "launches": v["n"],
-                                                      "avg_ms": round(v["ms"] / v["n"], 3),
-                                                      "Tpairs_per_s": round(v["flops"] / (2.0 * 32 * N_MATMUL[k.split("[")[0]]) / (v["ms"] * 1e-3) / 1e12, 3)}
-                                                  for k, v in sorted(ops.KERNEL_TIMER.by_tag.items()) if k.startswith("bevr_attn")}
-        # What actually paces the attention kernels is per-pair work on the LDS pipe (bias taps, per-key constants, the
-        # table-gradient atomics), not the matrix cores.  Secondary, clearly separate from
-        # `roofline`: the pair rate against the rate at which one CU's LDS pipe could issue each kernel's LDS
-        # instructions back to back (clk per wave and key row = per 64 pairs, from the measured instruction costs in
-        # profiles/r02_lds_*.txt; bf16 mode).
-        LDS_CLK_PER_KEYROW = {"bevr_attn_fwd": 10.0,     # taps 4.8 + constants (b64 + b32 broadcast) 5.2
-                              "bevr_attn_bwd_q": 22.6,   # + two ds_add_u64 12.6
-                              "bevr_attn_slab_bwd_q": 22.6,   # the same five instructions per key row and half (no window moves)
-                              "bevr_attn_bwd_k": 6.0}    # per-lane tap gathers: 3 reads per 4 rows and table column
-        roof_lds = []
-        if args.precision == "bf16":
-            for k, v in sorted(attn.items()):
-                if k not in LDS_CLK_PER_KEYROW:      # the cell kernels are not paced by per-pair LDS work
-                    continue
-                prs = v["flops"] / (2.0 * 32 * N_MATMUL[k]) / (v["ms"] * 1e-3)
-                peak_prs = N_CU * CLOCK_HZ * 64.0 / LDS_CLK_PER_KEYROW[k]
-                roof_lds.append({"bound": "lds", "kernel": k, "achieved": round(prs, 0), "peak": round(peak_prs, 0),
-                                 "unit": "pairs/s", "frac": round(prs / peak_prs, 4),
-                                 "lds_clk_per_wave_keyrow": LDS_CLK_PER_KEYROW[k]})
-        # the HBM-bound kernels of the path: bilinear feature sampling, forward and backward scatter.
-        # achieved = algorithmic (compulsory) bytes / launch time: feature map once + one row and one position per key
-        # (forward); + the map's gradient once (backward).  `traffic` = what the PMC counters saw (the backward's
-        # scatter is memory-side float atomics, 4 taps per key)
-        roof_hbm = []
-        # bevr_kv_project: sampling + K | V projection + operand packing in one pass (feature map in, packed operands out)
-        # bevr_corr_fwd / _bwd: the ground <-> aerial correlation of the retrieval losses (train.py:551-572,
-        # loss/contrastive_loss.py:10-19): at B = 8 a (16 x 2.56 M) embedding matrix against itself -- the Gram on the f32
-        # matrix cores, HBM-bound (82 MB per operand set read once; the backward reads it again and writes the
-        # gradient once)
-        # bevr_merge_views_fwd / _bwd: the attention output into proj_out's layout (+ the two segments' softmax merge)
-        for k in ("bevr_kv_project", "bevr_sample_fwd", "bevr_sample_bwd", "bevr_corr_fwd", "bevr_corr_bwd",
-                  "bevr_merge_views_fwd", "bevr_merge_views_bwd"):
-            if k in ktimes and ktimes[k]["ms"] > 0:
-                v = ktimes[k]
-                gbs = v["bytes"] / (v["ms"] * 1e-3) / 1e9
-                roof_hbm.append({"bound": "hbm", "kernel": k, "achieved": round(gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                 "frac": round(gbs / HBM_PEAK_GBS, 4), "traffic": traffic_db.get(k, {}).get("hbm_bytes_per_launch"),
-                                 "avg_ms": round(v["ms"] / v["n"], 3), "max_ms": round(v["max_ms"], 3), "launches": v["n"],
-                                 "algorithmic_bytes_per_launch": round(v["bytes"] / v["n"])})
         out = {
             "metric": "samples/sec fwd+bwd, 6-cam 256x704 BEV-lift+corr",
             "value": round(total_samples / dt, 4), "unit": "samples/s", "n_gpus": world, "steps": args.steps,
@@ -481,17 +556,10 @@ def main():
                                    f"contrastive + lifted-structure losses, AdamW; "
                                    f"batch {B} per GPU; backbone/render CNN excluded",
                        "global_batch": B * world, "per_gpu_batch": B, "parallelism": f"dp{world}"},
-            "roofline": roof, "roofline_hbm": roof_hbm, "roofline_lds": roof_lds,
         }
-        if (S, args.frames, args.img) == (200, 2, "704x256") and B in BLOCK_HBM_BYTES_PER_SAMPLE:
-            # the block as a whole against HBM (north_star / SURVEY 8d): algorithmic bytes per sample x samples/s.  Small by
-            # construction: the block is compute-bound (arithmetic intensity ~1.6e5 flop/B)
-            gbs = BLOCK_HBM_BYTES_PER_SAMPLE[B] * (total_samples / dt) / world / 1e9
-            out["roofline_hbm_block"] = {"bound": "hbm", "achieved": round(gbs, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                         "frac": round(gbs / HBM_PEAK_GBS, 6),
-                                         "bytes_per_sample": BLOCK_HBM_BYTES_PER_SAMPLE[B],
-                                         "note": "whole block per GPU, SURVEY 8d's algorithmic bytes; compute-bound, so small"}
-        if world == 1 and args.f32_steps > 0 and args.precision == "bf16":
+        if args.full:
+            out.update(roofline_figures(ktimes, args, B, S, world, total_samples / dt))
+        if args.full and world == 1 and args.f32_steps > 0 and args.precision == "bf16":
             # the reference's arithmetic is fp32: the same workload in the kernels' exact-f32 MFMA mode, as a secondary
             # figure (never `value`)
             del net, opt, model
@@ -535,7 +603,7 @@ def main():
                                       "limits); peak = bf16 dense / 3")
             out["f32_mode"] = dict(timed_mode("f32", 1), note="exact-f32 MFMA operands (v_mfma_f32_32x32x2_f32), the "
                                    "tests' reference mode and the reference's arithmetic; peak = the f32 matrix rate")
-        if not args.no_cpu_baseline and world == 1:   # rank 0 at N = 1 only (bench contract)
+        if args.full and not args.no_cpu_baseline and world == 1:   # rank 0 at N = 1 only (bench contract)
             torch.cuda.empty_cache()
             same = gpu_same_workloads(dev)
             out["cpu_baseline"] = cpu_baseline()

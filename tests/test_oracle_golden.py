@@ -33,6 +33,20 @@ def check_grads(z, p, inputs, rtol, atol):
             np.testing.assert_allclose(g.numpy(), v, rtol=rtol, atol=atol, err_msg=k)
 
 
+def _mkl_on_intel_avx512():
+    """The CPU kernel path the goldens were recorded on and the bit-exact checks hold on: MKL on an Intel CPU with
+    AVX-512.  MKL picks its GEMM and matrix-inverse kernels by CPU vendor, instruction set and operand shape (on AMD
+    CPUs MKL_CBWR does not pin them), so elsewhere the same float op sequence rounds a few elements differently."""
+    try:
+        with open("/proc/cpuinfo") as fh:
+            intel = "GenuineIntel" in fh.read()
+    except OSError:
+        intel = False
+    return intel and torch.backends.mkl.is_available() and torch.backends.cpu.get_cpu_capability() == "AVX512"
+
+
+EXACT_BLAS = _mkl_on_intel_avx512()
+
 TSA = sorted(os.path.basename(f) for f in glob.glob(os.path.join(GOLDEN, "tsa_*.npz")))
 SCA = sorted(os.path.basename(f) for f in glob.glob(os.path.join(GOLDEN, "sca_*.npz")))
 PROJ = sorted(os.path.basename(f) for f in glob.glob(os.path.join(GOLDEN, "proj_*.npz")))
@@ -76,7 +90,10 @@ def test_projector_matches_reference_bit_exact(name):
     np.testing.assert_array_equal(pts.numpy(), z["points_3d"])
     p2 = O.bev_grid_to_camera(pts, list(z["imu_to_rgb"]), list(z["K"]), iw, ih, ow, oh)
     got = torch.stack(p2, 0).numpy()
-    np.testing.assert_array_equal(got, z["points_2d"])
+    if EXACT_BLAS:
+        np.testing.assert_array_equal(got, z["points_2d"])
+    else:   # a few float32 ulps of the pixel coordinates, scaled to [-1, 1]; a point flipping the mask moves by ~1
+        np.testing.assert_allclose(got, z["points_2d"], rtol=0, atol=1e-6)
     # the fixture exercises the mask: some points are pinned to (-1, -1)
     masked = np.all(z["points_2d"] == -1.0, axis=1).mean()
     assert 0.0 < masked < 1.0
@@ -216,7 +233,10 @@ def test_streaming_and_row_subset_forms_equal_the_materialised_core():
         np.testing.assert_allclose(stream.numpy(), full.numpy(), rtol=0, atol=1e-12)
         rows = torch.tensor([0, 5, M - 1, 7])
         sub = O.attention_core(q, k, v, pos, tab, S, S, g, c ** -0.5, rows=rows)
-        np.testing.assert_array_equal(sub.numpy(), full[:, :, rows].numpy())
+        if EXACT_BLAS:
+            np.testing.assert_array_equal(sub.numpy(), full[:, :, rows].numpy())
+        else:   # the 4-row products may run on another BLAS kernel than the 36-row ones: rounding of <= 70-term sums
+            np.testing.assert_allclose(sub.numpy(), full[:, :, rows].numpy(), rtol=0, atol=1e-14)
 
 
 def test_ego_motion_warp_restatement_properties():
