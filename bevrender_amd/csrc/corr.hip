@@ -109,11 +109,12 @@ __global__ void finish_dist_kernel(float* D, const float* inc, const float* inm,
 // dX[i][e] = sum_j W[i][j] * Y[j][e] (+ optional  coef[i] * X[i][e]);  used for both sides of the backward.
 //   raw:        dcam_i = -2 sum_j dD_ij map_j
 //   normalised: dcam_i = -2/|c_i| ( sum_j dD_ij m^_j  -  (sum_j dD_ij <c^_i, m^_j>) c^_i )
+// accumulate: dX += instead of dX = (the second side of an aliased call, cam == map, adds onto the first's dcam)
 __global__ __launch_bounds__(256) void corr_bwd_kernel(const float* __restrict__ X, const float* __restrict__ Y,
                                                        const float* __restrict__ W, const float* __restrict__ Dm,
                                                        const float* __restrict__ inx, const float* __restrict__ iny,
                                                        float* __restrict__ dX, int nx, int ny, int E, int transposed,
-                                                       int normalize) {
+                                                       int normalize, int accumulate) {
   // grid (E chunks of 1024, nx rows)
   const int i = blockIdx.y;
   const long long e = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
@@ -135,7 +136,8 @@ __global__ __launch_bounds__(256) void corr_bwd_kernel(const float* __restrict__
     if (e + q < E) {
       float v = accv[q];
       if (normalize) v -= self * X[(size_t)i * E + e + q] * sx;
-      dX[(size_t)i * E + e + q] = -2.0f * sx * v;
+      const size_t o = (size_t)i * E + e + q;
+      dX[o] = (accumulate ? dX[o] : 0.0f) - 2.0f * sx * v;
     }
 }
 
@@ -418,11 +420,12 @@ extern "C" int bevr_corr_bwd(const float* cam, const float* map, const float* D,
   if (n <= 0 || m <= 0 || E <= 0) return BEVR_E_SHAPE;
   hipStream_t st = (hipStream_t)stream;
   const int chunks = (E + 1023) / 1024;
+  // cam == map and n == m (the retrieval losses correlate one embedding matrix with itself): dcam receives BOTH sides'
+  // sum and dmap is neither read nor written, on either path below (include/bevrender_hip.h)
+  const bool same = cam == map && n == m;
   if (n <= CORR_MAX_ROWS && m <= CORR_MAX_ROWS && (E & 3) == 0 && bevr_aligned16(cam) && bevr_aligned16(map) &&
       bevr_aligned16(dcam) && bevr_aligned16(dmap)) {
-    // cam == map (the retrieval losses correlate one embedding matrix with itself): dcam receives BOTH sides' sum and
-    // dmap is not written -- bevrender_amd/ops.py hands the sum to autograd once
-    if (cam == map && n == m)
+    if (same)
       hipLaunchKernelGGL((corr_bwd_slice_kernel<true>), dim3(chunks), dim3(256), 0, st, cam, map, dD, D, inv_norm_cam,
                          inv_norm_map, dcam, dmap, n, m, E, normalize);
     else
@@ -431,9 +434,10 @@ extern "C" int bevr_corr_bwd(const float* cam, const float* map, const float* D,
     return (int)hipGetLastError();
   }
   hipLaunchKernelGGL(corr_bwd_kernel, dim3(chunks, n), dim3(256), 0, st, cam, map, dD, D, inv_norm_cam, inv_norm_map,
-                     dcam, n, m, E, 0, normalize);
+                     dcam, n, m, E, 0, normalize, 0);
+  // aliased: the map side's rows are the cam side's; stream order puts this launch after the first one's writes
   hipLaunchKernelGGL(corr_bwd_kernel, dim3(chunks, m), dim3(256), 0, st, map, cam, dD, D, inv_norm_map, inv_norm_cam,
-                     dmap, m, n, E, 1, normalize);
+                     same ? dcam : dmap, m, n, E, 1, normalize, same ? 1 : 0);
   return (int)hipGetLastError();
 }
 

@@ -1225,7 +1225,17 @@ class _Corr(torch.autograd.Function):
     @staticmethod
     def forward(ctx, cam, mp, normalize: bool):
         _require_gpu(cam, mp)
-        cam, mp = cam.float().contiguous(), mp.float().contiguous()
+        # one autograd input passed as both arguments (the retrieval losses: pairwise_corr(emb, emb)) with both gradients
+        # wanted: the backward may hand autograd the two sides' sum once.  Anything else -- a detached alias, one side
+        # without a gradient, two tensors on one buffer -- keeps the sides apart
+        ctx.summed = cam is mp and ctx.needs_input_grad[0] and ctx.needs_input_grad[1]
+        alias = cam is mp
+        cam = cam.float().contiguous()
+        if cam.data_ptr() % 16:     # the one-pass kernels read rows as 16-byte vectors: a view off that grid is copied
+            cam = cam.clone()
+        mp = cam if alias else mp.float().contiguous()
+        if mp.data_ptr() % 16:
+            mp = mp.clone()
         n, E = cam.shape
         m = mp.shape[0]
         D = torch.empty(n, m, device=cam.device, dtype=torch.float32)
@@ -1244,16 +1254,22 @@ class _Corr(torch.autograd.Function):
         cam, mp, D, inc, inm = ctx.saved_tensors
         n, E = cam.shape
         m = mp.shape[0]
-        dcam, dmap = torch.empty_like(cam), torch.empty_like(mp)
+        # bevr_corr_bwd with cam == map (one pointer, n == m) writes the two sides' SUM into dcam and leaves dmap alone
+        # (include/bevrender_hip.h).  That is the gradient wanted only when it is summed anyway (ctx.summed); a call whose
+        # two arguments merely share a buffer gets a copy of one side, so that the kernels keep the sides apart
+        same = cam.data_ptr() == mp.data_ptr() and n == m
+        if same and not ctx.summed:
+            mp, same = mp.clone(), False
+        dcam = torch.empty_like(cam)
+        dmap = dcam if same else torch.empty_like(mp)
         # algorithmic (compulsory) HBM bytes: both operands read once, both gradients written once; one matrix correlated
         # with itself (the retrieval losses): read once, and the two sides' SUM written once (csrc/corr.hip)
-        same = cam.data_ptr() == mp.data_ptr() and n == m and n <= 64 and E % 4 == 0
         _lib.check(KERNEL_TIMER.run("bevr_corr_bwd", 0.0, _lib.lib().bevr_corr_bwd, _ptr(cam), _ptr(mp), _ptr(D),
                                     _ptr(dD.contiguous()), _ptr(inc), _ptr(inm), _ptr(dcam), _ptr(dmap), n, m, E,
                                     int(ctx.normalize), _stream(), nbytes=4.0 * E * (2 * n if same else 2 * (n + m))),
                    "bevr_corr_bwd")
-        # same: dcam holds d/dcam + d/dmap (one gradient for the one tensor both arguments are)
-        return dcam, (None if same else dmap), None
+        # summed (forward: one buffer for both sides, so `same`): dcam is the one input's whole gradient, handed over once
+        return (dcam, None, None) if ctx.summed else (dcam, dmap, None)
 
 
 def pairwise_corr(cam: torch.Tensor, mp: torch.Tensor, normalize: bool = False) -> torch.Tensor:

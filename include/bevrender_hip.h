@@ -51,6 +51,10 @@ extern "C" {
  *    table: a workgroup owns a slab of table columns); bevr_attn_tap_bwd_k's table operand is declared as what it always
  *    was (the plain packed table, not the pair table); bevr_kv_project takes the channel-group count (before `stream`);
  *    nothing else changed. */
+/* 6: bevr_kv_project takes `float* knorm2_max` (the largest squared K row norm per problem and head) before `groups`;
+ *    new entry points bevr_merge_views_fwd / _bwd, bevr_merge_tap_fwd / _bwd, bevr_attn_bwd_prep and
+ *    bevr_dwconv_res_gelu; bevr_corr_bwd with aliased operands (cam == map, n == m) writes both sides' sum into dcam and
+ *    leaves dmap untouched, on every path (see its declaration); nothing else changed. */
 #define BEVR_ABI_VERSION 6
 
 enum {
@@ -372,6 +376,9 @@ int bevr_project_bev_grid_masked(const float* points_3d, const float* cam_inv, c
  *   normalize != 0: rows are L2-normalised first (the LpDistance(normalize_embeddings=True) of the
  *   retrieval losses); inv_norm_cam [n], inv_norm_map [m] receive 1/||row|| for the backward.
  * backward: dcam [n][E], dmap [m][E] written from dD [n][m].
+ *   Aliased operands, cam == map (the same pointer) and n == m: dcam receives the SUM of both sides' gradients (the
+ *   gradient of the one matrix both arguments are) and dmap is neither read nor written -- the same for every n, m, E
+ *   and alignment.  A caller that wants the two sides apart passes two buffers (a copy of one side).
  * ---------------------------------------------------------------------------------------------- */
 int bevr_corr_fwd(const float* cam, const float* map, float* D, float* inv_norm_cam, float* inv_norm_map,
                   int n, int m, int E, int normalize, void* stream);

@@ -1,0 +1,324 @@
+"""Seeded random sweep of attention_core ROUTE by route against one float64 oracle per configuration: explicit K | V with
+a cell segment (cell-sorted or not, split anywhere in [0, N]), explicit K | V on the region kernels alone in the modes the
+plain sweep skips, the fused K | V source (channel groups, f32 or bf16 feature maps, with and without a cell segment), and
+the pinned-key tap route of the benchmarked SCA call (kv_source + cell_split + tap_source, split 0 included).  Forward and
+every input's gradient; each case asserts the kernels its route must run (ops.KERNEL_TIMER; merge_tap through a spy), so
+no case passes on a fall-back route.  BEVR_SWEEP=n widens it (n configurations per route and mode)."""
+import os
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from bevrender_amd import _lib, ops
+from test_gpu_fullsize import kink_distance
+from test_gpu_ops import GRAD_LIM, _oracle_core, rel_err
+from oracle import bevrender_oracle as O
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+NSEED = int(os.environ.get("BEVR_SWEEP", "6"))
+F32, X3, BF16, F16 = _lib.PREC_F32, _lib.PREC_BF16X3, _lib.PREC_BF16, _lib.PREC_F16
+
+# forward, max-norm relative: the plain sweep's limits (tests/test_gpu_random_sweep.py) for F32 / BF16; BF16X3 is held to
+# F32's everywhere; F16 takes TOL[F16]'s rtol (tests/test_gpu_ops.py) scaled as the plain sweep scales BF16's (2.5 / 3)
+OUT_LIM = {F32: 2e-4, X3: 2e-4, BF16: 2.5e-2, F16: 5e-3}
+# tap route: the limits of tests/test_gpu_tap.py (bf16: rtol 3e-2 forward, 3e-2 every gradient; fp16: 2.5e-3 / 5e-3)
+TAP_OUT_LIM = {BF16: 2.5e-2, F16: 2.5e-3}
+TAP_GRAD_LIM = {BF16: 3e-2, F16: 5e-3}
+# d(pos) in the 2-norm away from kinks: the plain sweep's limits; F16 = BF16's scaled by GRAD_LIM's F16 / BF16 ratio
+# (1 / 5 -- fp16's significand is 3 bits longer, the operand rounding 8x smaller)
+POS_LIM = {F32: 5e-3, X3: 5e-3, BF16: 6e-2, F16: 1.2e-2}
+# unit roundoff of the operands, for the term bounds (gradient_terms) of clustered / pinned keys; BF16X3: each operand
+# hi + lo with the lo * lo product dropped, 2^-16 of a term
+UNIT = {F32: 2.0 ** -24, X3: 2.0 ** -16, BF16: 2.0 ** -8, F16: 2.0 ** -11}
+
+ROUTE_MODES = [("kv_cell", p) for p in (F32, X3, BF16, F16)] + [("kv_region", p) for p in (X3, F16)] \
+    + [("kv_source", p) for p in (BF16, F16)] + [("tap", p) for p in (BF16, F16)]
+MODE_NAME = {F32: "f32", X3: "bf16x3", BF16: "bf16", F16: "f16"}
+
+
+def key_positions(N, P, kind, gen):
+    u = torch.rand(P, N, 2, generator=gen)
+    if kind == 0:      # inside the grid
+        return u * 2 - 1
+    if kind == 1:      # well outside too (clamped taps, zero bias; zero-padded samples)
+        return (u * 2 - 1) * 1.6
+    if kind == 2:      # one tight cluster (pinned-key case)
+        return -0.97 + 0.02 * u
+    return torch.where(torch.arange(N)[None, :, None] % 2 == 0, -0.8 + 0.05 * u, 0.7 + 0.05 * u)
+
+
+def cell_sort(pos, S, Wt, split, g):
+    """the permutation of keys [split, N) that cell-sorts group 0's positions (one order for every group: a key is one row
+    of K and V), as a (P, N) index into the keys."""
+    P = pos.shape[0] // g
+    N = pos.shape[1]
+    p0 = pos.reshape(P, g, N, 2)[:, 0]
+    a, b = ops.key_coords(p0[:, split:], S, Wt, N - split)
+    order = ops.cell_order(a, b) + split
+    return torch.cat((torch.arange(split)[None].expand(P, -1), order), 1)
+
+
+def draw(route, prec, seed):
+    """One configuration of `route`, redrawn until the route can take it (no silent fall-back)."""
+    for t in range(1000):
+        r = np.random.RandomState(10007 * seed + 131 * prec + {"kv_cell": 0, "kv_region": 1, "kv_source": 2, "tap": 3}[route] + 7919 * t)
+        h = int(r.choice([1, 2, 4]))
+        c = int(r.choice([8, 16, 32]))
+        V = int(r.choice([1, 1, 2, 3]))
+        B = int(r.choice([1, 2]))
+        cfg = dict(route=route, prec=prec, h=h, C=h * c, V=V, B=B, concat=bool(r.randint(0, 2)),
+                   cs=float(r.choice([1.0, 1e-5])) if prec == F16 else 1.0, sorted=True, feat_bf16=False, kind=0)
+        if route == "tap":
+            S = int(r.choice([4, 6, 8, 12, 16, 17, 20, 33, 34]))
+            D = int(r.choice([1, 2, 3]))
+            Hk, Wk = S // 2, S * D
+            if Hk < 2 or Wk < 2:
+                continue
+            # the tap contract (SCADeformableAttention._pinned_keys_tap): 2.5 (Hi - 1) / (Hk - 1) < 3 and
+            # 2.5 (Wi - 1) / (Wk - 1) < 2 -- or an image inside the 4 x 3 tap grid (sides >= 2: bevr_kv_project's contract)
+            if r.randint(0, 3) == 0:
+                Hi, Wi = int(r.randint(2, ops.TAP_R + 1)), int(r.randint(2, ops.TAP_C + 1))
+            else:
+                # the largest sides that keep the bound 1e-3 inside the grid (as _pinned_keys_tap checks it), capped
+                hi_max = min(48, max(ops.TAP_R, int(np.ceil(1 + (ops.TAP_R - 1 - 1e-3) * (Hk - 1) / 2.5)) - 1))
+                wi_max = min(48, max(ops.TAP_C, int(np.ceil(1 + (ops.TAP_C - 1 - 1e-3) * (Wk - 1) / 2.5)) - 1))
+                Hi, Wi = int(r.randint(ops.TAP_R, hi_max + 1)), int(r.randint(ops.TAP_C, wi_max + 1))
+            N = Hk * Wk
+            n_pin = int(r.choice([N, N, int(r.randint(1, N + 1)), int(r.randint(1, N + 1)), 64 * max(1, N // 128)]))
+            cfg.update(S=S, D=D, N=N, g=1, Hi=Hi, Wi=Wi, split=N - min(n_pin, N), feat_bf16=bool(r.randint(0, 2)))
+            if not (ops.kv_source_supported(cfg["C"], h, 1, prec) and ops.tap_supported(prec, 1)):
+                continue
+            return cfg
+        S = int(r.choice([3, 5, 8, 13, 17, 21, 31, 32, 33, 40]))
+        D = int(r.choice([1, 2, 3, 5, 9]))
+        # (one key, N = 1: P = 1 and most gradients are rounding noise of zero -- tests/test_gpu_random_sweep.py covers it)
+        N = int(r.choice([7, 31, 32, 33, 63, 64, 65, 127, 200, 383, 384, 385, 450]))
+        g = int(r.choice([d for d in (1, 2, 4) if h % d == 0])) if route == "kv_source" else \
+            int(r.choice([d for d in (1, 2) if h % d == 0]))
+        kind = int(r.randint(0, 4))
+        split = N
+        if route in ("kv_cell", "kv_source") and (route == "kv_cell" or r.randint(0, 2)):
+            split = int(r.choice([0, N, int(r.randint(0, N + 1)), int(r.randint(0, N + 1))]))
+        cfg.update(S=S, D=D, N=N, g=g, kind=kind, split=split, sorted=bool(r.randint(0, 4) != 0))
+        if route == "kv_source":
+            cfg.update(Hi=int(r.randint(2, 20)), Wi=int(r.randint(2, 24)), feat_bf16=bool(r.randint(0, 2)))   # sides >= 2
+            if not ops.kv_source_supported(cfg["C"], h, g, prec):
+                continue
+        return cfg
+    raise AssertionError("no configuration drawn")
+
+
+def make(cfg, seed):
+    """inputs as the route takes them (float32, CPU) and the cell-sorting permutation already applied."""
+    gen = torch.Generator().manual_seed(seed)
+    B, V, C, h, g, S, D, N = (cfg[k] for k in ("B", "V", "C", "h", "g", "S", "D", "N"))
+    Wt = 2 * S * D - 1
+    P = B * V
+    query = torch.randn(B, C, S, S, generator=gen)
+    table = torch.randn(h, 2 * S - 1, Wt, generator=gen) * 0.3
+    if cfg["route"] == "tap":
+        # tests/test_gpu_tap.py _tap_problem: keys [0, split) scattered over the image, [split, N) pinned to pixel (0, 0)
+        # and moved by offsets inside the learned range, cell-sorted
+        Hk, Wk = S // 2, S * D
+        n_pin = N - cfg["split"]
+        feat = torch.randn(P, cfg["Hi"], cfg["Wi"], C, generator=gen)
+        Wkv = torch.randn(2 * C, C, generator=gen) * C ** -0.5
+        bkv = torch.randn(2 * C, generator=gen) * 0.3
+        scat = (torch.rand(P, N - n_pin, 2, generator=gen) * 2 - 1) * 1.05
+        off = torch.tanh(torch.randn(P, n_pin, 2, generator=gen) * 1.5) * torch.tensor([5.0 / (Hk - 1), 5.0 / (Wk - 1)])
+        pin = off - 1.0
+        a, b = ops.key_coords(pin, S, Wt, n_pin)
+        pin = pin.gather(1, ops.cell_order(a, b)[..., None].expand(-1, -1, 2))
+        pos = torch.cat((scat, pin), 1)
+        if cfg["feat_bf16"]:
+            feat = feat.to(torch.bfloat16)
+        return dict(query=query, feat=feat, Wkv=Wkv, bkv=bkv, pos=pos, table=table)
+    pos = key_positions(N, P * g, cfg["kind"], gen)
+    if cfg["route"] == "kv_source":
+        feat = torch.randn(P, cfg["Hi"], cfg["Wi"], C, generator=gen)
+        Wkv = torch.randn(2 * C, C, generator=gen) * C ** -0.5
+        bkv = torch.randn(2 * C, generator=gen) * 0.3
+        if cfg["split"] < N and cfg["sorted"]:
+            idx = cell_sort(pos, S, Wt, cfg["split"], g).repeat_interleave(g, 0)
+            pos = pos.gather(1, idx[..., None].expand(-1, -1, 2))
+        if cfg["feat_bf16"]:
+            feat = feat.to(torch.bfloat16)
+        return dict(query=query, feat=feat, Wkv=Wkv, bkv=bkv, pos=pos, table=table)
+    k = torch.randn(P, N, C, generator=gen)
+    v = torch.randn(P, N, C, generator=gen)
+    if cfg["split"] < N and cfg["sorted"]:
+        idx = cell_sort(pos, S, Wt, cfg["split"], g)
+        k = k.gather(1, idx[..., None].expand(-1, -1, C))
+        v = v.gather(1, idx[..., None].expand(-1, -1, C))
+        pos = pos.gather(1, idx.repeat_interleave(g, 0)[..., None].expand(-1, -1, 2))
+    return dict(query=query, k=k, v=v, pos=pos, table=table)
+
+
+def chain_kv(feat, Wkv, bkv, pos, g):
+    """K, V of the fused source in the oracle's arithmetic: group gi's channels grid-sampled (bilinear, align_corners,
+    zeros) at group gi's positions, then proj_k | proj_v."""
+    P, Hi, Wi, C = feat.shape
+    N = pos.shape[1]
+    f = feat.permute(0, 3, 1, 2).reshape(P * g, C // g, Hi, Wi)
+    xs = F.grid_sample(f, pos[:, None, :, (1, 0)], mode="bilinear", padding_mode="zeros", align_corners=True)
+    xs = xs.reshape(P, g, C // g, N).permute(0, 3, 1, 2).reshape(P, N, C)
+    kv = F.linear(xs, Wkv, bkv)
+    return kv[..., :C], kv[..., C:]
+
+
+def gradient_terms(ins, cot, h, g, V):
+    """(table, query): per element, the sum over (query, key) of the magnitudes of the terms whose signed sum is the
+    table gradient (sum w dS, w >= 0 the bilinear taps) and d(query) (c^-0.5 sum dS K), in float64.  A term's magnitude
+    is |dS| plus P (A + sum_m P_m A_m), A[q, n] = sum_c |dO[q, c]| |V[n, c]|: the bound of what the 16-bit roundings of
+    dO and V do to dP - delta.  Keys sampled from one tight cluster of feature pixels have nearly equal K and V rows:
+    dP - delta and sum_n dS K are then differences of nearly equal numbers, the roundings apply to the TERMS
+    (tests/test_gpu_random_sweep.py table_gradient_terms: the same bound with the |dS| part alone)."""
+    query, k, v, pos, table = [t.detach() for t in ins]
+    B, C, S, _ = query.shape
+    c = C // h
+    Bp, N, _ = k.shape
+    M = S * S
+    tab = table.clone().requires_grad_(True)
+    q_grid = O.normalized_grid(S, S, torch.float64).reshape(1, M, 2)
+    dq = torch.zeros(B, h, c, M, dtype=torch.float64)
+    total = 0.0
+    for bp in range(Bp):
+        q = query[bp // V].reshape(h, c, M)
+        kk = k[bp].reshape(N, h, c).permute(1, 2, 0)
+        vv = v[bp].reshape(N, h, c).permute(1, 2, 0)
+        disp = (q_grid.unsqueeze(2) - pos[bp * g:(bp + 1) * g].reshape(g, 1, N, 2)) * 0.5
+        bias = F.grid_sample(tab.reshape(g, h // g, *tab.shape[-2:]), disp[..., (1, 0)], mode="bilinear",
+                             align_corners=True).reshape(h, M, N)
+        P = torch.softmax(torch.einsum("bcm,bcn->bmn", q, kk) * c ** -0.5 + bias.detach(), dim=2)
+        dO = cot[bp].t().reshape(h, c, M)
+        dP = torch.einsum("bcm,bcn->bmn", dO, vv)
+        dS = P * (dP - (P * dP).sum(2, keepdim=True))
+        A = torch.einsum("bcm,bcn->bmn", dO.abs(), vv.abs())
+        mag = dS.abs() + P * (A + (P * A).sum(2, keepdim=True))
+        total = total + (bias * mag).sum()
+        dq[bp // V] += c ** -0.5 * torch.einsum("bmn,bcn->bcm", mag, kk.abs())
+    total.backward()
+    return tab.grad, dq.reshape(B, C, S, S)
+
+
+def pixel_kink_distance(pos, Hi, Wi):
+    """how close a key's sampling position comes to an integer pixel coordinate: the bilinear sample's derivative with
+    respect to the position jumps there (the fused source's share of d(pos))."""
+    y = (pos[..., 0].double() + 1) * 0.5 * (Hi - 1)
+    x = (pos[..., 1].double() + 1) * 0.5 * (Wi - 1)
+    return torch.minimum((y - y.round()).abs(), (x - x.round()).abs())
+
+
+@pytest.mark.parametrize("seed", list(range(NSEED)))
+@pytest.mark.parametrize("route,prec", ROUTE_MODES, ids=[f"{r}-{MODE_NAME[p]}" for r, p in ROUTE_MODES])
+def test_route_random_configuration(route, prec, seed, monkeypatch):
+    cfg = draw(route, prec, seed)
+    run_case(cfg, 2000 + 97 * seed + prec, monkeypatch)
+
+
+def run_case(cfg, seed, monkeypatch):
+    route, prec = cfg["route"], cfg["prec"]
+    B, V, C, h, g, S, D, N, split = (cfg[k] for k in ("B", "V", "C", "h", "g", "S", "D", "N", "split"))
+    Wt = 2 * S * D - 1
+    M = S * S
+    ins = make(cfg, seed)
+    names = list(ins)
+    fused = "feat" in ins
+    tag = f"{cfg}"
+
+    # ---- float64 oracle ----
+    cpu = {n: t.clone().double().requires_grad_(True) for n, t in ins.items()}
+    if fused:
+        k64, v64 = chain_kv(cpu["feat"], cpu["Wkv"], cpu["bkv"], cpu["pos"], g)
+    else:
+        k64, v64 = cpu["k"], cpu["v"]
+    want = _oracle_core(cpu["query"], k64, v64, cpu["pos"], cpu["table"], h, g, V)      # (B V, M, C)
+    cot = torch.randn(want.shape, generator=torch.Generator().manual_seed(seed + 1), dtype=torch.float64) * cfg["cs"]
+    want.backward(cot)
+
+    # ---- device ----
+    gpu = {n: t.clone().to(DEV).requires_grad_(True) for n, t in ins.items()}
+    merges = []
+    orig_merge = ops.merge_tap
+
+    def merge_spy(*a, **kw):
+        merges.append(1)
+        return orig_merge(*a, **kw)
+    monkeypatch.setattr(ops, "merge_tap", merge_spy)
+    kw = dict(heads=h, groups=g, views=V, precision=prec, concat_views=cfg["concat"])
+    if route in ("kv_cell", "kv_source") and split < N or route == "tap":
+        kw["cell_split"] = split
+    ops.KERNEL_TIMER.start()
+    if fused:
+        got = ops.attention_core(gpu["query"], None, None, gpu["pos"], gpu["table"],
+                                 kv_source=(gpu["feat"], gpu["Wkv"], gpu["bkv"]), tap_source=route == "tap", **kw)
+    else:
+        got = ops.attention_core(gpu["query"], gpu["k"], gpu["v"], gpu["pos"], gpu["table"], **kw)
+    if cfg["concat"]:       # (B, M, V C) -> (B V, M, C), the oracle's layout
+        assert got.shape == (B, M, V * C)
+        got_v = got.reshape(B, M, V, C).permute(0, 2, 1, 3).reshape(B * V, M, C)
+    else:
+        got_v = got
+    got_v.backward(cot.float().to(DEV))
+    used = set(ops.KERNEL_TIMER.stop())
+
+    # ---- the route ran ----
+    tap = route == "tap"
+    region = split > 0
+    cell = split < N and not tap
+    if tap:
+        for k in ("bevr_attn_tap_fwd", "bevr_attn_tap_bwd_q", "bevr_attn_tap_bwd_k"):
+            assert k in used, f"{tag}: {k} did not run ({sorted(used)})"
+        assert len(merges) == (1 if region else 0), f"{tag}: merge_tap calls {len(merges)}"
+    else:
+        assert not merges and not any(k.startswith("bevr_attn_tap") for k in used), f"{tag}: {sorted(used)}"
+    for k in ("bevr_attn_cell_fwd", "bevr_attn_cell_bwd_q", "bevr_attn_cell_bwd_k"):
+        assert (k in used) == cell, f"{tag}: {k} {'missing' if cell else 'ran'} ({sorted(used)})"
+    if fused and (region or cell):
+        assert "bevr_kv_project" in used, f"{tag}: {sorted(used)}"
+    if region:
+        fwd = "bevr_attn_gather_fwd" if ops.gather_supported(prec, S) else "bevr_attn_fwd"
+        bwd_q = "bevr_attn_slab_bwd_q" if ops.slab_supported(prec, S, Wt) else "bevr_attn_bwd_q"
+        for k in (fwd, bwd_q, "bevr_attn_bwd_k"):
+            assert k in used, f"{tag}: {k} did not run ({sorted(used)})"
+    else:
+        assert not {"bevr_attn_gather_fwd", "bevr_attn_fwd", "bevr_attn_bwd_q", "bevr_attn_slab_bwd_q"} & used, tag
+
+    # ---- numbers ----
+    out_lim = TAP_OUT_LIM[prec] if tap else OUT_LIM[prec]
+    lim_g = TAP_GRAD_LIM[prec] if tap else GRAD_LIM[prec]
+    e = rel_err(got_v.detach().cpu().double(), want.detach())
+    assert e < out_lim, f"{tag}: out {e:.3e}"
+    cs = cfg["cs"]
+    # every key in the same few table cells: the bound of tests/test_gpu_random_sweep.py (2 u per term, x 2 of slack)
+    clustered = tap or cfg["kind"] == 2
+    for n in names:
+        a, b = gpu[n].grad, cpu[n].grad
+        assert a is not None and b is not None, f"{tag}: no gradient for {n}"
+        a = a.cpu().double()
+        if n == "pos":
+            clean = kink_distance(ins["pos"], S, Wt) >= 1e-4
+            if fused:
+                clean &= pixel_kink_distance(ins["pos"], ins["feat"].shape[1], ins["feat"].shape[2]) >= 1e-4
+            assert clean.float().mean().item() > 0.5, f"{tag}: kink neighbourhood too wide for this case"
+            dg, dw = a[clean], b[clean]
+            ep = (dg - dw).norm().item() / max(dw.norm().item(), 2e-2 * cs * max(dw.numel(), 1) ** 0.5)
+            assert ep < POS_LIM[prec], f"{tag}: grad pos 2-norm {ep:.3e}"
+            continue
+        scale = max(b.abs().max().item(), 2e-2 * cs)
+        if n in ("table", "query") and clustered:
+            # each element held to u per term magnitude (gradient_terms), x 2 of slack, or to the ordinary limit,
+            # whichever is wider (the table bound of tests/test_gpu_random_sweep.py)
+            terms = gradient_terms([cpu["query"], k64, v64, cpu["pos"], cpu["table"]], cot, h, g, V)[n == "query"]
+            bound = 2.0 * UNIT[prec] * terms + lim_g * scale
+            worst = ((a - b).abs() / bound).max().item()
+            assert worst < 1.0, f"{tag}: grad {n} {worst:.2f} x its term bound"
+            continue
+        e = (a - b).abs().max().item() / scale
+        # a bf16 feature map's gradient is stored in bf16 (autograd: the input's dtype): its own rounding, 2^-9 of an
+        # element, on top of the mode's limit -- x 2 of slack
+        lim = lim_g + (2.0 ** -8 if n == "feat" and cfg["feat_bf16"] else 0.0)
+        assert e < lim, f"{tag}: grad {n} {e:.3e}"
