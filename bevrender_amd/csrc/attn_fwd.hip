@@ -382,12 +382,13 @@ __global__ __launch_bounds__(TF, is16(PREC) ? 4 : 2) void attn_fwd_kernel(
       l += ls2[0] + ls2[1];
 #if BEVR_DROP
       {
-        // dropout acts on the normalised weights: the denominator above is of the unmasked ones; a kept weight is scaled
+        // dropout acts on the normalised weights: the denominator above is of the unmasked ones.  A dropped weight is
+        // zeroed here; the kept ones' 1 / (1 - p) is applied in the epilogue (in fp16 the weights reach 2^12 here, and
+        // scaled before the MFMA they would pass 65504 once 1 / (1 - p) > 16)
         const uint32_t hrow = bevr_drop_row(drop_seed, (uint32_t)ph, (uint32_t)(jc * d.Sp + i0 + lq));
-        const float ksc = 65536.0f / (65536.0f - (float)drop_thr);
 #pragma unroll
         for (int r = 0; r < 16; ++r)
-          s[r] = bevr_drop_keep(hrow, (uint32_t)(step * KT + ks * 32 + crow(r, hi)), drop_thr) ? s[r] * ksc : 0.f;
+          s[r] = bevr_drop_keep(hrow, (uint32_t)(step * KT + ks * 32 + crow(r, hi)), drop_thr) ? s[r] : 0.f;
       }
 #endif
       PROF_TD(t5, l + s[3]);
@@ -416,7 +417,11 @@ __global__ __launch_bounds__(TF, is16(PREC) ? 4 : 2) void attn_fwd_kernel(
     float* Oh = O + ((size_t)ph * Mp) * 32;
     float* Lh = LSE + (size_t)ph * Mp;
     float lt = l + __shfl_xor(l, 32);
+#if BEVR_DROP
+    float inv = (65536.0f / (65536.0f - (float)drop_thr)) / lt;   // the kept weights' 1 / (1 - p)
+#else
     float inv = 1.0f / lt;
+#endif
     size_t mq = (size_t)jcol * d.Sp + i0 + lq;
     float* orow = Oh + mq * 32;
 #pragma unroll

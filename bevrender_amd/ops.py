@@ -507,13 +507,16 @@ def _u32(x):
     return x & 0xFFFFFFFF
 
 
-def dropout_keep_mask(seed: int, thr16: int, n_ph: int, S: int, N: int, device="cpu") -> torch.Tensor:
+def dropout_keep_mask(seed: int, thr16: int, n_ph: int, S: int, N: int, device="cpu", rows=None) -> torch.Tensor:
     """The attention-dropout keep mask the kernels evaluate (csrc/bevr_common.h:bevr_drop_keep), on the host:
     (n_ph, S*S, N) bool, query index m = i*S + j (the reference's flattening), key index n in the kernels' key order.
-    keep iff the hash's top 16 bits >= thr16 = round(p * 65536).  Tests build the oracle's mask with it."""
+    keep iff the hash's top 16 bits >= thr16 = round(p * 65536).  Tests build the oracle's mask with it.
+    rows: query indices m (1-D) -- the (n_ph, len(rows), N) rows of that mask alone (large grids)."""
     Sp = 32 * ((S + 31) // 32)
     i = torch.arange(S, dtype=torch.int64, device=device)
     mq = (i[None, :] * Sp + i[:, None]).reshape(-1)                    # m = i*S + j -> packed j*Sp + i
+    if rows is not None:
+        mq = mq[torch.as_tensor(rows, dtype=torch.int64, device=device)]
     ph = torch.arange(n_ph, dtype=torch.int64, device=device)
     n = torch.arange(N, dtype=torch.int64, device=device)
     row = _u32(seed ^ _u32(ph * 0x9E3779B1)[:, None] ^ _u32(mq * 0x85EBCA77)[None, :])       # (n_ph, M)
@@ -553,6 +556,25 @@ def slab_supported(precision, S, Wt=None) -> bool:
     if mode == "0" or precision not in (_lib.PREC_BF16, _lib.PREC_F16) or S > 211:
         return False
     return mode == "2" or Wt is None or Wt - 1 >= 4 * (S - 1)
+
+
+def backward_scales(bound: torch.Tensor, pmax_log2: torch.Tensor, f16: bool, drop_thr: int = 0) -> torch.Tensor:
+    """grad_scale[8] of the backward kernels (include/bevrender_hip.h) from bound >= |dP - delta| of every pair and
+    pmax_log2 >= log2 of the largest softmax weight (0-d tensors; powers of two out, no host sync).
+    Attention dropout (drop_thr = round(p * 65536) > 0): the kernels form dS = P (D dP - delta) and the dV operand D P',
+    D = 65536 / (65536 - drop_thr) >= 1.  P |D dP - delta| <= D P bound, so log2 D added to pmax_log2 keeps all three
+    bounds of the contract (s D Pmax bound <= 2^30; fp16: D Pmax 2^kp <= 2^14, D Pmax bound 2^kp c2 <= 2^14)."""
+    dev = bound.device
+    if drop_thr:
+        pmax_log2 = pmax_log2 + math.log2(65536.0 / (65536.0 - drop_thr))
+    zero, one = torch.zeros((), device=dev), torch.ones((), device=dev)
+    if f16:
+        kp = torch.floor(14.0 - pmax_log2)
+        e16 = torch.floor(14.0 - torch.log2(bound) - pmax_log2).clamp(-100.0, 100.0)
+        return torch.stack((torch.exp2(e16 + 16.0), torch.exp2(-e16 - 16.0), kp, torch.exp2(e16 - kp),
+                            torch.exp2(-e16), torch.exp2(-kp), zero, zero)).float().contiguous()
+    e = torch.floor(30.0 - torch.log2(bound) - pmax_log2).clamp(-100.0, 100.0)
+    return torch.stack((torch.exp2(e), torch.exp2(-e), zero, one, one, one, zero, zero)).float().contiguous()
 
 
 class _AttnCore(torch.autograd.Function):
@@ -645,8 +667,9 @@ class _AttnCore(torch.autograd.Function):
                                             _ptr(Qe), _ptr(Ke), _ptr(Vt), _ptr(key_ws), _ptr(pair), o_in, l_in, _ptr(O),
                                             _ptr(LSE), _stream(), tag=_call_tag(g)), "bevr_attn_cell_fwd")
             elif ctx.drop:
-                _lib.check(L.bevr_attn_fwd_dropout(C.byref(d), _ptr(Qe), _ptr(Ke), _ptr(Vt), _ptr(key_ws), _ptr(pair), _ptr(O),
-                                                   _ptr(LSE), ctx.drop[0], ctx.drop[1], _stream()), "bevr_attn_fwd_dropout")
+                _lib.check(KERNEL_TIMER.run("bevr_attn_fwd_dropout", _attn_flops(g, 2), L.bevr_attn_fwd_dropout, C.byref(d),
+                                            _ptr(Qe), _ptr(Ke), _ptr(Vt), _ptr(key_ws), _ptr(pair), _ptr(O), _ptr(LSE),
+                                            ctx.drop[0], ctx.drop[1], _stream(), tag=_call_tag(g)), "bevr_attn_fwd_dropout")
             elif gather_supported(g.precision, g.S):
                 if pair_pk is None:
                     pair_pk = pair.to(torch.bfloat16)       # (h, Wp, Hp, 2) 16-bit: one dword per (column, row) entry
@@ -751,6 +774,7 @@ class _AttnCore(torch.autograd.Function):
         #             dO and delta as it loads them -- exact -- and ln2 / s when it stores);
         #   fp16 only: [2] kp with Pmax 2^kp <= 2^14 (softmax weights as fp16 operands), [3] c2 with
         #             Pmax bound 2^kp c2 <= 2^14 (logit gradients as fp16 operands), [4], [5] the inverses; s = 2^16 2^kp c2.
+        # With dropout every Pmax above is D Pmax (backward_scales).
         if ctx.fused:      # from the packing kernel (squared, of the unrounded rows: + 1 % for the rounding to E)
             vmax = src[3][0].sqrt() * 1.01
         elif x3:
@@ -762,15 +786,7 @@ class _AttnCore(torch.autograd.Function):
         else:
             bound = (dOr.norm(dim=-1).max() * vmax + delta.abs().max()).clamp_min(1e-30)
         pmax_log2 = (LSE[1].max() + 0.05).clamp(-60.0, 0.0)
-        zero, one = torch.zeros((), device=dev), torch.ones((), device=dev)
-        if f16:
-            kp = torch.floor(14.0 - pmax_log2)
-            e16 = torch.floor(14.0 - torch.log2(bound) - pmax_log2).clamp(-100.0, 100.0)
-            gscale = torch.stack((torch.exp2(e16 + 16.0), torch.exp2(-e16 - 16.0), kp, torch.exp2(e16 - kp),
-                                  torch.exp2(-e16), torch.exp2(-kp), zero, zero)).float().contiguous()
-        else:
-            e = torch.floor(30.0 - torch.log2(bound) - pmax_log2).clamp(-100.0, 100.0)
-            gscale = torch.stack((torch.exp2(e), torch.exp2(-e), zero, one, one, one, zero, zero)).float().contiguous()
+        gscale = backward_scales(bound, pmax_log2, f16, ctx.drop[0] if ctx.drop else 0)
         das, dbs = [], []
         for i, sg in enumerate(ctx.segs):
             g = sg.geom
@@ -782,9 +798,10 @@ class _AttnCore(torch.autograd.Function):
                                             _ptr(LSE), _ptr(delta), _ptr(gscale), _ptr(dQ), _ptr(dT), _stream(),
                                             tag=_call_tag(g)), "bevr_attn_cell_bwd_q")
             elif ctx.drop:
-                _lib.check(L.bevr_attn_bwd_q_dropout(C.byref(d), _ptr(Qe), _ptr(Ke), _ptr(Kt), _ptr(Ve), _ptr(key_ws), _ptr(pair),
-                                                     _ptr(dOe), _ptr(LSE), _ptr(delta), _ptr(gscale), _ptr(dQ), _ptr(dT),
-                                                     ctx.drop[0], ctx.drop[1], _stream()), "bevr_attn_bwd_q_dropout")
+                _lib.check(KERNEL_TIMER.run("bevr_attn_bwd_q_dropout", _attn_flops(g, 3), L.bevr_attn_bwd_q_dropout,
+                                            C.byref(d), _ptr(Qe), _ptr(Ke), _ptr(Kt), _ptr(Ve), _ptr(key_ws), _ptr(pair),
+                                            _ptr(dOe), _ptr(LSE), _ptr(delta), _ptr(gscale), _ptr(dQ), _ptr(dT),
+                                            ctx.drop[0], ctx.drop[1], _stream(), tag=_call_tag(g)), "bevr_attn_bwd_q_dropout")
             elif slab_supported(g.precision, g.S, g.Wt):
                 # keys sorted by table column b per problem-group; K and V rows gathered into that order (softmax and its
                 # gradients do not depend on the order of the keys; dK / dV come from the key-side kernel in the caller's)
@@ -817,10 +834,11 @@ class _AttnCore(torch.autograd.Function):
                                             _ptr(dOt), _ptr(LSE), _ptr(delta), _ptr(gscale), _ptr(dK), _ptr(dV),
                                             _ptr(da), _ptr(db), _stream(), tag=_call_tag(g)), "bevr_attn_cell_bwd_k")
             elif ctx.drop:
-                _lib.check(L.bevr_attn_bwd_k_dropout(C.byref(d), _ptr(Qe), _ptr(Qt), _ptr(Ke), _ptr(Ve), _ptr(ka), _ptr(kb),
-                                                     _ptr(pair), _ptr(dOe), _ptr(dOt), _ptr(LSE), _ptr(delta), _ptr(gscale),
-                                                     _ptr(dK), _ptr(dV), _ptr(da), _ptr(db), ctx.drop[0], ctx.drop[1],
-                                                     _stream()), "bevr_attn_bwd_k_dropout")
+                _lib.check(KERNEL_TIMER.run("bevr_attn_bwd_k_dropout", _attn_flops(g, 4), L.bevr_attn_bwd_k_dropout,
+                                            C.byref(d), _ptr(Qe), _ptr(Qt), _ptr(Ke), _ptr(Ve), _ptr(ka), _ptr(kb), _ptr(pair),
+                                            _ptr(dOe), _ptr(dOt), _ptr(LSE), _ptr(delta), _ptr(gscale), _ptr(dK), _ptr(dV),
+                                            _ptr(da), _ptr(db), ctx.drop[0], ctx.drop[1], _stream(),
+                                            tag=_call_tag(g)), "bevr_attn_bwd_k_dropout")
             else:
                 _lib.check(KERNEL_TIMER.run("bevr_attn_bwd_k", _attn_flops(g, 4), L.bevr_attn_bwd_k, C.byref(d), _ptr(Qe),
                                             _ptr(Qt), _ptr(Ke), _ptr(Ve), _ptr(ka), _ptr(kb), _ptr(pair), _ptr(dOe),

@@ -192,7 +192,11 @@ int bevr_attn_bwd_k(const bevr_attn_desc* d, const void* Q, const void* Qt, cons
  * with drop_thr = round(p * 65536) < 65536, and a kept weight is scaled by 65536 / (65536 - drop_thr).  The forward
  * masks the weights AFTER the normalisation (LSE is of the unmasked logits, as the reference's softmax-then-dropout);
  * the backward entry points evaluate the same function (same seed): dS = P (D dP - delta), dV from D P.  delta is
- * still rowsum(dO * O).  bevrender_amd/ops.py:dropout_keep_mask is the host twin.  Region kernels only: a caller with
+ * still rowsum(dO * O).  grad_scale as for bevr_attn_bwd_q / _bwd_k with every Pmax of its contract read as D Pmax,
+ * D = 65536 / (65536 - drop_thr): s D Pmax bound <= 2^30; fp16: D Pmax 2^kp <= 2^14 and D Pmax bound 2^kp c2 <= 2^14
+ * (|D dP - delta| <= D bound: the fixed-point contributions and the fp16 operands D P', P' (D dP - delta) c2 stay in
+ * range).  The forward applies D after the normalisation, to the output (its fp16 operands are the unscaled weights).
+ * bevrender_amd/ops.py:dropout_keep_mask is the host twin.  Region kernels only: a caller with
  * dropout keeps every key on these entry points (the cell / tap entry points have no mask). */
 int bevr_attn_fwd_dropout(const bevr_attn_desc* d, const void* Q, const void* K, const void* Vt,
                           const void* key_ws, const float* table_pair, float* O, float* LSE,

@@ -178,11 +178,13 @@ def tsa_key_positions(p: Dict[str, Tensor], query: Tensor, n_groups: int, kernel
 
 def tsa_forward(p: Dict[str, Tensor], query: Tensor, prev_bev: Optional[Tensor], *, n_heads: int,
                 n_groups: int = 1, kernel_size: int = 3, stride: int = 1,
-                scale_offset_range: bool = True, rows: Optional[Tensor] = None) -> Tensor:
+                scale_offset_range: bool = True, rows: Optional[Tensor] = None, keep: Optional[Tensor] = None) -> Tensor:
     """TSADeformableAttention.forward(x=prev_bev, query).  `p` uses the reference's state_dict names.
     rows (long tensor of query indices m = i*W + j, optional): evaluate the module's output at those BEV positions only
     (attention rows and the 1x1 proj_out are independent per position) and return (B, C, len(rows)): how the module is
-    checked at sizes whose (M x N) tensors do not fit in host memory."""
+    checked at sizes whose (M x N) tensors do not fit in host memory.
+    keep (B*h, M or len(rows), N), optional: attn_drop's multiplier (0 or 1 / (1 - p)), keys in this function's order
+    (row-major over the key grid); attention_core's `keep`."""
     x = query.clone() if prev_bev is None else prev_bev                      # :142-143
     B, C, H, W = x.shape
     h, g = n_heads, n_groups
@@ -195,7 +197,7 @@ def tsa_forward(p: Dict[str, Tensor], query: Tensor, prev_bev: Optional[Tensor],
     q = query.reshape(B * h, c, H * W)                                        # :220 (raw query, proj_q unused)
     k = F.conv2d(xs, p["proj_k.weight"], p["proj_k.bias"]).reshape(B * h, c, N)
     v = F.conv2d(xs, p["proj_v.weight"], p["proj_v.bias"]).reshape(B * h, c, N)
-    out = attention_core(q, k, v, pos.reshape(B * g, N, 2), p["rpe_table"], H, W, g, c ** -0.5, rows=rows)
+    out = attention_core(q, k, v, pos.reshape(B * g, N, 2), p["rpe_table"], H, W, g, c ** -0.5, rows=rows, keep=keep)
     if rows is not None:
         return F.conv1d(out.reshape(B, C, len(rows)), p["proj_out.weight"].flatten(2), p["proj_out.bias"])
     out = out.reshape(B, C, H, W)
@@ -230,9 +232,11 @@ def sca_key_positions(p: Dict[str, Tensor], query: Tensor, ref_view: Tensor, vie
 
 def sca_forward(p: Dict[str, Tensor], x: Tensor, query: Tensor, reference_points: Tensor, *, n_heads: int,
                 n_groups: int = 1, depth_dim: int = 5, scale_offset_range: bool = True,
-                rows: Optional[Tensor] = None) -> Tensor:
+                rows: Optional[Tensor] = None, keep: Optional[Tensor] = None) -> Tensor:
     """SCADeformableAttention.forward.  x (B, V, C, Hi, Wi); reference_points (B, V, S/2, S*D, 2) in (x, y).
-    rows: as tsa_forward -- the output at the selected BEV positions only, (B, C, len(rows))."""
+    rows: as tsa_forward -- the output at the selected BEV positions only, (B, C, len(rows)).
+    keep (B*V*h, M or len(rows), N), optional: attn_drop's multiplier per (sample, view, head) -- index (b V + v) h +
+    head -- keys row-major over each view's key grid (attention_core's `keep`)."""
     B, V, C, Hi, Wi = x.shape
     S = query.shape[-1]
     h, g = n_heads, n_groups
@@ -249,7 +253,8 @@ def sca_forward(p: Dict[str, Tensor], x: Tensor, query: Tensor, reference_points
         q = query.reshape(B * h, c, S * S)                                    # :304-306
         k = F.conv2d(xs, p["proj_k.weight"], p["proj_k.bias"]).reshape(B * h, c, N)
         v = F.conv2d(xs, p["proj_v.weight"], p["proj_v.bias"]).reshape(B * h, c, N)
-        o = attention_core(q, k, v, pos.reshape(B * g, N, 2), p["rpe_table"], S, S, g, c ** -0.5, rows=rows)
+        view_keep = None if keep is None else keep.reshape(B, V, h, -1, N)[:, v_idx].reshape(B * h, -1, N)
+        o = attention_core(q, k, v, pos.reshape(B * g, N, 2), p["rpe_table"], S, S, g, c ** -0.5, rows=rows, keep=view_keep)
         outs.append(o.reshape(B, C, S, S) if rows is None else o.reshape(B, C, len(rows)))
     out = torch.cat(outs, dim=1)                                              # "b v c h w -> b (v c) h w"
     if rows is not None:

@@ -90,11 +90,12 @@ def permute_keys(t, perm):
     return torch.gather(t, 1, idx)
 
 
-def oracle_rows(p, h, rows, cot, want_grads=True, dtype=torch.float64):
+def oracle_rows(p, h, rows, cot, want_grads=True, dtype=torch.float64, keep=None):
     """oracle.attention_core on the query subset `rows`, one view at a time (each view is an independent softmax
     problem sharing the query).  Returns out (V, R, C) and the gradients for the cotangent `cot` (V, R, C).
     float64 by default: d(pos) is discontinuous where a table coordinate crosses an integer, and a float32 oracle
-    lands on either side of such a kink by its own rounding (see check_dpos)."""
+    lands on either side of such a kink by its own rounding (see check_dpos).
+    keep (V h, R, N), optional: attention dropout's multiplier on those rows, keys in the order of p["k"]."""
     query, k, v, pos, table = (p[n].clone().to(dtype).requires_grad_(want_grads)
                                for n in ("query", "k", "v", "pos", "table"))
     if cot is not None:
@@ -107,7 +108,8 @@ def oracle_rows(p, h, rows, cot, want_grads=True, dtype=torch.float64):
         q = query[0].reshape(h, c, S * S)
         kk = k[vi].reshape(N, h, c).permute(1, 2, 0)
         vv = v[vi].reshape(N, h, c).permute(1, 2, 0)
-        o = O.attention_core(q, kk, vv, pos[vi:vi + 1], table, S, S, 1, c ** -0.5, rows=rows)     # (h, c, R)
+        o = O.attention_core(q, kk, vv, pos[vi:vi + 1], table, S, S, 1, c ** -0.5, rows=rows,
+                             keep=None if keep is None else keep[vi * h:(vi + 1) * h])             # (h, c, R)
         o = o.reshape(C, len(rows)).t()
         if want_grads:
             (o * cot[vi]).sum().backward()

@@ -169,13 +169,15 @@ def chain_kv(feat, Wkv, bkv, pos, g):
     return kv[..., :C], kv[..., C:]
 
 
-def gradient_terms(ins, cot, h, g, V):
+def gradient_terms(ins, cot, h, g, V, keep=None, keys=False):
     """(table, query): per element, the sum over (query, key) of the magnitudes of the terms whose signed sum is the
     table gradient (sum w dS, w >= 0 the bilinear taps) and d(query) (c^-0.5 sum dS K), in float64.  A term's magnitude
     is |dS| plus P (A + sum_m P_m A_m), A[q, n] = sum_c |dO[q, c]| |V[n, c]|: the bound of what the 16-bit roundings of
     dO and V do to dP - delta.  Keys sampled from one tight cluster of feature pixels have nearly equal K and V rows:
     dP - delta and sum_n dS K are then differences of nearly equal numbers, the roundings apply to the TERMS
-    (tests/test_gpu_random_sweep.py table_gradient_terms: the same bound with the |dS| part alone)."""
+    (tests/test_gpu_random_sweep.py table_gradient_terms: the same bound with the |dS| part alone).
+    keep (B' h, M, N): attention dropout's multiplier D mask, folded into the dP and A terms (dS = P (D dP - delta)).
+    keys=True: d(K) (c^-0.5 sum_q dS Q) as a third output, (B', N, C)."""
     query, k, v, pos, table = [t.detach() for t in ins]
     B, C, S, _ = query.shape
     c = C // h
@@ -184,6 +186,7 @@ def gradient_terms(ins, cot, h, g, V):
     tab = table.clone().requires_grad_(True)
     q_grid = O.normalized_grid(S, S, torch.float64).reshape(1, M, 2)
     dq = torch.zeros(B, h, c, M, dtype=torch.float64)
+    dk = torch.zeros(Bp, h, c, N, dtype=torch.float64) if keys else None
     total = 0.0
     for bp in range(Bp):
         q = query[bp // V].reshape(h, c, M)
@@ -195,12 +198,19 @@ def gradient_terms(ins, cot, h, g, V):
         P = torch.softmax(torch.einsum("bcm,bcn->bmn", q, kk) * c ** -0.5 + bias.detach(), dim=2)
         dO = cot[bp].t().reshape(h, c, M)
         dP = torch.einsum("bcm,bcn->bmn", dO, vv)
-        dS = P * (dP - (P * dP).sum(2, keepdim=True))
         A = torch.einsum("bcm,bcn->bmn", dO.abs(), vv.abs())
+        if keep is not None:
+            kp = keep[bp * h:(bp + 1) * h].double()
+            dP, A = dP * kp, A * kp
+        dS = P * (dP - (P * dP).sum(2, keepdim=True))
         mag = dS.abs() + P * (A + (P * A).sum(2, keepdim=True))
         total = total + (bias * mag).sum()
         dq[bp // V] += c ** -0.5 * torch.einsum("bmn,bcn->bcm", mag, kk.abs())
+        if keys:
+            dk[bp] = c ** -0.5 * torch.einsum("bmn,bcm->bcn", mag, q.abs())
     total.backward()
+    if keys:
+        return tab.grad, dq.reshape(B, C, S, S), dk.permute(0, 3, 1, 2).reshape(Bp, N, C)
     return tab.grad, dq.reshape(B, C, S, S)
 
 
