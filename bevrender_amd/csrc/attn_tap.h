@@ -101,12 +101,45 @@ __device__ __forceinline__ int half_min_i(int v) {
   return v;
 }
 
+// Attention dropout (bevr_common.h: bevr_drop_keep).  The dropout variants are separate translation units
+// (attn_tap_*_drop.hip: #define BEVR_DROP 1 and #include the kernel's source), as the region kernels': the kernels
+// without dropout stay what they were.  key0: index of the segment's first key in the caller's key order for the whole
+// call -- the mask is hashed with n = key0 + (index inside the segment), so that the segments of one softmax share ONE
+// mask (ops.py:dropout_keep_mask over all N keys).  Dropout acts on P after the softmax: R accumulates the kept weights
+// (slot TAP_ONE: the kept mass), the row sum of ALL weights goes out on its own (lsum), and the logit gradient is
+// dS = P (keep ? D dP : 0 - delta), the droppable part D dP = w . H + H[TAP_ONE] (the caller folds D into H), -delta in
+// slots TAP_CHI / TAP_CLO of H as without dropout.
+#if BEVR_DROP
+#define TAP_DROP_PARAMS , unsigned key0, unsigned drop_thr, unsigned drop_seed
+#define TAP_DROP_ARGS , key0, drop_thr, drop_seed
+// The key part of the hash, n * 0xC2B2AE3D, for the 8 keys of a 32-key tile whose logits a lane of the query-stationary
+// kernels holds (element k: key n0 + 4 kg + (k & 3) + 16 (k >> 2)): one register per tile (the first key's product), the
+// other seven differ from it by constants (the product is linear modulo 2^32)
+__device__ __forceinline__ uint32_t tap_drop_key0(uint32_t n0, int kg) { return (n0 + (uint32_t)(4 * kg)) * 0xC2B2AE3Du; }
+__device__ __forceinline__ bool tap_drop_keep(uint32_t hrow, uint32_t kh, uint32_t thr16) {
+#if defined(BEVR_VARIANT) && BEVR_VARIANT == 31
+  // A/B timing only (make VARIANT=31): the mask without the mixing rounds (a WRONG mask) -- what is left of the dropout
+  // kernels' extra time is not the hash's
+  return ((hrow ^ kh) >> 16) >= thr16;
+#else
+  return (bevr_drop_mix(hrow ^ kh) >> 16) >= thr16;
+#endif
+}
+__device__ __forceinline__ bool tap_drop_keep8(uint32_t hrow, uint32_t kh0, int k, uint32_t thr16) {
+  return tap_drop_keep(hrow, kh0 + (uint32_t)(16 * (k >> 2) + (k & 3)) * 0xC2B2AE3Du, thr16);
+}
+#else
+#define TAP_DROP_PARAMS
+#define TAP_DROP_ARGS
+#endif
+
 // ---------------------------------------------------------------------------------------------------------------
 // The key stream of the query-stationary tap kernels (forward, query-side backward): LDS layout and the producer wave.
 struct LdsT {
   static constexpr int OFF_TAPS = 0;            // [64 keys][16 slots] 16-bit
   static constexpr int OFF_CELLS = 2048;        // [64 keys][16 cells] 16-bit
   static constexpr int OFF_CT = 4096;           // u32x4: flags (bit 0 / 1: tile 0 / 1 live, bit 2: done), alloc0, alloc1, 0
+                                                //        (dropout build: the 4th dword = record index of tile 0's first key)
   static constexpr int OFF_ORG = 4096 + 16;     // i32x4: chunk origin of tile 0 (x0, a0), of tile 1 (x0, a0)
   static constexpr int BUF = 4096 + 32;
   static constexpr int RING = 4;
@@ -224,7 +257,13 @@ __device__ __forceinline__ void tap_producer(const bevr_attn_desc& d, char* smem
         al1 = alloc;
       }
       if (lane == 0) {
+#if BEVR_DROP
+        // dropout: the record index of the emission's first slot (lane l is key step * KT + l of the segment in EVERY
+        // masked pass of the step: one keep decision per key)
+        *reinterpret_cast<u32x4*>(bb + L::OFF_CT) = u32x4{(unsigned)(ok0 | (ok1 << 1)), (unsigned)al0, (unsigned)al1, (unsigned)(step * KT)};
+#else
         *reinterpret_cast<u32x4*>(bb + L::OFF_CT) = u32x4{(unsigned)(ok0 | (ok1 << 1)), (unsigned)al0, (unsigned)al1, 0u};
+#endif
         *reinterpret_cast<u32x4*>(bb + L::OFF_ORG) = u32x4{(unsigned)ox0, (unsigned)oa0, (unsigned)tag_x, (unsigned)tag_a};
       }
       rem = rem && !sel;

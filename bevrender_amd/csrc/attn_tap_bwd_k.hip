@@ -51,7 +51,7 @@ template <int PREC, bool SLOW>
 __global__ __launch_bounds__(64 * (NKW + 1), 4) void attn_tap_bwd_k_kernel(
     bevr_attn_desc d, const char* __restrict__ G, const char* __restrict__ H, const char* __restrict__ tap_ws,
     const float* __restrict__ table_t, float* __restrict__ dkey_a, float* __restrict__ dkey_b,
-    float* __restrict__ dkey_y, float* __restrict__ dkey_x, int n_wg_ph) {
+    float* __restrict__ dkey_y, float* __restrict__ dkey_x, int n_wg_ph TAP_DROP_PARAMS) {
   typedef LdsK L;
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -237,6 +237,16 @@ __global__ __launch_bounds__(64 * (NKW + 1), 4) void attn_tap_bwd_k_kernel(
   const int a_row = L::OFF_G + li * 32 + (g & 1) * 16;                          // row read of a staged image (lanes 0..31)
   const int t_off = (4 * g + (li >> 2)) * 32 + (lane & 3) * 8;                  // transposed read, second block + 512
   const int cell_c = li >> 2, cell_r = li & 3;                                   // this lane's cell in the transposed table operands
+#if BEVR_DROP
+  // dropout: dS = P (keep ? D dP : 0 - delta) and the value path from keep P (D rides in H).  The key is on the lane: its
+  // part of the hash is computed once; the query part changes with the row
+  // (with the seed and the problem-head folded in: the hash's three parts are combined by xor)
+  uint32_t khk[2];
+#pragma unroll
+  for (int kb = 0; kb < 2; ++kb)
+    khk[kb] = ((key0 + (uint32_t)(tl * 32 + 16 * kb + li)) * 0xC2B2AE3Du) ^ drop_seed ^ ((uint32_t)ph * 0x9E3779B1u);
+  uint32_t hcol = 0u;      // the query part mq * 0x85EBCA77 for row 4 g of the column -- set per column
+#endif
 
   int e = 0;
   float jrx = 0.f;
@@ -280,6 +290,19 @@ __global__ __launch_bounds__(64 * (NKW + 1), 4) void attn_tap_bwd_k_kernel(
       thi = __builtin_bit_cast(bf16x8, a);
       tlo = __builtin_bit_cast(bf16x8, b);
     }
+#if BEVR_DROP
+    // the 8 queries of this lane's accumulator rows: i0 + 4 g + r (row block 0) and + 16 (row block 1): the row hash and
+    // -delta out of slots TAP_CHI / TAP_CLO of the staged H row
+    // (the query part of the other seven rows differs from hq0's by constants: the product is linear modulo 2^32)
+    const uint32_t hq0 = hcol + (uint32_t)i0 * 0x85EBCA77u;
+    auto hq = [&](int r) { return hq0 + (uint32_t)(16 * (r >> 2) + (r & 3)) * 0x85EBCA77u; };
+    float ndel[8];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+      const uint32_t c2 = *reinterpret_cast<const uint32_t*>(base + L::OFF_H + (16 * (r >> 2) + 4 * g + (r & 3)) * 32 + TAP_CHI * 2);
+      ndel[r] = Half<PREC>::lo(c2) + Half<PREC>::hi(c2);
+    }
+#endif
 #pragma unroll
     for (int kb = 0; kb < 2; ++kb) {
       const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
@@ -305,7 +328,15 @@ __global__ __launch_bounds__(64 * (NKW + 1), 4) void attn_tap_bwd_k_kernel(
           const float u0 = t00 + fy * (t01 - t00), u1 = t10 + fy * (t11 - t10);
           const float sv = (r < 4 ? s0[r & 3] : s1[r & 3]) + (dead ? 0.f : u0 + fx * (u1 - u0));
           p[r] = fast_exp2(sv);
+#if BEVR_DROP
+          {
+            const bool keep = tap_drop_keep(hq(r), khk[kb], drop_thr);
+            ds[r] = p[r] * (keep ? (r < 4 ? q0[r & 3] : q1[r & 3]) : ndel[r]);
+            p[r] = keep ? p[r] : 0.f;
+          }
+#else
           ds[r] = p[r] * (r < 4 ? q0[r & 3] : q1[r & 3]);
+#endif
           pa += ds[r] * ((1.0f - fx) * (t01 - t00) + fx * (t11 - t10));
           pb += ds[r] * (u1 - u0);
         }
@@ -314,10 +345,20 @@ __global__ __launch_bounds__(64 * (NKW + 1), 4) void attn_tap_bwd_k_kernel(
       } else {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
+#if BEVR_DROP
+          p[r] = fast_exp2(s0[r]);
+          p[4 + r] = fast_exp2(s1[r]);
+          const bool keep0 = tap_drop_keep(hq(r), khk[kb], drop_thr), keep1 = tap_drop_keep(hq(4 + r), khk[kb], drop_thr);
+          ds[r] = p[r] * (keep0 ? q0[r] : ndel[r]);
+          ds[4 + r] = p[4 + r] * (keep1 ? q1[r] : ndel[4 + r]);
+          p[r] = keep0 ? p[r] : 0.f;
+          p[4 + r] = keep1 ? p[4 + r] : 0.f;
+#else
           p[r] = fast_exp2(s0[r]);
           ds[r] = p[r] * q0[r];
           p[4 + r] = fast_exp2(s1[r]);
           ds[4 + r] = p[4 + r] * q1[r];
+#endif
         }
       }
       u32x4 dsw, pw;
@@ -338,6 +379,9 @@ __global__ __launch_bounds__(64 * (NKW + 1), 4) void attn_tap_bwd_k_kernel(
 
   for (int j = 0; j < d.S; ++j) {
     jrx = (float)j * rx;
+#if BEVR_DROP
+    hcol = (uint32_t)(j * d.Sp + 4 * g) * 0x85EBCA77u;
+#endif
     const int x0 = (int)floorf(jrx + sb.bmin), a0 = sb.amin;
     const int dx = x0 - (int)floorf(jrx + bminw);
     const bool fit = tile_fits(sb, jrx, a0w, bminw);    // uniform over the wave
@@ -435,7 +479,7 @@ __global__ __launch_bounds__(64 * (NKW + 1), 4) void attn_tap_bwd_k_kernel(
 
 template <int PREC>
 int launch(const bevr_attn_desc& d, const void* G, const void* H, const void* tap_ws, const float* table_t, float* dkey_a,
-           float* dkey_b, float* dkey_y, float* dkey_x, hipStream_t st) {
+           float* dkey_b, float* dkey_y, float* dkey_x, hipStream_t st TAP_DROP_PARAMS) {
   typedef LdsK L;
   const int n_ph = d.n_prob * d.heads;
   const int n_tiles = d.Np / 32;
@@ -445,26 +489,34 @@ int launch(const bevr_attn_desc& d, const void* G, const void* H, const void* ta
   const long long grid = (long long)((n_ph + 7) / 8) * 8 * n_wg_ph;
   if (grid > 0x7fffffffLL) return BEVR_E_SHAPE;
   hipLaunchKernelGGL((attn_tap_bwd_k_kernel<PREC, false>), dim3((unsigned)grid), dim3(64 * (NKW + 1)), lds, st, d, (const char*)G,
-                     (const char*)H, (const char*)tap_ws, table_t, dkey_a, dkey_b, dkey_y, dkey_x, n_wg_ph);
+                     (const char*)H, (const char*)tap_ws, table_t, dkey_a, dkey_b, dkey_y, dkey_x, n_wg_ph TAP_DROP_ARGS);
   const int rc = (int)hipGetLastError();
   if (rc) return rc;
   hipLaunchKernelGGL((attn_tap_bwd_k_kernel<PREC, true>), dim3((unsigned)grid), dim3(64 * (NKW + 1)), lds, st, d, (const char*)G,
-                     (const char*)H, (const char*)tap_ws, table_t, dkey_a, dkey_b, dkey_y, dkey_x, n_wg_ph);
+                     (const char*)H, (const char*)tap_ws, table_t, dkey_a, dkey_b, dkey_y, dkey_x, n_wg_ph TAP_DROP_ARGS);
   return (int)hipGetLastError();
 }
 
 }  // namespace
 
+#if BEVR_DROP
+extern "C" int bevr_attn_tap_bwd_k_dropout(const bevr_attn_desc* d, const void* G, const void* H, const void* tap_ws,
+                                           const float* table_t, float* dkey_a, float* dkey_b, float* dkey_y,
+                                           float* dkey_x, unsigned key0, unsigned drop_thr, unsigned drop_seed,
+                                           void* stream) {
+  if (drop_thr >= 65536u) return BEVR_E_SHAPE;
+#else
 extern "C" int bevr_attn_tap_bwd_k(const bevr_attn_desc* d, const void* G, const void* H, const void* tap_ws,
                                    const float* table_t, float* dkey_a, float* dkey_b, float* dkey_y, float* dkey_x,
                                    void* stream) {
+#endif
   int rc = bevr_check_desc(d);
   if (rc) return rc;
   if (!G || !H || !tap_ws || !table_t || !dkey_a || !dkey_b || !dkey_y || !dkey_x) return BEVR_E_NULL;
   if (d->groups != 1) return BEVR_E_SHAPE;
   if (!bevr_aligned16(G) || !bevr_aligned16(H) || !bevr_aligned16(tap_ws)) return BEVR_E_ALIGN;
   hipStream_t st = (hipStream_t)stream;
-  if (d->precision == BEVR_PREC_BF16) return launch<BEVR_PREC_BF16>(*d, G, H, tap_ws, table_t, dkey_a, dkey_b, dkey_y, dkey_x, st);
-  if (d->precision == BEVR_PREC_F16) return launch<BEVR_PREC_F16>(*d, G, H, tap_ws, table_t, dkey_a, dkey_b, dkey_y, dkey_x, st);
+  if (d->precision == BEVR_PREC_BF16) return launch<BEVR_PREC_BF16>(*d, G, H, tap_ws, table_t, dkey_a, dkey_b, dkey_y, dkey_x, st TAP_DROP_ARGS);
+  if (d->precision == BEVR_PREC_F16) return launch<BEVR_PREC_F16>(*d, G, H, tap_ws, table_t, dkey_a, dkey_b, dkey_y, dkey_x, st TAP_DROP_ARGS);
   return BEVR_E_PRECISION;
 }

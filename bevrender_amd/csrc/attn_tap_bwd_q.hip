@@ -18,7 +18,7 @@ namespace {
 template <int PREC, int NB>
 __global__ __launch_bounds__(512, 4) void attn_tap_bwd_q_kernel(
     bevr_attn_desc d, const char* __restrict__ G, const char* __restrict__ H, const char* __restrict__ tap_ws, const char* __restrict__ table_pair,
-    float* __restrict__ dG, float* __restrict__ dtable) {
+    float* __restrict__ dG, float* __restrict__ dtable TAP_DROP_PARAMS) {
   typedef LdsT L;
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -67,6 +67,18 @@ __global__ __launch_bounds__(512, 4) void attn_tap_bwd_q_kernel(
     ytap[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
     ycell[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
+#if BEVR_DROP
+  // dropout: dS = P (keep ? D dP : 0 - delta).  The MFMA gives x = D dP - delta (D dP = w . H + H[TAP_ONE], -delta in slots
+  // TAP_CHI / TAP_CLO); a dropped pair keeps -delta alone, which every lane reads for its row once, with the row hash
+  uint32_t hrow[NB];
+  float ndel[NB];
+#pragma unroll
+  for (int nb = 0; nb < NB; ++nb) {
+    hrow[nb] = bevr_drop_row(drop_seed, (uint32_t)ph, (uint32_t)(j * d.Sp + min(blk0 + nb, nblk - 1) * QB + li));
+    const uint32_t c2 = *reinterpret_cast<const uint32_t*>(H + (mqv[nb] * TAP_SLOTS + TAP_CHI) * 2);
+    ndel[nb] = Half<PREC>::lo(c2) + Half<PREC>::hi(c2);
+  }
+#endif
   const int a_off = (kg < 2 ? L::OFF_TAPS : L::OFF_CELLS) + li * 32 + (kg & 1) * 16;     // + tile * 1024 + sub * 512
   const int t_off = (4 * kg + (li >> 2)) * 32 + (lane & 3) * 8;                           // transposed reads: + image, + tile * 1024
   const int i_off = li * 32 + (kg & 1) * 16;
@@ -105,7 +117,11 @@ __global__ __launch_bounds__(512, 4) void attn_tap_bwd_q_kernel(
     for (int nb = 0; nb < NB; ++nb) ycell[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
   };
 
+#if BEVR_DROP
+  auto tile = [&](const char* base, int t, uint32_t kh) {
+#else
   auto tile = [&](const char* base, int t) {
+#endif
     const bf16x8 a0 = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(base + a_off + t * 1024));
     const bf16x8 a1 = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(base + a_off + t * 1024 + 512));
     const bf16x8 wt = lds_tr8(base + L::OFF_TAPS + t_off + t * 1024, 512);
@@ -119,10 +135,21 @@ __global__ __launch_bounds__(512, 4) void attn_tap_bwd_q_kernel(
       const f32x4 p0 = mfma16<PREC>(a0, hop[nb], z4);
       const f32x4 p1 = mfma16<PREC>(a1, hop[nb], z4);
       u32x4 dsw;
+#if BEVR_DROP
+      float ds[8];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        ds[k] = fast_exp2(s0[k]) * (tap_drop_keep8(hrow[nb], kh, k, drop_thr) ? p0[k] : ndel[nb]);
+        ds[4 + k] = fast_exp2(s1[k]) * (tap_drop_keep8(hrow[nb], kh, 4 + k, drop_thr) ? p1[k] : ndel[nb]);
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) dsw[k] = Half<PREC>::pack2(ds[2 * k], ds[2 * k + 1]);
+#else
       dsw[0] = Half<PREC>::pack2(fast_exp2(s0[0]) * p0[0], fast_exp2(s0[1]) * p0[1]);
       dsw[1] = Half<PREC>::pack2(fast_exp2(s0[2]) * p0[2], fast_exp2(s0[3]) * p0[3]);
       dsw[2] = Half<PREC>::pack2(fast_exp2(s1[0]) * p1[0], fast_exp2(s1[1]) * p1[1]);
       dsw[3] = Half<PREC>::pack2(fast_exp2(s1[2]) * p1[2], fast_exp2(s1[3]) * p1[3]);
+#endif
       const bf16x8 ds8 = __builtin_bit_cast(bf16x8, dsw);
       ytap[nb] = mfma16<PREC>(wt, ds8, ytap[nb]);
       ycell[nb] = mfma16<PREC>(wct, ds8, ycell[nb]);
@@ -151,7 +178,11 @@ __global__ __launch_bounds__(512, 4) void attn_tap_bwd_q_kernel(
             bop[nb] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(img + min(blk0 + nb, nblk - 1) * 512));
         }
       }
+#if BEVR_DROP
+      tile(base, t, tap_drop_key0(key0 + (uint32_t)__builtin_amdgcn_readfirstlane((int)ct[3]) + 32u * t, kg));
+#else
       tile(base, t);
+#endif
     }
   }
   if (have != 0) flush();
@@ -165,7 +196,7 @@ __global__ __launch_bounds__(512, 4) void attn_tap_bwd_q_kernel(
 
 template <int PREC>
 int launch(const bevr_attn_desc& d, const void* G, const void* H, const void* tap_ws,
-           const float* table_pair, float* dG, float* dtable, hipStream_t st) {
+           const float* table_pair, float* dG, float* dtable, hipStream_t st TAP_DROP_PARAMS) {
   typedef LdsT L;
   const int n_ph = d.n_prob * d.heads;
   const int grid = ((n_ph + 7) / 8) * 8 * d.S;
@@ -177,7 +208,7 @@ int launch(const bevr_attn_desc& d, const void* G, const void* H, const void* ta
   const dim3 block(64 * (n_cw + 1));
 #define BEVR_TAP_LAUNCH(NB_)                                                                                            \
   hipLaunchKernelGGL((attn_tap_bwd_q_kernel<PREC, NB_>), dim3(grid), block, lds, st, d, (const char*)G, (const char*)H,     \
-                     (const char*)tap_ws, (const char*)table_pair, dG, dtable)
+                     (const char*)tap_ws, (const char*)table_pair, dG, dtable TAP_DROP_ARGS)
   if (nb == 1) BEVR_TAP_LAUNCH(1);
   else if (nb == 2) BEVR_TAP_LAUNCH(2);
   else BEVR_TAP_LAUNCH(4);
@@ -187,8 +218,15 @@ int launch(const bevr_attn_desc& d, const void* G, const void* H, const void* ta
 
 }  // namespace
 
+#if BEVR_DROP
+extern "C" int bevr_attn_tap_bwd_q_dropout(const bevr_attn_desc* d, const void* G, const void* H, const void* tap_ws,
+                                           const float* table_pair, float* dG, float* dtable, unsigned key0,
+                                           unsigned drop_thr, unsigned drop_seed, void* stream) {
+  if (drop_thr >= 65536u) return BEVR_E_SHAPE;
+#else
 extern "C" int bevr_attn_tap_bwd_q(const bevr_attn_desc* d, const void* G, const void* H, const void* tap_ws,
                                    const float* table_pair, float* dG, float* dtable, void* stream) {
+#endif
   int rc = bevr_check_desc(d);
   if (rc) return rc;
   if (!G || !H || !tap_ws || !table_pair || !dG || !dtable) return BEVR_E_NULL;
@@ -196,7 +234,7 @@ extern "C" int bevr_attn_tap_bwd_q(const bevr_attn_desc* d, const void* G, const
   if (!bevr_aligned16(G) || !bevr_aligned16(H) || !bevr_aligned16(tap_ws) || !bevr_aligned16(table_pair) || !bevr_aligned16(dG))
     return BEVR_E_ALIGN;
   hipStream_t st = (hipStream_t)stream;
-  if (d->precision == BEVR_PREC_BF16) return launch<BEVR_PREC_BF16>(*d, G, H, tap_ws, table_pair, dG, dtable, st);
-  if (d->precision == BEVR_PREC_F16) return launch<BEVR_PREC_F16>(*d, G, H, tap_ws, table_pair, dG, dtable, st);
+  if (d->precision == BEVR_PREC_BF16) return launch<BEVR_PREC_BF16>(*d, G, H, tap_ws, table_pair, dG, dtable, st TAP_DROP_ARGS);
+  if (d->precision == BEVR_PREC_F16) return launch<BEVR_PREC_F16>(*d, G, H, tap_ws, table_pair, dG, dtable, st TAP_DROP_ARGS);
   return BEVR_E_PRECISION;
 }

@@ -25,10 +25,20 @@ namespace {
 // NB: 16-row blocks per row-block wave (at most 7 row-block waves + the producer: fewer, fatter waves beat one wave per
 // block by 1.5x -- the barrier is cheaper and the A operand is read once per wave).  EXACT: online maximum (the recompute
 // pass of flagged columns).
+#if BEVR_DROP
+// (the eight keep hashes of a tile are in flight together: NB = 2 needs more than the 80 registers of 6 waves per SIMD)
+#define TAP_FWD_WAVES(NB_) ((NB_) == 1 ? 6 : 4)
+#else
+#define TAP_FWD_WAVES(NB_) ((NB_) == 4 ? 4 : 6)
+#endif
 template <int PREC, int NB, bool EXACT>
-__global__ __launch_bounds__(512, (NB == 4 ? 4 : 6)) void attn_tap_fwd_kernel(
+__global__ __launch_bounds__(512, TAP_FWD_WAVES(NB)) void attn_tap_fwd_kernel(
     bevr_attn_desc d, const char* __restrict__ G, const char* __restrict__ tap_ws,
-    const char* __restrict__ table_pair, float* __restrict__ mref, float* __restrict__ R, int* __restrict__ flags) {
+    const char* __restrict__ table_pair, float* __restrict__ mref, float* __restrict__ R, int* __restrict__ flags
+#if BEVR_DROP
+    , float* __restrict__ lsum TAP_DROP_PARAMS
+#endif
+    ) {
   typedef LdsT L;
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -77,6 +87,15 @@ __global__ __launch_bounds__(512, (NB == 4 ? 4 : 6)) void attn_tap_fwd_kernel(
     r[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
     sh[nb] = -3.0e38f;
   }
+#if BEVR_DROP
+  uint32_t hrow[NB];  // the row part of the keep hash, out of the key loop
+  float ls[NB];       // this lane's share of the row sum of ALL weights (R's slot TAP_ONE holds the kept mass)
+#pragma unroll
+  for (int nb = 0; nb < NB; ++nb) {
+    hrow[nb] = bevr_drop_row(drop_seed, (uint32_t)ph, (uint32_t)(j * d.Sp + min(blk0 + nb, nblk - 1) * QB + li));
+    ls[nb] = 0.f;
+  }
+#endif
   // this lane's LDS addresses inside a buffer
   const int a_off = (kg < 2 ? L::OFF_TAPS : L::OFF_CELLS) + li * 32 + (kg & 1) * 16;     // + tile * 1024 + sub * 512
   const int t_off = L::OFF_TAPS + (4 * kg + (li >> 2)) * 32 + (lane & 3) * 8;             // + tile * 1024, second block + 512
@@ -88,7 +107,11 @@ __global__ __launch_bounds__(512, (NB == 4 ? 4 : 6)) void attn_tap_fwd_kernel(
   int have0 = 0, have1 = 0;      // allocation numbers of the table images in bop / bop1 (0: the zeroed image)
 
   // one 32-key tile against one row block: S^T (two 16-key sub-tiles) -> weights -> R += w^T P
+#if BEVR_DROP
+  auto tile = [&](const bf16x8& a0, const bf16x8& a1, const bf16x8& wt, const bf16x8& b, int nb, uint32_t kh) {
+#else
   auto tile = [&](const bf16x8& a0, const bf16x8& a1, const bf16x8& wt, const bf16x8& b, int nb) {
+#endif
     const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
     f32x4 s0 = mfma16<PREC>(a0, b, z4);
     f32x4 s1 = mfma16<PREC>(a1, b, z4);
@@ -99,15 +122,37 @@ __global__ __launch_bounds__(512, (NB == 4 ? 4 : 6)) void attn_tap_fwd_kernel(
       const float mn = fmaxf(sh[nb], tm);
       const float al2 = fast_exp2(sh[nb] - mn);
       r[nb] *= al2;
+#if BEVR_DROP
+      ls[nb] *= al2;
+#endif
       sh[nb] = mn;
       s0 -= mn;
       s1 -= mn;
     }
     u32x4 pw;
+#if BEVR_DROP
+    float p[8];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      p[k] = fast_exp2(s0[k]);
+      p[4 + k] = fast_exp2(s1[k]);
+    }
+    ls[nb] += ((p[0] + p[1]) + (p[2] + p[3])) + ((p[4] + p[5]) + (p[6] + p[7]));
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      p[k] = tap_drop_keep8(hrow[nb], kh, k, drop_thr) ? p[k] : 0.f;
+      // (the select stays on the float: moved behind the conversion it splits every v_cvt_pk into two conversions and a
+      // v_perm, one more instruction per pair)
+      asm("" : "+v"(p[k]));
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) pw[k] = Half<PREC>::pack2(p[2 * k], p[2 * k + 1]);
+#else
     pw[0] = Half<PREC>::pack2(fast_exp2(s0[0]), fast_exp2(s0[1]));
     pw[1] = Half<PREC>::pack2(fast_exp2(s0[2]), fast_exp2(s0[3]));
     pw[2] = Half<PREC>::pack2(fast_exp2(s1[0]), fast_exp2(s1[1]));
     pw[3] = Half<PREC>::pack2(fast_exp2(s1[2]), fast_exp2(s1[3]));
+#endif
     r[nb] = mfma16<PREC>(wt, __builtin_bit_cast(bf16x8, pw), r[nb]);
   };
 
@@ -143,11 +188,20 @@ __global__ __launch_bounds__(512, (NB == 4 ? 4 : 6)) void attn_tap_fwd_kernel(
     const bf16x8 a11 = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(base + a_off + 1536));
     const bf16x8 wt0 = lds_tr8(base + t_off, 512);
     const bf16x8 wt1 = lds_tr8(base + t_off + 1024, 512);
+#if BEVR_DROP
+    const uint32_t kh0 = tap_drop_key0(key0 + (uint32_t)__builtin_amdgcn_readfirstlane((int)ct[3]), kg);
+    const uint32_t kh1 = kh0 + 32u * 0xC2B2AE3Du;
+#endif
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
       if (NB > 1 && blk0 + nb >= nblk) continue;
+#if BEVR_DROP
+      tile(a00, a01, wt0, bop[nb], nb, kh0);
+      tile(a10, a11, wt1, bop1[nb], nb, kh1);
+#else
       tile(a00, a01, wt0, bop[nb], nb);
       tile(a10, a11, wt1, bop1[nb], nb);
+#endif
     }
   }
 
@@ -158,10 +212,20 @@ __global__ __launch_bounds__(512, (NB == 4 ? 4 : 6)) void attn_tap_fwd_kernel(
     if (blk0 + nb >= nblk) continue;
     *reinterpret_cast<f32x4*>(R + mqv[nb] * TAP_SLOTS + 4 * kg) = r[nb];
     const int row = (blk0 + nb) * QB + li;
+#if BEVR_DROP
+    float lall = ls[nb];     // one cross-lane reduction: the four lane groups hold four keys of every 16 each
+    lall += __shfl_xor(lall, 16);
+    lall += __shfl_xor(lall, 32);
+    if (kg == 0) lsum[mqv[nb]] = lall;
+#endif
     if constexpr (EXACT) {
       if (kg == 0) mref[mqv[nb]] += sh[nb];
     } else {
+#if BEVR_DROP
+      const float l = lall;  // the UNMASKED mass: a row whose kept keys are few is not an underflowed row
+#else
       const float l = r[nb][3];
+#endif
       if (kg == 3 && row < d.S && !(l >= 7.9e-31f && l < 3.0e38f)) bad = true;
     }
   }
@@ -172,7 +236,11 @@ __global__ __launch_bounds__(512, (NB == 4 ? 4 : 6)) void attn_tap_fwd_kernel(
 
 template <int PREC>
 int launch(const bevr_attn_desc& d, const void* G, const void* tap_ws, const float* table_pair,
-           float* mref, float* R, int* flags, hipStream_t st) {
+           float* mref, float* R, int* flags, hipStream_t st
+#if BEVR_DROP
+           , float* lsum TAP_DROP_PARAMS
+#endif
+           ) {
   typedef LdsT L;
   const int n_ph = d.n_prob * d.heads;
   const int grid = ((n_ph + 7) / 8) * 8 * d.S;
@@ -183,9 +251,14 @@ int launch(const bevr_attn_desc& d, const void* G, const void* tap_ws, const flo
   if (nblk > 28) return BEVR_E_SHAPE;
   const int n_cw = (nblk + nb - 1) / nb;
   const dim3 block(64 * (n_cw + 1));
+#if BEVR_DROP
+#define BEVR_TAP_FWD_DROP_ARGS , lsum TAP_DROP_ARGS
+#else
+#define BEVR_TAP_FWD_DROP_ARGS
+#endif
 #define BEVR_TAP_LAUNCH(NB_, EX_)                                                                                     \
   hipLaunchKernelGGL((attn_tap_fwd_kernel<PREC, NB_, EX_>), dim3(grid), block, lds, st, d, (const char*)G,          \
-                     (const char*)tap_ws, (const char*)table_pair, mref, R, flags)
+                     (const char*)tap_ws, (const char*)table_pair, mref, R, flags BEVR_TAP_FWD_DROP_ARGS)
   for (int ex = 0; ex < 2; ++ex) {
     if (nb == 1) { if (ex) BEVR_TAP_LAUNCH(1, true); else BEVR_TAP_LAUNCH(1, false); }
     else if (nb == 2) { if (ex) BEVR_TAP_LAUNCH(2, true); else BEVR_TAP_LAUNCH(2, false); }
@@ -199,15 +272,23 @@ int launch(const bevr_attn_desc& d, const void* G, const void* tap_ws, const flo
 
 }  // namespace
 
+#if BEVR_DROP
+extern "C" int bevr_attn_tap_fwd_dropout(const bevr_attn_desc* d, const void* G, const void* tap_ws,
+                                         const float* table_pair, float* mref, float* R, float* lsum, int* flags,
+                                         unsigned key0, unsigned drop_thr, unsigned drop_seed, void* stream) {
+  if (drop_thr >= 65536u) return BEVR_E_SHAPE;
+  if (!lsum) return BEVR_E_NULL;
+#else
 extern "C" int bevr_attn_tap_fwd(const bevr_attn_desc* d, const void* G, const void* tap_ws,
                                  const float* table_pair, float* mref, float* R, int* flags, void* stream) {
+#endif
   int rc = bevr_check_desc(d);
   if (rc) return rc;
   if (!G || !tap_ws || !table_pair || !mref || !R || !flags) return BEVR_E_NULL;
   if (d->groups != 1) return BEVR_E_SHAPE;
   if (!bevr_aligned16(G) || !bevr_aligned16(tap_ws) || !bevr_aligned16(table_pair) || !bevr_aligned16(R)) return BEVR_E_ALIGN;
   hipStream_t st = (hipStream_t)stream;
-  if (d->precision == BEVR_PREC_BF16) return launch<BEVR_PREC_BF16>(*d, G, tap_ws, table_pair, mref, R, flags, st);
-  if (d->precision == BEVR_PREC_F16) return launch<BEVR_PREC_F16>(*d, G, tap_ws, table_pair, mref, R, flags, st);
+  if (d->precision == BEVR_PREC_BF16) return launch<BEVR_PREC_BF16>(*d, G, tap_ws, table_pair, mref, R, flags, st BEVR_TAP_FWD_DROP_ARGS);
+  if (d->precision == BEVR_PREC_F16) return launch<BEVR_PREC_F16>(*d, G, tap_ws, table_pair, mref, R, flags, st BEVR_TAP_FWD_DROP_ARGS);
   return BEVR_E_PRECISION;
 }

@@ -144,7 +144,10 @@ class SCADeformableAttention(nn.Module):
         passes True.  Only then, in the bf16 operand mode and with the offsets inside the tanh range (_pinned_keys_tap),
         does the segment run on the TAP kernels, which never form K and V and are exact only for keys that sample inside
         the top-left 4 x 3 feature pixels (csrc/attn_tap.h; the DEBUG build traps on a key outside them).  Without the
-        promise a caller's own reference_points / split stay on the cell kernels."""
+        promise a caller's own reference_points / split stay on the cell kernels.
+        Attention dropout (training mode, attn_drop_rate > 0): the keep mask lives in the region kernels and in the tap
+        kernels.  A split that runs on the tap kernels is kept (scattered keys: region dropout kernels, pinned keys: tap
+        dropout kernels, one mask); any other split is dropped and every key runs on the region kernels."""
         B, V, C, Hi, Wi = x.shape
         S = query.shape[-1]
         if V != self.n_views:
@@ -154,8 +157,11 @@ class SCADeformableAttention(nn.Module):
         N = pos.shape[3]
         pos = pos.reshape(B * V * g, N, 2)
         drop = attention_dropout(self)      # (p, seed) in training mode with attn_drop_rate > 0, else None
-        if drop is not None:
-            cell_split = None               # the keep mask lives in the region kernels: every key goes there
+        if drop is not None and not (split_is_pinned and self._pinned_keys_tap(S, Hi, Wi) and x.is_cuda
+                                     and ops.kv_source_supported(C, self.n_heads, g, self.precision)):
+            # the keep mask lives in the region and the tap kernels: the pinned keys keep their segment when it runs on the
+            # tap kernels, otherwise every key goes to the region kernels
+            cell_split = None
         if cell_split is not None and cell_split < N and g == 1:
             # groups > 1: a key is one row of K built from all groups' samples, so the groups cannot be ordered
             # independently; the split is simply not used then
@@ -178,7 +184,8 @@ class SCADeformableAttention(nn.Module):
             feat = (xf if xf.dtype == torch.bfloat16 else xf.float()).permute(0, 2, 3, 1).contiguous()
             o = ops.attention_core(query, None, None, pos, self.rpe_table, heads=self.n_heads, groups=g, views=V,
                                    precision=self.precision, kv_source=(feat, Wkv, bkv), cell_split=cell_split,
-                                   tap_source=bool(split_is_pinned) and cell_split is not None and self._pinned_keys_tap(S, Hi, Wi),
+                                   tap_source="pinned" if (split_is_pinned and cell_split is not None
+                                                           and self._pinned_keys_tap(S, Hi, Wi)) else False,
                                    attn_drop=drop, concat_views=True)
         else:
             xs = ops.sample_features(xf, pos, g)                                     # (B*V, N, C)

@@ -595,7 +595,8 @@ class _AttnCore(torch.autograd.Function):
         _require_gpu(Qp, kv, key_a, key_b, Tt, feat, spos, Wkv, bkv)
         L = _lib.lib()
         ed = _edtype(geom.precision)
-        # drop = (thr16, seed): attention dropout, region kernels only (the keep mask is a function of (seed, ph, mq, n))
+        # drop = (thr16, seed): attention dropout, region kernels only here (the keep mask is a function of
+        # (seed, ph, mq, n), n from 0: a tap segment behind these keys hashes on from n = split, attention_core)
         ctx.drop = drop if drop and drop[0] > 0 else None
         x3 = geom.precision == _lib.PREC_BF16X3
         Qe = _split_rows(Qp.float()) if x3 else Qp.to(ed).contiguous()
@@ -911,8 +912,16 @@ def attention_core(query: torch.Tensor, kproj: Optional[torch.Tensor], vproj: Op
     O = Rn Vpix, both thin GEMMs here -- and the segment is merged with the region kernels' through (O, LSE).
     attn_drop = (p, seed): dropout on the softmax weights (the reference's attn_drop, :402-409): a weight is kept with
     probability 1 - p (p rounded to 1/65536) and scaled by 1 / (1 - p); the mask is the function dropout_keep_mask of
-    (seed, problem-head, query, key) that the forward and backward kernels share.  Every key then runs on the region
-    kernels (cell_split / tap_source are ignored).
+    (seed, problem-head, query, key) that the forward and backward kernels share.  With tap_source (and a call the tap
+    kernels support) the split is kept: keys [0, cell_split) run on the region dropout kernels, keys [cell_split, N) on
+    the tap dropout kernels (csrc/attn_tap_*_drop.hip), which hash the same mask from key index cell_split on.  Without
+    tap_source every key runs on the region kernels (cell_split is ignored: the cell, gather and slab kernels have no mask).
+    Until the tap kernels had a mask, dropout ignored tap_source whatever the keys were; so with dropout tap_source=True
+    is CHECKED: the split is kept only if it leaves a region segment (cell_split > 0) and every key of [cell_split, N)
+    samples inside the tap grid (one reduction over the positions and a host sync per call); otherwise every key runs on
+    the region kernels as before (tests/test_gpu_random_sweep_dropout.py pins that for arbitrary keys and splits).
+    tap_source="pinned" is the promise without the check (SCADeformableAttention: split_is_pinned and the offset range
+    bound the positions).
     Returns (B*views, S*S, C): per view softmax(QK^T c^-0.5 + bias) V, rows in i*S + j order -- or, with
     concat_views=True, (B, S*S, views*C): the views side by side in the channel axis (unpack_out_views: what SCA's
     proj_out contracts, written in one pass).
@@ -925,7 +934,9 @@ def attention_core(query: torch.Tensor, kproj: Optional[torch.Tensor], vproj: Op
         if not 0 < thr < 65536:
             raise ValueError("attention dropout probability must lie in (0, 1)")
         drop = (thr, int(attn_drop[1]) & 0xFFFFFFFF)
-        cell_split, tap_source = None, None
+        if not (tap_source and cell_split is not None and kv_source is not None and tap_supported(precision, groups)
+                and 16 * ((S + 15) // 16) <= 448):
+            cell_split, tap_source = None, None
     if kv_source is not None:
         if kv is not None or kproj is not None or vproj is not None:
             raise ValueError("pass kv_source alone")
@@ -950,6 +961,14 @@ def attention_core(query: torch.Tensor, kproj: Optional[torch.Tensor], vproj: Op
     Wt = rpe_table.shape[-1]
     if rpe_table.shape[-2] != 2 * S - 1:
         raise ValueError("rpe_table height must be 2S-1")
+    if drop is not None and tap_source and tap_source != "pinned" and split < N:
+        ok = split > 0          # no region segment beside it: the route dropout always took for such a call
+        if ok:
+            ky = (pos[:, split:, 0].float() + 1.0) * (0.5 * (feat.shape[1] - 1))
+            kx = (pos[:, split:, 1].float() + 1.0) * (0.5 * (feat.shape[2] - 1))
+            ok = bool(((ky < TAP_R - 1) & (kx < TAP_C - 1)).all())      # csrc/attn_tap_prep.hip: the tap contract
+        if not ok:
+            tap_source, split = None, N
     tap = bool(tap_source) and split < N
     if tap and (kv_source is None or not tap_supported(precision, groups) or 16 * ((S + 15) // 16) > 448):
         raise ValueError("tap_source needs kv_source, groups == 1, a 16-bit operand mode and S <= 448")
@@ -977,7 +996,7 @@ def attention_core(query: torch.Tensor, kproj: Optional[torch.Tensor], vproj: Op
     O_r = LSE_r = None
     if split > 0:
         O_r, LSE_r = _AttnCore.apply(Qp, None, a[:, :split], b[:, :split], Tt, geom, split, feat,
-                                     pos[:, :split].float().contiguous(), Wkv, bkv)
+                                     pos[:, :split].float().contiguous(), Wkv, bkv, drop)
     # the 12 pixels' K | V rows, without the bias: (B', 12, 2C); rows the image does not have are zero (zero padding)
     fpix = feat[:, :TAP_R, :TAP_C, :].float()
     fpix = F.pad(fpix, (0, 0, 0, TAP_C - fpix.shape[2], 0, TAP_R - fpix.shape[1])).reshape(Bp, TAP_N, Cc)
@@ -990,10 +1009,22 @@ def attention_core(query: torch.Tensor, kproj: Optional[torch.Tensor], vproj: Op
     tgeom = dc_replace(geom, N=N - split)
     key_y = (pos[:, split:, 0].float() + 1.0) * (0.5 * (Hi - 1))
     key_x = (pos[:, split:, 1].float() + 1.0) * (0.5 * (Wi - 1))
-    Rn, LSE_c = _TapAttn.apply(G, a[:, split:], b[:, split:], key_y, key_x, Tt, tgeom)
+    mass = None
+    if drop is not None:
+        # dropout acts on P after the softmax and Rn is linear in P: Rn' = sum_n keep D P w, the kept mass m' = sum_n keep D P
+        # (1 without dropout) multiplies bv, LSE is of all keys.  One mask for the whole call: the tap keys hash n = split + n'
+        Rn, mass, LSE_c = _TapAttn.apply(G, a[:, split:], b[:, split:], key_y, key_x, Tt, tgeom, (drop[0], drop[1], split))
+    else:
+        Rn, LSE_c = _TapAttn.apply(G, a[:, split:], b[:, split:], key_y, key_x, Tt, tgeom)
     LSE_c = (LSE_c.reshape(B, V, heads, geom.Mp) + Gb[:, None]).reshape(Bp, heads, geom.Mp)
     Vp = F.pad(kvp[..., Cc:].reshape(Bp, TAP_N, heads, c), (0, pad_c)).permute(0, 2, 1, 3)          # (B', h, 12, 32)
     bv = F.pad(bkv[Cc:].float().reshape(1, heads, 1, c), (0, pad_c))
+    if mass is not None:
+        # (the fused merge_tap assumes a mass of 1)
+        O_c = torch.matmul(Rn, Vp) + mass[..., None] * bv
+        if O_r is None:
+            return _unpacked(O_c, S, c, views, concat_views)
+        return _unpacked(O_r, S, c, views, concat_views, LSE_r, O_c, LSE_c)
     if O_r is not None and c % 4 == 0 and os.environ.get("BEVR_MERGE_TAP", "1") != "0":
         # the two halves of the softmax merged and unpacked in one pass, the tap half's O = Rn Vpix + bv formed on the way
         return merge_tap(O_r, LSE_r, Rn, LSE_c, Vp, bv.reshape(heads, HEAD_DIM), S, c, views if concat_views else 1)
@@ -1047,10 +1078,15 @@ class _TapAttn(torch.autograd.Function):
         LSE[q]   = log2 sum_n 2^S[n][q]                 (P, h, Mp)
     Both outputs are differentiable (the caller turns Rn into O = Rn Vpix + bv and merges LSE with the other key segment
     of the same softmax in plain torch code).  G (P, h, Mp, 12) float: log2-domain logit per tap; key_a, key_b (P, N)
-    table coordinates, key_y, key_x (P, N) sampling positions in feature pixels; Tt the packed table (pack_table)."""
+    table coordinates, key_y, key_x (P, N) sampling positions in feature pixels; Tt the packed table (pack_table).
+    drop = (thr16, seed, key0): attention dropout (the tap dropout kernels; the mask is dropout_keep_mask's at key index
+    key0 + n).  Three outputs then, all differentiable, with D = 65536 / (65536 - thr16):
+        Rn'[q][t] = sum_n keep D softmax_n(S)[n][q] w_t(n),   m'[q] = sum_n keep D softmax_n(S)[n][q]   (P, h, Mp),
+        LSE as above (of ALL keys: the mask acts after the softmax)
+    and the caller's output is O = Rn' Vpix + m' bv."""
 
     @staticmethod
-    def forward(ctx, G, key_a, key_b, key_y, key_x, Tt, geom: AttnGeom):
+    def forward(ctx, G, key_a, key_b, key_y, key_x, Tt, geom: AttnGeom, drop=None):
         _require_gpu(G, key_a, key_b, key_y, key_x, Tt)
         L = _lib.lib()
         ed = _edtype(geom.precision)
@@ -1075,10 +1111,28 @@ class _TapAttn(torch.autograd.Function):
         # zeros: the kernels work in 16-row blocks and never touch the rows past the last block of a column
         R = torch.zeros(P, h, Mp, TAP_SLOTS, device=dev, dtype=torch.float32)
         flags = torch.zeros(P * h, geom.S, device=dev, dtype=torch.int32)
+        ctx.drop = drop if drop and drop[0] > 0 else None
+        valid = (torch.arange(Mp, device=dev) % geom.Sp) < geom.S
+        if ctx.drop:
+            thr, seed, key0 = ctx.drop
+            lsum = torch.zeros(P, h, Mp, device=dev, dtype=torch.float32)
+            _lib.check(KERNEL_TIMER.run("bevr_attn_tap_fwd_dropout", _attn_flops(geom, 2), L.bevr_attn_tap_fwd_dropout,
+                                        C.byref(d), _ptr(G16), _ptr(ws), _ptr(pair), _ptr(mref), _ptr(R), _ptr(lsum),
+                                        _ptr(flags), key0, thr, seed, _stream(), tag=_call_tag(geom)),
+                       "bevr_attn_tap_fwd_dropout")
+            # R holds the kept weights (slot 15: the kept mass), lsum the row sum of all of them
+            l = torch.where(valid, lsum, torch.ones_like(mref))
+            LSE = torch.where(valid, mref + torch.log2(l), torch.zeros_like(mref))
+            sc = torch.where(valid, (65536.0 / (65536.0 - thr)) / l, torch.zeros_like(l))
+            Rn = R[..., :TAP_N] * sc[..., None]
+            mass = R[..., 15] * sc
+            ctx.geom = geom
+            ctx.save_for_backward(G16, Rn, LSE, ws, pair, Ttc, mass)
+            ctx.set_materialize_grads(False)
+            return Rn, mass, LSE
         _lib.check(KERNEL_TIMER.run("bevr_attn_tap_fwd", _attn_flops(geom, 2), L.bevr_attn_tap_fwd, C.byref(d), _ptr(G16),
                                     _ptr(ws), _ptr(pair), _ptr(mref), _ptr(R), _ptr(flags), _stream(), tag=_call_tag(geom)), "bevr_attn_tap_fwd")
         # rows past the grid: Rn = 0, LSE = 0 (finite: the caller's merge with the other key segment stays finite there)
-        valid = (torch.arange(Mp, device=dev) % geom.Sp) < geom.S
         l = torch.where(valid, R[..., 15], torch.ones_like(mref))
         LSE = torch.where(valid, mref + torch.log2(l), torch.zeros_like(mref))
         Rn = torch.where(valid[:, None], R[..., :TAP_N] / l[..., None], torch.zeros_like(R[..., :TAP_N]))
@@ -1088,9 +1142,13 @@ class _TapAttn(torch.autograd.Function):
         return Rn, LSE
 
     @staticmethod
-    def backward(ctx, dRn, dLSE):
+    def backward(ctx, dRn, *rest):
         geom: AttnGeom = ctx.geom
-        G16, Rn, LSE, ws, pair, Ttc = ctx.saved_tensors
+        drop = ctx.drop
+        dmass, dLSE = rest if drop else (None, rest[0])
+        G16, Rn, LSE, ws, pair, Ttc, *more = ctx.saved_tensors
+        # dropout: the kernels take D = 65536 / (65536 - thr) folded into H
+        Dk = 65536.0 / (65536.0 - drop[0]) if drop else 1.0
         L = _lib.lib()
         ed = G16.dtype
         dev = G16.device
@@ -1108,13 +1166,22 @@ class _TapAttn(torch.autograd.Function):
                 big = torch.maximum(big, dRn.abs().max())
             if dLSE is not None:
                 big = torch.maximum(big, dLSE.abs().max())
-            sdo = torch.exp2(torch.floor(8.0 - torch.log2(big.clamp_min(1e-30))))
+            if dmass is not None:
+                big = torch.maximum(big, dmass.abs().max())
+            # (dropout: the H operand carries D times the cotangent -- ceil(log2 D) binades of the room go to it)
+            sdo = torch.exp2(torch.floor(8.0 - torch.log2(big.clamp_min(1e-30))) - math.ceil(math.log2(Dk)))
             dRn = None if dRn is None else dRn * sdo
             dLSE = None if dLSE is None else dLSE * sdo
+            dmass = None if dmass is None else dmass * sdo
         if dRn is not None:
-            H16[..., :TAP_N] = dRn * LN2
+            H16[..., :TAP_N] = dRn * (LN2 * Dk)
+        if dmass is not None:
+            H16[..., 15] = dmass * (LN2 * Dk)     # the cotangent of the kept mass: the droppable part of the constant
         # delta from the values the kernel contracts (the rounded H): dS = P (dP - delta) then cancels where P -> 1
         delta = (Rn * H16[..., :TAP_N].float()).sum(-1)
+        if drop:
+            # delta = sum_n P keep (w . H + H_one) = (Rn' . H + m' H_one) / D  (Rn', m' carry D, and so does H)
+            delta = (delta + more[0] * H16[..., 15].float()) / Dk
         if dLSE is not None:
             delta = delta - dLSE
         _set_offset(H16, -delta)
@@ -1122,17 +1189,26 @@ class _TapAttn(torch.autograd.Function):
         _set_offset(Gq, torch.where(valid, -LSE, torch.full_like(LSE, _neg_big(ed))))
         dG = torch.zeros(P, h, Mp, TAP_SLOTS, device=dev, dtype=torch.float32)     # rows past the last 16-row block: never written
         dT = torch.zeros_like(Ttc)
-        _lib.check(KERNEL_TIMER.run("bevr_attn_tap_bwd_q", _attn_flops(geom, 3), L.bevr_attn_tap_bwd_q, C.byref(d), _ptr(Gq),
-                                    _ptr(H16), _ptr(ws), _ptr(pair), _ptr(dG), _ptr(dT), _stream(), tag=_call_tag(geom)), "bevr_attn_tap_bwd_q")
         dk = [torch.zeros(P, geom.Np, device=dev, dtype=torch.float32) for _ in range(4)]
-        _lib.check(KERNEL_TIMER.run("bevr_attn_tap_bwd_k", _attn_flops(geom, 4), L.bevr_attn_tap_bwd_k, C.byref(d), _ptr(Gq),
-                                    _ptr(H16), _ptr(ws), _ptr(Ttc), *[_ptr(t) for t in dk], _stream(), tag=_call_tag(geom)), "bevr_attn_tap_bwd_k")
+        if drop:
+            thr, seed, key0 = drop
+            _lib.check(KERNEL_TIMER.run("bevr_attn_tap_bwd_q_dropout", _attn_flops(geom, 3), L.bevr_attn_tap_bwd_q_dropout,
+                                        C.byref(d), _ptr(Gq), _ptr(H16), _ptr(ws), _ptr(pair), _ptr(dG), _ptr(dT), key0, thr,
+                                        seed, _stream(), tag=_call_tag(geom)), "bevr_attn_tap_bwd_q_dropout")
+            _lib.check(KERNEL_TIMER.run("bevr_attn_tap_bwd_k_dropout", _attn_flops(geom, 4), L.bevr_attn_tap_bwd_k_dropout,
+                                        C.byref(d), _ptr(Gq), _ptr(H16), _ptr(ws), _ptr(Ttc), *[_ptr(t) for t in dk], key0,
+                                        thr, seed, _stream(), tag=_call_tag(geom)), "bevr_attn_tap_bwd_k_dropout")
+        else:
+            _lib.check(KERNEL_TIMER.run("bevr_attn_tap_bwd_q", _attn_flops(geom, 3), L.bevr_attn_tap_bwd_q, C.byref(d), _ptr(Gq),
+                                        _ptr(H16), _ptr(ws), _ptr(pair), _ptr(dG), _ptr(dT), _stream(), tag=_call_tag(geom)), "bevr_attn_tap_bwd_q")
+            _lib.check(KERNEL_TIMER.run("bevr_attn_tap_bwd_k", _attn_flops(geom, 4), L.bevr_attn_tap_bwd_k, C.byref(d), _ptr(Gq),
+                                        _ptr(H16), _ptr(ws), _ptr(Ttc), *[_ptr(t) for t in dk], _stream(), tag=_call_tag(geom)), "bevr_attn_tap_bwd_k")
         da, db, dy, dx = (t[:, :geom.N] for t in dk)
         dGo = dG[..., :TAP_N] * valid[:, None]
         if sdo is not None:
             inv = 1.0 / sdo
             dGo, da, db, dy, dx, dT = dGo * inv, da * inv, db * inv, dy * inv, dx * inv, dT * inv
-        return dGo, da, db, dy, dx, dT, None
+        return dGo, da, db, dy, dx, dT, None, None
 
 
 def tap_supported(precision: int, groups: int) -> bool:

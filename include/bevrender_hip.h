@@ -54,7 +54,9 @@ extern "C" {
 /* 6: bevr_kv_project takes `float* knorm2_max` (the largest squared K row norm per problem and head) before `groups`;
  *    new entry points bevr_merge_views_fwd / _bwd, bevr_merge_tap_fwd / _bwd, bevr_attn_bwd_prep and
  *    bevr_dwconv_res_gelu; bevr_corr_bwd with aliased operands (cam == map, n == m) writes both sides' sum into dcam and
- *    leaves dmap untouched, on every path (see its declaration); nothing else changed. */
+ *    leaves dmap untouched, on every path (see its declaration); nothing else changed.
+ *    Added since, without a new version (nothing a version-6 caller uses changed): bevr_attn_tap_fwd_dropout,
+ *    bevr_attn_tap_bwd_q_dropout, bevr_attn_tap_bwd_k_dropout (attention dropout on the tap entry points). */
 #define BEVR_ABI_VERSION 6
 
 enum {
@@ -196,8 +198,9 @@ int bevr_attn_bwd_k(const bevr_attn_desc* d, const void* Q, const void* Qt, cons
  * D = 65536 / (65536 - drop_thr): s D Pmax bound <= 2^30; fp16: D Pmax 2^kp <= 2^14 and D Pmax bound 2^kp c2 <= 2^14
  * (|D dP - delta| <= D bound: the fixed-point contributions and the fp16 operands D P', P' (D dP - delta) c2 stay in
  * range).  The forward applies D after the normalisation, to the output (its fp16 operands are the unscaled weights).
- * bevrender_amd/ops.py:dropout_keep_mask is the host twin.  Region kernels only: a caller with
- * dropout keeps every key on these entry points (the cell / tap entry points have no mask). */
+ * bevrender_amd/ops.py:dropout_keep_mask is the host twin.  The cell, gather and slab entry points have no mask: a
+ * caller with dropout keeps their keys on these entry points; the tap entry points have dropout variants of their own
+ * (bevr_attn_tap_*_dropout below), which hash the same function with an offset into the caller's key order. */
 int bevr_attn_fwd_dropout(const bevr_attn_desc* d, const void* Q, const void* K, const void* Vt,
                           const void* key_ws, const float* table_pair, float* O, float* LSE,
                           unsigned drop_thr, unsigned drop_seed, void* stream);
@@ -296,6 +299,36 @@ int bevr_attn_tap_bwd_q(const bevr_attn_desc* d, const void* G, const void* H, c
  *   wrong dkey_a / dkey_b (tests/test_gpu_tap.py::test_tap_bwd_k_through_the_c_abi_as_the_header_describes). */
 int bevr_attn_tap_bwd_k(const bevr_attn_desc* d, const void* G, const void* H, const void* tap_ws,
                         const float* table, float* dkey_a, float* dkey_b, float* dkey_y, float* dkey_x, void* stream);
+
+/* Attention dropout on the tap entry points: the three above with the keep mask of bevr_attn_*_dropout (same hash, same
+ * drop_thr = round(p * 65536) < 65536, BEVR_E_SHAPE otherwise).  The pair (ph, mq, key n' of this segment) is hashed
+ * with n = key0 + n': key0 is the index of the segment's first key in the caller's key order for the whole call, so
+ * that a region segment [0, split) (bevr_attn_*_dropout, which hash from 0) and a tap segment [split, N) with
+ * key0 = split evaluate ONE mask over all N keys (bevrender_amd/ops.py:dropout_keep_mask(seed, thr, n_ph, S, N)).  A
+ * key that is emitted in several masked passes (a run that does not fit one table chunk) has one keep decision.
+ * Dropout acts on the weights after the softmax and the tap formulation is linear in them:
+ *   forward   R[slot][q] = sum_n keep w_slot(n) 2^(S[n][q] - mref[q]): the KEPT weights; rows 12, 13, 15 are the kept
+ *             mass, not the denominator.  lsum [n_prob][heads][Mp] float WRITTEN: sum_n 2^(S[n][q] - mref[q]) over ALL
+ *             keys (the segment's log2-sum-exp is mref + log2 lsum; the mask does not enter it, and the recompute of
+ *             underflowed rows is decided on it).  The caller normalises and applies D = 65536 / (65536 - drop_thr):
+ *             Rn' = D R[0..11] / lsum, kept mass m' = D R[15] / lsum, O = Rn' Vpix + m' bv.
+ *   backward  dS[n][q] = P[n][q] (keep ? sum_t w_t(n) H[t][q] + H[15][q] : 0  +  Hc[q])
+ *             H slots 0..11 = D ln2 (dO_q . Vpix_t), slot 15 = D ln2 (dO_q . bv) (the cotangent of the kept mass: the
+ *             droppable part of the constant, ONE 16-bit value as the taps'), slots 12, 13 the hi and lo parts of
+ *             Hc = -ln2 delta_q (never dropped), slot 14 zero.  delta = sum_n P keep D dP - dLSE: rowsum(dO * O) of the
+ *             merged softmax as for the region entry points.  The caller folds D into H; the fp16 operands then carry
+ *             D times the cotangent and the caller's power-of-two scaling must leave room for it.
+ *             bevr_attn_tap_bwd_k_dropout takes the value path sum_q keep P H / ln2 from the kept weights.
+ *   G, tap_ws, tables, dG, dtable, dkey_* as for the entry points above. */
+int bevr_attn_tap_fwd_dropout(const bevr_attn_desc* d, const void* G, const void* tap_ws, const float* table_pair,
+                              float* mref, float* R, float* lsum, int32_t* flags, unsigned key0, unsigned drop_thr,
+                              unsigned drop_seed, void* stream);
+int bevr_attn_tap_bwd_q_dropout(const bevr_attn_desc* d, const void* G, const void* H, const void* tap_ws,
+                                const float* table_pair, float* dG, float* dtable, unsigned key0, unsigned drop_thr,
+                                unsigned drop_seed, void* stream);
+int bevr_attn_tap_bwd_k_dropout(const bevr_attn_desc* d, const void* G, const void* H, const void* tap_ws,
+                                const float* table, float* dkey_a, float* dkey_b, float* dkey_y, float* dkey_x,
+                                unsigned key0, unsigned drop_thr, unsigned drop_seed, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Gather kernel: the FORWARD of bevr_attn_fwd for SCATTERED keys with the relative-position bias on the matrix cores
