@@ -33,9 +33,20 @@
 // underflowed against it flags its column and the EXACT instantiation -- the only one with an online maximum (the
 // maximum of the row's first tile, raised with a rescale when a later logit exceeds it) -- recomputes that column.
 // The row's largest weight is tracked beside the sums for LSE plane 1.
+//
+// BEVR_GATHER_ROWS = 1 (attn_gather_fwd_rows.hip, a translation unit of its own so that the whole-column kernels stay
+// the code they were): the ROW-RANGE kernels.  A workgroup computes the BEV rows [row0, row0 + n_rows) of its column
+// (row0 a multiple of 16, at most 14 row blocks) instead of the whole column: query rows are independent, so only the
+// row ORIGIN moves -- the table row of a tap for the band's first BEV row, the Q / mref / O / LSE rows and the rows a
+// window must hold.  Rows outside the band are not written; the band that ends at S writes the rows past the grid as the
+// whole-column kernel does.  BEV sides up to 448 run as bands of at most 224 rows (bevrender_amd/ops.py).
 #include "attn_tap.h"
 
-#ifdef BEVR_GPROF
+#ifndef BEVR_GATHER_ROWS
+#define BEVR_GATHER_ROWS 0
+#endif
+
+#if defined(BEVR_GPROF) && !BEVR_GATHER_ROWS
 __device__ unsigned long long bevr_prof_gather[32];
 extern "C" int bevr_debug_prof_gather(unsigned long long* out, int reset) {
   if (reset) { unsigned long long z[32] = {0}; return (int)hipMemcpyToSymbol(HIP_SYMBOL(bevr_prof_gather), z, sizeof(z)); }
@@ -48,6 +59,7 @@ __device__ __forceinline__ unsigned long long gprof_now() {
 }
 #define GPROF(var) const unsigned long long var = gprof_now()
 #define GPROF_ADD(i, v) gacc[i] += (v)
+#define BEVR_GPROF_ON 1
 #else
 #define GPROF(var)
 #define GPROF_ADD(i, v)
@@ -95,6 +107,17 @@ __device__ __forceinline__ int w_image_pos(int n) {
 __device__ __forceinline__ void barrier_lds() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 __device__ __forceinline__ void wait_vm0() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 constexpr float RAISE = 40.0f;   // EXACT: binades a logit may exceed the reference before the reference moves
+// fp16 operands: the weights are rounded to 5 exponent bits (largest value 2^15.99, normal down to 2^-14, zero under 2^-25).
+// The EXACT reference is put F16_LIFT binades UNDER the maximum it has seen, so that weights down to 2^-(25 + F16_LIFT) of
+// the row's largest survive, and moves when a logit exceeds it by F16_RAISE binades (2^15 is an fp16 number; the rescale
+// of already packed weights multiplies by 2^-delta <= 1).
+constexpr float F16_RAISE = 15.0f;
+constexpr float F16_LIFT = 8.0f;
+// fp16, static pass: a weight under 2^-14 is stored with an absolute error of up to 2^-25 (subnormal step 2^-24; zero
+// under 2^-25), so N keys move the row sum and the numerator of O by up to N 2^-25 (x max |V|) -- relative to the row
+// sum, which is at least the largest ROUNDED weight pmax: N 2^-25 / pmax.  Held to 2^-11, one rounding of an fp16 operand
+// (a fifth of the mode's output tolerance 2.5e-3): a row with pmax < N 2^-14 sends its column to the exact pass.
+constexpr float F16_PMAX_PER_KEY = 6.103515625e-05f;      // 2^-14
 
 template <int V> struct IntC { static constexpr int value = V; };
 typedef const char __attribute__((address_space(1)))* gptr_t;
@@ -104,11 +127,22 @@ __device__ __forceinline__ void glds16(const char* src, char* lds_base) {
   __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)lds_base, 16, 0, 0);
 }
 
+#if BEVR_GATHER_ROWS
+#define BEVR_GATHER_KERNEL attn_gather_fwd_rows_kernel
+#define BEVR_GATHER_ROW_PARAMS , const int row0, const int n_rows
+#else
+#define BEVR_GATHER_KERNEL attn_gather_fwd_kernel
+#define BEVR_GATHER_ROW_PARAMS
+#endif
 template <int PREC, int NB, bool EXACT, bool DMA>
-__global__ __launch_bounds__(512, 4) void attn_gather_fwd_kernel(
+__global__ __launch_bounds__(512, 4) void BEVR_GATHER_KERNEL(
     bevr_attn_desc d, const char* __restrict__ Q, const char* __restrict__ K, const char* __restrict__ V,
     const char* __restrict__ key_ws, const uint32_t* __restrict__ table_pk, const float* __restrict__ mref,
-    float* __restrict__ O, float* __restrict__ LSE, int* __restrict__ flags) {
+    float* __restrict__ O, float* __restrict__ LSE, int* __restrict__ flags BEVR_GATHER_ROW_PARAMS) {
+  constexpr bool BAND = BEVR_GATHER_ROWS != 0;
+#if !BEVR_GATHER_ROWS
+  constexpr int row0 = 0, n_rows = 0;      // the whole column
+#endif
   typedef LdsG L;
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -125,8 +159,10 @@ __global__ __launch_bounds__(512, 4) void attn_gather_fwd_kernel(
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   const int li = lane & 15, kg = lane >> 4;
   const int Mp = d.S * d.Sp;
-  const int nblk = (d.S + QB - 1) / QB;
+  const int nblk = ((BAND ? n_rows : d.S) + QB - 1) / QB;      // row blocks of the column (BAND: of the band)
   const int rows_q = nblk * QB;
+  const int row_end = BAND ? row0 + n_rows : d.S;
+  const bool to_end = !BAND || row_end == d.S;                 // this launch owns the rows past the grid
   const float rx = (float)(d.Wt - 1) / (2.0f * (float)(d.S - 1));
   const float jrx = (float)j * rx;
   const unsigned smem_base = (unsigned)(size_t)(lptr_t)smem;     // window addresses are handed over as LDS addresses
@@ -201,6 +237,7 @@ __global__ __launch_bounds__(512, 4) void attn_gather_fwd_kernel(
         if (sb.amax < sb.amin) continue;               // a step of padding only
         const bool live = klane && step * GT + kl < d.N;
         ar = (kw.aoff >> 3) - d.x_off * d.Hp;          // padded table row of tap (y, .) for BEV row 0
+        if constexpr (BAND) ar += row0;                // ... for the band's first BEV row
         const float tx = jrx + kw.b;
         const float xf = floorf(tx);
         xc = (int)xf + d.x_off;                        // padded table column of tap (., x)
@@ -212,7 +249,7 @@ __global__ __launch_bounds__(512, 4) void attn_gather_fwd_kernel(
         const int x1 = (int)floorf(jrx + sb.bmax) + 1 + d.x_off;
         cols = x1 - x0 + 1;
         fits = cols <= WIN_COLS && sb.amax - sb.amin + rows_q + 1 <= ROWS;
-        a0w = max(0, min(sb.amin + d.y_off, d.Hp - ROWS));
+        a0w = max(0, min(sb.amin + d.y_off + (BAND ? row0 : 0), d.Hp - ROWS));
         rem = __ballot(live);
       }
       em.w = w_t;
@@ -294,7 +331,7 @@ __global__ __launch_bounds__(512, 4) void attn_gather_fwd_kernel(
       stage(cur, 0, more ? &nxt : nullptr);
       wait_vm0();
     }
-#ifdef BEVR_GPROF
+#ifdef BEVR_GPROF_ON
     unsigned long long gacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #endif
     // iteration e: the row-block waves work on emission e; the producer stages emission e + 1 (`nxt`), fills its share of
@@ -326,7 +363,7 @@ __global__ __launch_bounds__(512, 4) void attn_gather_fwd_kernel(
       GPROF_ADD(3, p4 - p3);
       GPROF_ADD(5, 1);
     }
-#ifdef BEVR_GPROF
+#ifdef BEVR_GPROF_ON
     if (lane == 0) for (int i = 0; i < 8; ++i) atomicAdd(&bevr_prof_gather[i], gacc[i]);
 #endif
     return;
@@ -346,7 +383,7 @@ __global__ __launch_bounds__(512, 4) void attn_gather_fwd_kernel(
   const unsigned qoff0 = (unsigned)(blk0 * QB + li) * 4u + (unsigned)(kg & 1) * (PITCH * 4u);
 #pragma unroll
   for (int nb = 0; nb < NB; ++nb) {
-    const int row = min(blk0 + nb, nblk - 1) * QB + li;
+    const int row = (BAND ? row0 : 0) + min(blk0 + nb, nblk - 1) * QB + li;
     const size_t mcol = (size_t)j * d.Sp + row;
     qf[nb] = __builtin_bit_cast(
         bf16x8, *reinterpret_cast<const u32x4*>(Q + ((((size_t)qb * d.heads + hd) * Mp + mcol) * 32 + 8 * kg) * 2));
@@ -370,7 +407,7 @@ __global__ __launch_bounds__(512, 4) void attn_gather_fwd_kernel(
     wait_vm0();
   }
   bool first = true;      // EXACT only
-#ifdef BEVR_GPROF
+#ifdef BEVR_GPROF_ON
   unsigned long long gacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   unsigned long long cprev = gprof_now();
 #endif
@@ -386,7 +423,7 @@ __global__ __launch_bounds__(512, 4) void attn_gather_fwd_kernel(
     GPROF_ADD(0, c1 - c0);
     GPROF_ADD(4, c0 - cprev);
     GPROF_ADD(5, 1);
-#ifdef BEVR_GPROF
+#ifdef BEVR_GPROF_ON
     cprev = c1;
 #endif
     const char* bb = smem + (e & 1) * L::BUF;
@@ -453,9 +490,11 @@ __global__ __launch_bounds__(512, 4) void attn_gather_fwd_kernel(
           if constexpr (EXACT) {
             // online reference: the maximum of the row's first keys, raised (with a rescale) when a later logit exceeds it
             const float tm = fmaxf(fmaxf(sv[nb][0], sv[nb][1]), fmaxf(sv[nb][2], sv[nb][3]));
-            if (first || __any(tm > RAISE)) {
+            constexpr float RAISE_P = PREC == BEVR_PREC_F16 ? F16_RAISE : RAISE;
+            if (first || __any(tm > RAISE_P)) {
               float tx = fmaxf(tm, __shfl_xor(tm, 16));
               tx = fmaxf(tx, __shfl_xor(tx, 32));
+              if constexpr (PREC == BEVR_PREC_F16) tx -= F16_LIFT;
               const float delta = first ? tx : fmaxf(tx, 0.f);
               const float al = first ? 1.0f : fast_exp2(-delta);
               negm[nb] -= delta;
@@ -498,7 +537,7 @@ __global__ __launch_bounds__(512, 4) void attn_gather_fwd_kernel(
   } else {
     sweep(IntC<0>{});
   }
-#ifdef BEVR_GPROF
+#ifdef BEVR_GPROF_ON
   if (lane == 0 && (wave == 0 || wave == 3)) for (int i = 0; i < 8; ++i) atomicAdd(&bevr_prof_gather[8 + (wave ? 8 : 0) + i], gacc[i]);
 #endif
 
@@ -510,8 +549,12 @@ __global__ __launch_bounds__(512, 4) void attn_gather_fwd_kernel(
     const float l = lacc[nb][0];
     float pm = fmaxf(pmx[nb], __shfl_xor(pmx[nb], 16));
     pm = fmaxf(pm, __shfl_xor(pm, 32));
-    const int row = (blk0 + nb) * QB + li;
-    if (!EXACT && row < d.S && !(l >= 7.9e-31f && l < 3.0e38f)) bad = true;
+    const int row = (BAND ? row0 : 0) + (blk0 + nb) * QB + li;
+    if (!EXACT && row < row_end && !(l >= 7.9e-31f && l < 3.0e38f)) bad = true;
+    if constexpr (!EXACT && PREC == BEVR_PREC_F16) {      // the largest weight too deep in fp16's subnormals: F16_PMAX_PER_KEY
+      if (row < row_end && !(pm >= (float)d.N * F16_PMAX_PER_KEY)) bad = true;
+    }
+    if (BAND && !to_end && row >= row_end) continue;      // rows of the next band (no shuffles below)
     // rows past the grid (zero Q rows of the last block) get their O and LSE like any other: the key-side backward
     // walks all Sp rows of a column and needs a finite LSE there; the rows no block covers take the last block's
     const float inv = 1.0f / l;
@@ -521,9 +564,20 @@ __global__ __launch_bounds__(512, 4) void attn_gather_fwd_kernel(
     *reinterpret_cast<f32x4*>(orow + 16 + 4 * kg) = o_hi[nb] * inv;
     if (kg == 0) {
       const float lg = __log2f(l);
-      const int n_copy = (blk0 + nb == nblk - 1) ? (d.Sp - row + QB - 1) / QB : 1;
+      const int n_copy = (to_end && blk0 + nb == nblk - 1) ? (d.Sp - row + QB - 1) / QB : 1;
       for (int k = 0; k < n_copy; ++k) {
-        LSE[mq + k * QB] = lg - negm[nb][0];
+        float lse0 = lg - negm[nb][0];
+        if constexpr (BAND || PREC == BEVR_PREC_F16) {
+          // A row past the grid that no block covers has Q = 0 -- its logits are the bias alone -- but carries the LSE of a
+          // REAL row: the key-side backward forms P = 2^(bias - LSE) there (times 0).  A real row whose logits all lie far
+          // under the bias (activations that explode along a recurrence) would make that P overflow: the copy is kept
+          // PAD_FLOOR binades over the padding row's own reference (an upper bound of its logits minus the headroom), which
+          // no row of ordinary size comes near in bf16; in fp16 P becomes an fp16 operand scaled for the launch's largest
+          // weight (>= 2^-60, grad_scale), so there the copy is put where P vanishes against any such scale.
+          constexpr float PAD_FLOOR = PREC == BEVR_PREC_F16 ? 70.0f : -36.0f;
+          if (k > 0) lse0 = fmaxf(lse0, mref[mq + k * QB] + PAD_FLOOR);
+        }
+        LSE[mq + k * QB] = lse0;
         // plane 1: log2 of the row's largest softmax weight
         LSE[(size_t)n_ph * Mp + mq + k * QB] = __log2f(pm) - lg;
       }
@@ -534,22 +588,29 @@ __global__ __launch_bounds__(512, 4) void attn_gather_fwd_kernel(
   }
 }
 
+// BEVR_GATHER_ROWS: the rows [row0, row0 + n_rows) of every column; else the whole column (row0, n_rows unused).
 template <int PREC>
 int launch(const bevr_attn_desc& d, const void* Q, const void* K, const void* V, const void* key_ws,
-           const void* table_pk, const float* mref, float* O, float* LSE, int* flags, hipStream_t st) {
+           const void* table_pk, const float* mref, float* O, float* LSE, int* flags, int row0, int n_rows,
+           hipStream_t st) {
   typedef LdsG L;
   const int n_ph = d.n_prob * d.heads;
   const int grid = ((n_ph + 7) / 8) * 8 * d.S;
-  const int nblk = (d.S + QB - 1) / QB;
-  // a key's taps for all BEV rows of a column must fit one window column
+  const int nblk = ((BEVR_GATHER_ROWS ? n_rows : d.S) + QB - 1) / QB;
+  // a key's taps for all BEV rows of a column (of a band) must fit one window column
   if (nblk * QB + 1 > ROWS || nblk > 14) return BEVR_E_SHAPE;
   const int nb = nblk <= 7 ? 1 : 2;      // row blocks per wave: at most 7 row-block waves + the producer
   const int n_cw = (nblk + nb - 1) / nb;
   const dim3 block(64 * (n_cw + 1));
+#if BEVR_GATHER_ROWS
+#define BEVR_GATHER_ROW_ARGS , row0, n_rows
+#else
+#define BEVR_GATHER_ROW_ARGS
+#endif
 #define BEVR_GATHER_LAUNCH(NB_, EX_, DMA_)                                                                           \
-  hipLaunchKernelGGL((attn_gather_fwd_kernel<PREC, NB_, EX_, DMA_>), dim3(grid), block, L::TOTAL, st, d,            \
+  hipLaunchKernelGGL((BEVR_GATHER_KERNEL<PREC, NB_, EX_, DMA_>), dim3(grid), block, L::TOTAL, st, d,                \
                      (const char*)Q, (const char*)K, (const char*)V, (const char*)key_ws, (const uint32_t*)table_pk, \
-                     mref, O, LSE, flags)
+                     mref, O, LSE, flags BEVR_GATHER_ROW_ARGS)
   const bool dma = d.Hp >= ROWS;        // else (small problems): the window columns are copied through registers
   for (int ex = 0; ex < 2; ++ex) {       // static reference, then the exact pass over the flagged columns
     if (nb == 1) {
@@ -568,6 +629,7 @@ int launch(const bevr_attn_desc& d, const void* Q, const void* K, const void* V,
 
 }  // namespace
 
+#if !BEVR_GATHER_ROWS
 extern "C" int bevr_attn_gather_fwd(const bevr_attn_desc* d, const void* Q, const void* K, const void* V,
                                     const void* key_ws, const void* table_pk, const float* mref, float* O, float* LSE,
                                     int* flags, void* stream) {
@@ -577,6 +639,27 @@ extern "C" int bevr_attn_gather_fwd(const bevr_attn_desc* d, const void* Q, cons
   if (!bevr_aligned16(Q) || !bevr_aligned16(K) || !bevr_aligned16(V) || !bevr_aligned16(O) || !bevr_aligned16(key_ws))
     return BEVR_E_ALIGN;
   hipStream_t st = (hipStream_t)stream;
-  if (d->precision == BEVR_PREC_BF16) return launch<BEVR_PREC_BF16>(*d, Q, K, V, key_ws, table_pk, mref, O, LSE, flags, st);
+  if (d->precision == BEVR_PREC_BF16)
+    return launch<BEVR_PREC_BF16>(*d, Q, K, V, key_ws, table_pk, mref, O, LSE, flags, 0, 0, st);
+  if (d->precision == BEVR_PREC_F16)
+    return launch<BEVR_PREC_F16>(*d, Q, K, V, key_ws, table_pk, mref, O, LSE, flags, 0, 0, st);
   return BEVR_E_PRECISION;
 }
+
+#else
+extern "C" int bevr_attn_gather_fwd_rows(const bevr_attn_desc* d, const void* Q, const void* K, const void* V,
+                                         const void* key_ws, const void* table_pk, const float* mref, float* O,
+                                         float* LSE, int* flags, int row0, int n_rows, void* stream) {
+  int rc = bevr_check_desc(d);
+  if (rc) return rc;
+  if (!Q || !K || !V || !key_ws || !table_pk || !mref || !O || !LSE || !flags) return BEVR_E_NULL;
+  if (!bevr_aligned16(Q) || !bevr_aligned16(K) || !bevr_aligned16(V) || !bevr_aligned16(O) || !bevr_aligned16(key_ws))
+    return BEVR_E_ALIGN;
+  if (d->precision != BEVR_PREC_BF16 && d->precision != BEVR_PREC_F16) return BEVR_E_PRECISION;
+  if (row0 < 0 || row0 % QB != 0 || n_rows < 1 || n_rows > 14 * QB || n_rows > d->S - row0) return BEVR_E_SHAPE;
+  hipStream_t st = (hipStream_t)stream;
+  if (d->precision == BEVR_PREC_BF16)
+    return launch<BEVR_PREC_BF16>(*d, Q, K, V, key_ws, table_pk, mref, O, LSE, flags, row0, n_rows, st);
+  return launch<BEVR_PREC_F16>(*d, Q, K, V, key_ws, table_pk, mref, O, LSE, flags, row0, n_rows, st);
+}
+#endif

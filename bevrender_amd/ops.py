@@ -539,9 +539,22 @@ class _Seg:
 
 def gather_supported(precision, S) -> bool:
     """Does the forward over scattered keys run on the gather kernel (csrc/attn_gather_fwd.hip: bias on the matrix cores,
-    table taps gathered from an LDS window) instead of the region kernel?  bf16 operands, S <= 224 (a window column holds a
-    key's taps for every BEV row of a column); BEVR_GATHER=0 turns it off (A/B timing)."""
-    return precision == _lib.PREC_BF16 and S <= 224 and os.environ.get("BEVR_GATHER", "1") != "0"
+    table taps gathered from an LDS window) instead of the region kernel?  bf16 and fp16 operands, S <= 448 (the module's
+    and the tap kernels' limit): a window column holds a key's taps for up to 224 BEV rows, a taller column runs as
+    bands (gather_bands); BEVR_GATHER=0 turns it off (A/B timing)."""
+    return precision in (_lib.PREC_BF16, _lib.PREC_F16) and S <= GATHER_MAX_S and os.environ.get("BEVR_GATHER", "1") != "0"
+
+
+GATHER_MAX_S, GATHER_BAND_ROWS = 448, 224
+
+
+def gather_bands(S):
+    """The row ranges (row0, n_rows) the gather forward covers a BEV column of S rows with: as few bands as a window
+    column allows (224 rows), of equal size up to the 16-row block -- S = 400: (0, 208), (208, 192), seven row-block
+    waves of two blocks each, the launch shape of S = 200."""
+    n = -(-S // GATHER_BAND_ROWS)
+    step = 16 * (-(-S // (16 * n)))
+    return [(r, min(step, S - r)) for r in range(0, S, step)]
 
 
 def slab_supported(precision, S, Wt=None) -> bool:
@@ -673,7 +686,7 @@ class _AttnCore(torch.autograd.Function):
                                             ctx.drop[0], ctx.drop[1], _stream(), tag=_call_tag(g)), "bevr_attn_fwd_dropout")
             elif gather_supported(g.precision, g.S):
                 if pair_pk is None:
-                    pair_pk = pair.to(torch.bfloat16)       # (h, Wp, Hp, 2) 16-bit: one dword per (column, row) entry
+                    pair_pk = pair.to(ed)                   # (h, Wp, Hp, 2) 16-bit: one dword per (column, row) entry
                     # Tt is the table in log2 units already; two-stage maximum (a reduction to `heads` outputs in one stage
                     # runs on `heads` workgroups: 0.6 ms for the 27 MB table)
                     tmax = torch.maximum(Ttc.amax(-1).amax(-1), -Ttc.amin(-1).amin(-1))
@@ -685,11 +698,22 @@ class _AttnCore(torch.autograd.Function):
                 else:
                     kmx = torch.linalg.vector_norm(Ke[:, :, :g.N], dim=-1, dtype=torch.float32).amax(-1)    # (B', h)
                 ub = 1.01 * (qn.repeat_interleave(g.q_div, 0) * kmx[..., None] + tmax[None, :, None]) + 0.01
-                mref = (ub - TAP_HEADROOM).contiguous()
-                gflags = torch.zeros(g.n_prob * g.heads * g.S, device=dev, dtype=torch.int32)
-                _lib.check(KERNEL_TIMER.run("bevr_attn_gather_fwd", _attn_flops(g, 2), L.bevr_attn_gather_fwd, C.byref(d),
-                                            _ptr(Qe), _ptr(Ke), _ptr(Ve), _ptr(key_ws), _ptr(pair_pk), _ptr(mref), _ptr(O),
-                                            _ptr(LSE), _ptr(gflags), _stream(), tag=_call_tag(g)), "bevr_attn_gather_fwd")
+                mref = (ub - tap_headroom(g.precision)).contiguous()
+                bands = gather_bands(g.S)
+                # scratch of one call's two passes: zeroed per call (per band)
+                gflags = torch.zeros(len(bands), g.n_prob * g.heads * g.S, device=dev, dtype=torch.int32)
+                if len(bands) == 1:
+                    _lib.check(KERNEL_TIMER.run("bevr_attn_gather_fwd", _attn_flops(g, 2), L.bevr_attn_gather_fwd,
+                                                C.byref(d), _ptr(Qe), _ptr(Ke), _ptr(Ve), _ptr(key_ws), _ptr(pair_pk),
+                                                _ptr(mref), _ptr(O), _ptr(LSE), _ptr(gflags), _stream(),
+                                                tag=_call_tag(g)), "bevr_attn_gather_fwd")
+                else:       # (the timer's name is the route's, whichever entry point runs it)
+                    for bi, (r0, nr) in enumerate(bands):
+                        _lib.check(KERNEL_TIMER.run("bevr_attn_gather_fwd", _attn_flops(g, 2) * nr / g.S,
+                                                    L.bevr_attn_gather_fwd_rows, C.byref(d), _ptr(Qe), _ptr(Ke), _ptr(Ve),
+                                                    _ptr(key_ws), _ptr(pair_pk), _ptr(mref), _ptr(O), _ptr(LSE),
+                                                    _ptr(gflags[bi]), r0, nr, _stream(), tag=_call_tag(g)),
+                                   "bevr_attn_gather_fwd_rows")
             else:
                 _lib.check(KERNEL_TIMER.run("bevr_attn_fwd", _attn_flops(g, 2), L.bevr_attn_fwd, C.byref(d), _ptr(Qe),
                                             _ptr(Ke), _ptr(Vt), _ptr(key_ws), _ptr(pair), _ptr(O), _ptr(LSE),

@@ -56,7 +56,9 @@ extern "C" {
  *    bevr_dwconv_res_gelu; bevr_corr_bwd with aliased operands (cam == map, n == m) writes both sides' sum into dcam and
  *    leaves dmap untouched, on every path (see its declaration); nothing else changed.
  *    Added since, without a new version (nothing a version-6 caller uses changed): bevr_attn_tap_fwd_dropout,
- *    bevr_attn_tap_bwd_q_dropout, bevr_attn_tap_bwd_k_dropout (attention dropout on the tap entry points). */
+ *    bevr_attn_tap_bwd_q_dropout, bevr_attn_tap_bwd_k_dropout (attention dropout on the tap entry points);
+ *    bevr_attn_gather_fwd_rows (the gather forward over a row range of every BEV column: BEV sides above 224), and
+ *    bevr_attn_gather_fwd accepts BEVR_PREC_F16 where it returned BEVR_E_PRECISION. */
 #define BEVR_ABI_VERSION 6
 
 enum {
@@ -334,19 +336,38 @@ int bevr_attn_tap_bwd_k_dropout(const bevr_attn_desc* d, const void* G, const vo
  * Gather kernel: the FORWARD of bevr_attn_fwd for SCATTERED keys with the relative-position bias on the matrix cores
  * (csrc/attn_gather_fwd.hip: a sparse contraction whose table side the lanes gather from an LDS window of the table;
  * any key set is handled; there is no gather backward: bevr_attn_bwd_q / _bwd_k or the slab entry point below take the
- * same operands).  BEVR_PREC_BF16 only, S <= 224.  Replaces model/SCA_deform_attn.py:331-413 and
+ * same operands).  BEVR_PREC_BF16 or BEVR_PREC_F16 (any other: BEVR_E_PRECISION), S <= 224 (a window column holds a key's
+ * taps for every BEV row of a column; taller: BEVR_E_SHAPE, see bevr_attn_gather_fwd_rows).  Replaces model/SCA_deform_attn.py:331-413 and
  * model/TSA_deform_attn.py:245-333 (reference) like the entry points above.
- *   Q, K, key_ws, O, LSE: as bevr_attn_fwd        V [n_prob][heads][Np][32] bf16 rows (not transposed)
- *   table_pk [heads][Wp][Hp] dwords: the pair table in bf16, (T2[y - y_off][x - x_off], T2[y + 1 - y_off][x - x_off]),
+ *   Q, K, key_ws, O, LSE: as bevr_attn_fwd        V [n_prob][heads][Np][32] rows of the operand type (not transposed)
+ *   table_pk [heads][Wp][Hp] dwords: the pair table in the operand type (bf16 / fp16; the key-side bilinear weights are
+ *            rounded to it too, as in that mode's other kernels), (T2[y - y_off][x - x_off], T2[y + 1 - y_off][x - x_off]),
  *            round-to-nearest of table_pair
  *   mref [n_prob][heads][Mp] float: the softmax reference of every row, as bevr_attn_tap_fwd's -- an upper bound of the
  *            row's logits minus a headroom (64 binades); rows whose weights all underflow against it (bound looser than
  *            ~160 binades) are recomputed with an online maximum: flags [n_prob * heads][S] int, zeroed by the caller,
- *            marks their columns (scratch)
+ *            marks their columns (scratch: this call's static pass writes it, its exact pass reads it).
+ *            BEVR_PREC_F16: headroom <= 8 as for bevr_attn_tap_fwd, and 5 exponent bits make the static reference useful
+ *            only near the bound -- a weight under 2^-14 is stored with an absolute error of up to 2^-25 (zero under
+ *            2^-25), N keys move a row's sum by up to N 2^-25, so a row whose LARGEST weight is under N 2^-14 (the error
+ *            could exceed 2^-11 of the sum) flags its column too.  The exact pass keeps its reference 8 binades under
+ *            the running maximum and moves it when a logit exceeds it by 15 binades (bf16: 0 and 40).
  * LSE plane 1 is log2 of an upper bound (within 2 binades) of the row's largest softmax weight. */
 int bevr_attn_gather_fwd(const bevr_attn_desc* d, const void* Q, const void* K, const void* V,
                          const void* key_ws, const void* table_pk, const float* mref, float* O, float* LSE,
                          int* flags, void* stream);
+/* The same over the BEV rows [row0, row0 + n_rows) of every BEV column of every (problem, head), for any S that
+ * bevr_check_desc accepts: query rows are independent, so a tall column is computed as bands.  Operands and precisions
+ * as above (checked in the same order), then row0 >= 0, row0 % 16 == 0, 1 <= n_rows <= 224, row0 + n_rows <= S, else
+ * BEVR_E_SHAPE.  O and both LSE planes of rows outside the range are not touched; the call with row0 + n_rows == S
+ * also writes the padding rows S .. Sp - 1 of each column as bevr_attn_gather_fwd does (LSE finite there: rows that no
+ * 16-row block covers take the last block's values), with one floor: the LSE copied into an uncovered padding row is at
+ * least mref of that row - 36 (bf16; never reached by rows of ordinary size) or mref + 70 (fp16; both entry points), so
+ * that 2^(bias - LSE), which bevr_attn_bwd_k forms for the zero Q rows there, cannot overflow its operand type.
+ * flags [n_prob * heads][S] int is zeroed by the caller before EVERY call. */
+int bevr_attn_gather_fwd_rows(const bevr_attn_desc* d, const void* Q, const void* K, const void* V,
+                              const void* key_ws, const void* table_pk, const float* mref, float* O, float* LSE,
+                              int* flags, int row0, int n_rows, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * SLAB entry points (csrc/attn_slab_bwd_q.hip): bevr_attn_bwd_q -- dQ and the rpe-table gradient of a key segment, same
