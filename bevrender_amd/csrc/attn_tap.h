@@ -47,12 +47,66 @@ __host__ __device__ __forceinline__ size_t tap_ws_box_offset(const bevr_attn_des
   return (size_t)d.n_prob * d.Np * sizeof(TapRec);
 }
 
+// BEVR_PREC_BF16X3 (bevr_common.h: split-bf16 products at f32 tolerance) on the tap kernels.  Every matrix operand is two
+// bf16 IMAGES, hi = bf16(x) and lo = bf16(x - hi), of the 16-bit modes' shape and addressing, the lo image a fixed
+// distance behind the hi image:
+//   G, H (caller-split, ops.tap_split_rows):  [2 planes][n_prob * heads * Mp rows][16 slots] bf16, plane 1 = lo
+//   A = [w | Wc] in LDS (the producer splits the f32 weights):  hi images as in LdsT, the lo images LdsTn<2>::OFF_LO behind
+//   Tsh ring image:  [rows][16 cells] hi, then the same lo (from the f32 pair table)
+//   P, dS: split in registers after exp2
+// and a product is three v_mfma_f32_16x16x32_bf16, lo hi + hi lo + hi hi (mfma16s; the logit contraction adds lo lo: mfma16s4).  The row offset c (G: Gb - reference,
+// H: -delta) is carried to FOUR bf16 parts with no further product: slot TAP_CHI holds parts 0 (hi plane) and 1 (lo plane),
+// slot TAP_CLO parts 2 and 3, all against w = 1 (hi image 1, lo image 0), so that hi lo + hi hi adds p0 + p1 + p2 + p3 = c
+// to the last bit of the float -- the logit's large constant part is exact, and the three-term product only has to carry
+// the tap and bias terms (a convex combination of 4 + 4 entries each, as in the region kernels' split mode).
+// The split instantiations live in translation units of their own (attn_tap_*_x3.hip: #define BEVR_TAP_X3 1 and #include
+// the kernel's source); in the 16-bit instantiations every `if constexpr (X3)` block is discarded.
+__host__ __device__ constexpr bool tap_x3(int prec) { return prec == BEVR_PREC_BF16X3; }
+// the 16-bit arithmetic (conversions, packing) an operand mode's images are made with
+template <int PREC> using TapHalf = Half<tap_x3(PREC) ? BEVR_PREC_BF16 : PREC>;
+#ifndef BEVR_TAP_X3
+#define BEVR_TAP_X3 0
+#endif
+
 template <int PREC> __device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c);
 template <> __device__ __forceinline__ f32x4 mfma16<BEVR_PREC_BF16>(bf16x8 a, bf16x8 b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
 template <> __device__ __forceinline__ f32x4 mfma16<BEVR_PREC_F16>(bf16x8 a, bf16x8 b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+}
+
+template <> __device__ __forceinline__ f32x4 mfma16<BEVR_PREC_BF16X3>(bf16x8 a, bf16x8 b, f32x4 c) {   // one of the three
+  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+}
+// split product (a_hi + a_lo)(b_hi + b_lo) without the lo lo term, small terms first
+__device__ __forceinline__ f32x4 mfma16s(bf16x8 ah, bf16x8 al, bf16x8 bh, bf16x8 bl, f32x4 c) {
+  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh, c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl, c, 0, 0, 0);
+  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh, c, 0, 0, 0);
+}
+// the LOGIT contraction S = A . [G ; Tsh] takes the fourth term too: one G entry carries a whole Q . Kpix product, tens of
+// binades at a large logit scale, and lo lo <= 2^-18 |w G| per tap is 2e-3 in log2 units at |G| ~ 600
+// (tests/test_gpu_tap_x3.py, the flagged-column case: 3.3e-3 against the 2e-3 limit with three terms).  The matrix pipe
+// has the room (the kernels are bound by VALU issue); dP, R, dG and Z keep three terms
+__device__ __forceinline__ f32x4 mfma16s4(bf16x8 ah, bf16x8 al, bf16x8 bh, bf16x8 bl, f32x4 c) {
+  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bl, c, 0, 0, 0);
+  return mfma16s(ah, al, bh, bl, c);
+}
+// two floats -> the packed bf16 pair of their hi parts and of their lo parts
+struct Split2 { uint32_t h, l; };
+__device__ __forceinline__ Split2 split2(float x0, float x1) {
+  const uint32_t h = pack_bf16x2(x0, x1);
+  return Split2{h, pack_bf16x2(x0 - __builtin_bit_cast(float, h << 16), x1 - __builtin_bit_cast(float, h & 0xffff0000u))};
+}
+#define TAP_SPLIT2(x0_, x1_, h_, l_) do { const Split2 sp_ = split2(x0_, x1_); (h_) = sp_.h; (l_) = sp_.l; } while (0)
+// eight floats (accumulator values of two 16-key sub-tiles) -> hi and lo B operands
+__device__ __forceinline__ void split8v(const float (&x)[8], bf16x8& h, bf16x8& l) {
+  u32x4 hw, lw;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) TAP_SPLIT2(x[2 * k], x[2 * k + 1], hw[k], lw[k]);
+  h = __builtin_bit_cast(bf16x8, hw);
+  l = __builtin_bit_cast(bf16x8, lw);
 }
 
 // two transposed LDS reads (4 rows x 16 columns of 16-bit each, rows 32 B apart in a [key][16] image): element e of
@@ -66,13 +120,12 @@ __device__ __forceinline__ bf16x8 lds_tr8(const char* p, int off2) {
 }
 
 // the 16 tap slots of one key as 8 packed dwords
-template <int PREC> __device__ __forceinline__ void tap_weights(float ys, float xs, u32x4& lo, u32x4& hi8) {
+__device__ __forceinline__ void tap_w16(float ys, float xs, float (&w)[TAP_SLOTS]) {
   float wy[TAP_R], wx[TAP_C];
 #pragma unroll
   for (int r = 0; r < TAP_R; ++r) wy[r] = hat((float)r - ys);
 #pragma unroll
   for (int c = 0; c < TAP_C; ++c) wx[c] = hat((float)c - xs);
-  float w[TAP_SLOTS];
 #pragma unroll
   for (int r = 0; r < TAP_R; ++r)
 #pragma unroll
@@ -81,10 +134,24 @@ template <int PREC> __device__ __forceinline__ void tap_weights(float ys, float 
   w[TAP_CLO] = 1.0f;
   w[TAP_DEAD] = ys < -50.0f ? 1.0f : 0.f;
   w[TAP_ONE] = 1.0f;
+}
+template <int PREC> __device__ __forceinline__ void tap_weights(float ys, float xs, u32x4& lo, u32x4& hi8) {
+  float w[TAP_SLOTS];
+  tap_w16(ys, xs, w);
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     lo[k] = Half<PREC>::pack2(w[2 * k], w[2 * k + 1]);
     hi8[k] = Half<PREC>::pack2(w[8 + 2 * k], w[8 + 2 * k + 1]);
+  }
+}
+// split mode: h0, h1 = slots 0..7, 8..15 of the hi image, l0, l1 of the lo image
+__device__ __forceinline__ void tap_weights_x3(float ys, float xs, u32x4& h0, u32x4& h1, u32x4& l0, u32x4& l1) {
+  float w[TAP_SLOTS];
+  tap_w16(ys, xs, w);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    TAP_SPLIT2(w[2 * k], w[2 * k + 1], h0[k], l0[k]);
+    TAP_SPLIT2(w[8 + 2 * k], w[8 + 2 * k + 1], h1[k], l1[k]);
   }
 }
 
@@ -92,6 +159,18 @@ template <int PREC> __device__ __forceinline__ void tap_weights(float ys, float 
 template <int PREC> __device__ __forceinline__ void tap_cells(float tcol, float trow, u32x4& c0, u32x4& c1) {
   c0 = __builtin_bit_cast(u32x4, cell_weights<PREC>(tcol, trow, 0).v);
   c1 = __builtin_bit_cast(u32x4, cell_weights<PREC>(tcol, trow, 1).v);
+}
+
+// split mode: cells 8 hf .. 8 hf + 7 (the 16-bit modes' order: element e = column 2 hf + (e >> 2), row e & 3)
+__device__ __forceinline__ void tap_cell_half_x3(float tcol, float trow, int hf, u32x4& h, u32x4& l) {
+  const float wx0 = hat((float)(2 * hf) - tcol), wx1 = hat((float)(2 * hf + 1) - tcol);
+  float wy[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) wy[r] = hat((float)r - trow);
+  TAP_SPLIT2(wx0 * wy[0], wx0 * wy[1], h[0], l[0]);
+  TAP_SPLIT2(wx0 * wy[2], wx0 * wy[3], h[1], l[1]);
+  TAP_SPLIT2(wx1 * wy[0], wx1 * wy[1], h[2], l[2]);
+  TAP_SPLIT2(wx1 * wy[2], wx1 * wy[3], h[3], l[3]);
 }
 
 // reductions inside a 32-lane half
@@ -135,15 +214,19 @@ __device__ __forceinline__ bool tap_drop_keep8(uint32_t hrow, uint32_t kh0, int 
 
 // ---------------------------------------------------------------------------------------------------------------
 // The key stream of the query-stationary tap kernels (forward, query-side backward): LDS layout and the producer wave.
-struct LdsT {
+// NP: images per operand (1; split mode 2: the lo images of taps and cells OFF_LO behind the hi images)
+template <int NP> struct LdsTn {
   static constexpr int OFF_TAPS = 0;            // [64 keys][16 slots] 16-bit
   static constexpr int OFF_CELLS = 2048;        // [64 keys][16 cells] 16-bit
-  static constexpr int OFF_CT = 4096;           // u32x4: flags (bit 0 / 1: tile 0 / 1 live, bit 2: done), alloc0, alloc1, 0
+  static constexpr int OFF_LO = 4096;
+  static constexpr int OFF_CT = 4096 * NP;      // u32x4: flags (bit 0 / 1: tile 0 / 1 live, bit 2: done), alloc0, alloc1, 0
                                                 //        (dropout build: the 4th dword = record index of tile 0's first key)
-  static constexpr int OFF_ORG = 4096 + 16;     // i32x4: chunk origin of tile 0 (x0, a0), of tile 1 (x0, a0)
-  static constexpr int BUF = 4096 + 32;
+  static constexpr int OFF_ORG = 4096 * NP + 16;   // i32x4: chunk origin of tile 0 (x0, a0), of tile 1 (x0, a0)
+  static constexpr int BUF = 4096 * NP + 32;
   static constexpr int RING = 4;
 };
+typedef LdsTn<1> LdsT;
+template <int PREC> using LdsTp = LdsTn<tap_x3(PREC) ? 2 : 1>;
 
 __device__ __forceinline__ bool box_fits(const StepBox& sb, float jrx) {
   const int x0 = (int)floorf(jrx + sb.bmin), x1 = (int)floorf(jrx + sb.bmax) + 1;
@@ -157,7 +240,8 @@ template <int PREC>
 __device__ __forceinline__ void tap_producer(const bevr_attn_desc& d, char* smem, char* ring, int img_bytes, int rows_img,
                                              const TapRec* __restrict__ recs, const StepBox* __restrict__ box,
                                              const char* __restrict__ tbl, float jrx, int lane) {
-  typedef LdsT L;
+  typedef LdsTp<PREC> L;
+  constexpr bool X3 = tap_x3(PREC);
   const int hi = lane >> 5;
   const int n_step = d.Np / KT;
   int alloc = 0, tag_x = 1 << 30, tag_a = 1 << 30;
@@ -166,7 +250,31 @@ __device__ __forceinline__ void tap_producer(const bevr_attn_desc& d, char* smem
   // its SIMD with row-block waves that would otherwise take most of the issue slots
   __builtin_amdgcn_s_setprio(3);
   // the table side of chunk origin (x0, a0): image[row][cell 4 c + r] = T2[x0 + c][a0 + row + r], 16-bit
+  // (split mode: img_bytes covers the hi rows and, rows_img * 32 behind them, the lo rows)
   auto build_image = [&](char* img, int x0, int a0) {
+    if constexpr (X3) {
+      for (int row = lane; row < rows_img; row += 64) {
+        const int yr0 = a0 + row + d.y_off;
+        const int e0 = max(0, min(yr0, d.Hp - 1)), e2 = max(0, min(yr0 + 2, d.Hp - 1));
+        u32x4 h0, h1, l0, l1;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const int xc = max(0, min(x0 + c + d.x_off, d.Wp - 1));
+          const char* col = tbl + (size_t)xc * d.Hp * 8;
+          const f32x2 p0 = *reinterpret_cast<const f32x2*>(col + (size_t)e0 * 8);
+          const f32x2 p2 = *reinterpret_cast<const f32x2*>(col + (size_t)e2 * 8);
+          uint32_t u0, u1, v0, v1;
+          TAP_SPLIT2(p0[0], p0[1], u0, v0);
+          TAP_SPLIT2(p2[0], p2[1], u1, v1);
+          if (c < 2) { h0[2 * c] = u0; h0[2 * c + 1] = u1; l0[2 * c] = v0; l0[2 * c + 1] = v1; }
+          else { h1[2 * (c - 2)] = u0; h1[2 * (c - 2) + 1] = u1; l1[2 * (c - 2)] = v0; l1[2 * (c - 2) + 1] = v1; }
+        }
+        *reinterpret_cast<u32x4*>(img + row * 32) = h0;
+        *reinterpret_cast<u32x4*>(img + row * 32 + 16) = h1;
+        *reinterpret_cast<u32x4*>(img + rows_img * 32 + row * 32) = l0;
+        *reinterpret_cast<u32x4*>(img + rows_img * 32 + row * 32 + 16) = l1;
+      }
+    } else
     for (int row = lane; row < rows_img; row += 64) {
       const int yr0 = a0 + row + d.y_off;
       const int e0 = max(0, min(yr0, d.Hp - 1)), e2 = max(0, min(yr0 + 2, d.Hp - 1));
@@ -177,7 +285,7 @@ __device__ __forceinline__ void tap_producer(const bevr_attn_desc& d, char* smem
         const char* col = tbl + (size_t)xc * d.Hp * 8;
         const f32x2 p0 = *reinterpret_cast<const f32x2*>(col + (size_t)e0 * 8);
         const f32x2 p2 = *reinterpret_cast<const f32x2*>(col + (size_t)e2 * 8);
-        const uint32_t u0 = Half<PREC>::pack2(p0[0], p0[1]), u1 = Half<PREC>::pack2(p2[0], p2[1]);
+        const uint32_t u0 = TapHalf<PREC>::pack2(p0[0], p0[1]), u1 = TapHalf<PREC>::pack2(p2[0], p2[1]);
         if (c < 2) { w0[2 * c] = u0; w0[2 * c + 1] = u1; }
         else { w1[2 * (c - 2)] = u0; w1[2 * (c - 2) + 1] = u1; }
       }
@@ -223,7 +331,20 @@ __device__ __forceinline__ void tap_producer(const bevr_attn_desc& d, char* smem
       const unsigned long long selm = __ballot(sel);
       const int ok0 = (selm & 0xffffffffull) != 0ull, ok1 = (selm >> 32) != 0ull;
       char* bb = smem + (e & 1) * L::BUF;
-      {
+      if constexpr (X3) {
+        u32x4 th[2], tl[2], ch[2], cl[2];
+        tap_weights_x3(sel ? rc.ys : TAP_YS_DEAD, rc.xs, th[0], th[1], tl[0], tl[1]);
+        const float tcol = sel ? (xf - (float)x0) + (tx - xf) : -8.0f;
+        tap_cell_half_x3(tcol, rc.a - (float)a0, 0, ch[0], cl[0]);
+        tap_cell_half_x3(tcol, rc.a - (float)a0, 1, ch[1], cl[1]);
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+          *reinterpret_cast<u32x4*>(bb + L::OFF_TAPS + lane * 32 + 16 * k) = th[k];
+          *reinterpret_cast<u32x4*>(bb + L::OFF_CELLS + lane * 32 + 16 * k) = ch[k];
+          *reinterpret_cast<u32x4*>(bb + L::OFF_LO + L::OFF_TAPS + lane * 32 + 16 * k) = tl[k];
+          *reinterpret_cast<u32x4*>(bb + L::OFF_LO + L::OFF_CELLS + lane * 32 + 16 * k) = cl[k];
+        }
+      } else {
         u32x4 t0, t1, c0, c1;
         tap_weights<PREC>(sel ? rc.ys : TAP_YS_DEAD, rc.xs, t0, t1);
         const float tcol = sel ? (xf - (float)x0) + (tx - xf) : -8.0f;

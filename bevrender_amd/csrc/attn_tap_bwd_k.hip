@@ -27,12 +27,18 @@ constexpr int NKW = 7;                 // key waves per workgroup (A/B on the be
 constexpr int NCW = 8;                 // table columns of the shared window (a chunk is 4 wide: origins may differ by 4 columns ...
 constexpr int NRX = 8;                 // ... and by 8 rows inside one workgroup)
 constexpr int SPB = 2;                 // 32-row slabs per step (= per barrier; one per barrier: 27.5 against 24.4 ms)
-struct LdsK {
+// NP: images per operand (1; split mode 2: the lo rows of G | H OFF_LO behind the hi rows)
+template <int NP> struct LdsKn {
   static constexpr int OFF_G = 0;      // [32 rows][16 slots] 16-bit
   static constexpr int OFF_H = 1024;
-  static constexpr int SLAB = 2048;    // one slab's G | H rows
+  static constexpr int OFF_LO = 2048;
+  static constexpr int SLAB = 2048 * NP;    // one slab's G | H rows
   static constexpr int BUF = SPB * SLAB;
 };
+typedef LdsKn<1> LdsK;
+template <int PREC> using LdsKp = LdsKn<tap_x3(PREC) ? 2 : 1>;
+// (split mode: every operand twice -- the registers of 2 waves per SIMD)
+constexpr int tap_bwd_k_waves(int prec) { return tap_x3(prec) ? 2 : 4; }
 // dwords per (kind, parity, column) of a window: rows 0 .. Sp + NRX + 7, two rows per dword
 __host__ __device__ __forceinline__ int win_dwords(int Sp) { return (Sp + NRX + 8) / 2; }
 
@@ -48,11 +54,13 @@ __device__ __forceinline__ bool tile_fits(const StepBox& sb, float jrx, int a0w,
 // workgroup without any leaves at once: every workgroup of a cell-sorted segment).  Two launches: with both bodies in one
 // loop the matrix path reloaded loop invariants from scratch on every slab.
 template <int PREC, bool SLOW>
-__global__ __launch_bounds__(64 * (NKW + 1), 4) void attn_tap_bwd_k_kernel(
+__global__ __launch_bounds__(64 * (NKW + 1), tap_bwd_k_waves(PREC)) void attn_tap_bwd_k_kernel(
     bevr_attn_desc d, const char* __restrict__ G, const char* __restrict__ H, const char* __restrict__ tap_ws,
     const float* __restrict__ table_t, float* __restrict__ dkey_a, float* __restrict__ dkey_b,
     float* __restrict__ dkey_y, float* __restrict__ dkey_x, int n_wg_ph TAP_DROP_PARAMS) {
-  typedef LdsK L;
+  typedef LdsKp<PREC> L;
+  constexpr bool X3 = tap_x3(PREC);
+  constexpr int NP = X3 ? 2 : 1;
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
   const int n_ph = d.n_prob * d.heads;
@@ -127,12 +135,12 @@ __global__ __launch_bounds__(64 * (NKW + 1), 4) void attn_tap_bwd_k_kernel(
     auto item_store = [&](int jn, int it, const float (&t)[5]) {
       if (it >= n_item || jn >= d.S) return;
       const int c = it / n_quad, m = it - c * n_quad;
-      const uint32_t h01 = Half<PREC>::pack2(t[0], t[1]), h23 = Half<PREC>::pack2(t[2], t[3]);
-      const uint32_t h12 = Half<PREC>::pack2(t[1], t[2]), h34 = Half<PREC>::pack2(t[3], t[4]);
-      const uint32_t l01 = Half<PREC>::pack2(t[0] - Half<PREC>::lo(h01), t[1] - Half<PREC>::hi(h01));
-      const uint32_t l23 = Half<PREC>::pack2(t[2] - Half<PREC>::lo(h23), t[3] - Half<PREC>::hi(h23));
-      const uint32_t l12 = Half<PREC>::pack2(t[1] - Half<PREC>::lo(h12), t[2] - Half<PREC>::hi(h12));
-      const uint32_t l34 = Half<PREC>::pack2(t[3] - Half<PREC>::lo(h34), t[4] - Half<PREC>::hi(h34));
+      const uint32_t h01 = TapHalf<PREC>::pack2(t[0], t[1]), h23 = TapHalf<PREC>::pack2(t[2], t[3]);
+      const uint32_t h12 = TapHalf<PREC>::pack2(t[1], t[2]), h34 = TapHalf<PREC>::pack2(t[3], t[4]);
+      const uint32_t l01 = TapHalf<PREC>::pack2(t[0] - TapHalf<PREC>::lo(h01), t[1] - TapHalf<PREC>::hi(h01));
+      const uint32_t l23 = TapHalf<PREC>::pack2(t[2] - TapHalf<PREC>::lo(h23), t[3] - TapHalf<PREC>::hi(h23));
+      const uint32_t l12 = TapHalf<PREC>::pack2(t[1] - TapHalf<PREC>::lo(h12), t[2] - TapHalf<PREC>::hi(h12));
+      const uint32_t l34 = TapHalf<PREC>::pack2(t[3] - TapHalf<PREC>::lo(h34), t[4] - TapHalf<PREC>::hi(h34));
       uint32_t* w = reinterpret_cast<uint32_t*>(win_base + (jn % 3) * win_bytes) + c * NRWD + 2 * m;
       const bool second = 2 * m + 1 < NRWD;
       w[0] = h01;
@@ -167,11 +175,19 @@ __global__ __launch_bounds__(64 * (NKW + 1), 4) void attn_tap_bwd_k_kernel(
     // slab `sl` (0 .. S nslab - 1, column-major) of the packed rows starts sl * 1024 bytes in; a step stages SPB slabs
     auto slab_index = [&](int j2, int st2, int u) { return min(j2 * nslab + min(SPB * st2 + u, nslab - 1), d.S * nslab - 1); };
     int e = 0;
-    u32x4 gv[SPB], hv[SPB];
+    u32x4 gv[SPB * NP], hv[SPB * NP];     // split mode: [SPB + u] the lo planes' rows
+    [[maybe_unused]] const size_t g_lo = (size_t)n_ph * Mp * 32;
 #pragma unroll
     for (int u = 0; u < SPB; ++u) {
       gv[u] = gload16(Gp + (size_t)slab_index(0, 0, u) * 1024);
       hv[u] = gload16(Hq + (size_t)slab_index(0, 0, u) * 1024);
+    }
+    if constexpr (X3) {
+#pragma unroll
+      for (int u = 0; u < SPB; ++u) {
+        gv[SPB * (NP - 1) + u] = gload16(Gp + g_lo + (size_t)slab_index(0, 0, u) * 1024);
+        hv[SPB * (NP - 1) + u] = gload16(Hq + g_lo + (size_t)slab_index(0, 0, u) * 1024);
+      }
     }
     for (int j = 0; j < d.S; ++j) {
       for (int st = 0; st < nstep; ++st, ++e) {
@@ -180,6 +196,13 @@ __global__ __launch_bounds__(64 * (NKW + 1), 4) void attn_tap_bwd_k_kernel(
         for (int u = 0; u < SPB; ++u) {
           *reinterpret_cast<u32x4*>(bb + u * L::SLAB + L::OFF_G + lane * 16) = gv[u];
           *reinterpret_cast<u32x4*>(bb + u * L::SLAB + L::OFF_H + lane * 16) = hv[u];
+        }
+        if constexpr (X3) {
+#pragma unroll
+          for (int u = 0; u < SPB; ++u) {
+            *reinterpret_cast<u32x4*>(bb + u * L::SLAB + L::OFF_LO + L::OFF_G + lane * 16) = gv[SPB * (NP - 1) + u];
+            *reinterpret_cast<u32x4*>(bb + u * L::SLAB + L::OFF_LO + L::OFF_H + lane * 16) = hv[SPB * (NP - 1) + u];
+          }
         }
         if constexpr (!SLOW) {
           item_store(j + 1, slice_item(st, 0), f0);
@@ -197,6 +220,13 @@ __global__ __launch_bounds__(64 * (NKW + 1), 4) void attn_tap_bwd_k_kernel(
         for (int u = 0; u < SPB; ++u) {
           gv[u] = gload16(Gp + (size_t)slab_index(jn, stn, u) * 1024);
           hv[u] = gload16(Hq + (size_t)slab_index(jn, stn, u) * 1024);
+        }
+        if constexpr (X3) {
+#pragma unroll
+          for (int u = 0; u < SPB; ++u) {
+            gv[SPB * (NP - 1) + u] = gload16(Gp + g_lo + (size_t)slab_index(jn, stn, u) * 1024);
+            hv[SPB * (NP - 1) + u] = gload16(Hq + g_lo + (size_t)slab_index(jn, stn, u) * 1024);
+          }
         }
         if constexpr (!SLOW) {
           const int jf = st + 1 < nstep ? j + 1 : j + 2;
@@ -218,7 +248,8 @@ __global__ __launch_bounds__(64 * (NKW + 1), 4) void attn_tap_bwd_k_kernel(
   const StepBox sb = box[tl];
   const int da = sb.amin - a0w;                       // rows between the window's origin and this tile's chunk origin
 
-  bf16x8 bk[2];        // B operand of S / dP for key sub-tile kb: lanes 0..31 the tap slots, lanes 32..63 the cells (per column)
+  bf16x8 bk[2 * NP];   // (split mode: [2 + kb] the lo parts)
+  //                      B operand of S / dP for key sub-tile kb: lanes 0..31 the tap slots, lanes 32..63 the cells (per column)
   // Z[slot 4 g + e][key] of the logit path (G^T dS) and of the value path (H^T P: H carries ln2, undone at the end),
   // Z[cell (c = g, r = e)][key]
   f32x4 zt[2], zv[2], zc[2];
@@ -227,9 +258,16 @@ __global__ __launch_bounds__(64 * (NKW + 1), 4) void attn_tap_bwd_k_kernel(
   for (int kb = 0; kb < 2; ++kb) {
     const TapRec r0 = recs[(size_t)tl * 32 + 16 * kb + li];
     if (g == 0) stash[16 * kb + li] = r0;
-    u32x4 t0, t1;
-    tap_weights<PREC>(r0.ys, r0.xs, t0, t1);
-    bk[kb] = __builtin_bit_cast(bf16x8, g == 0 ? t0 : t1);
+    if constexpr (X3) {
+      u32x4 th0, th1, tl0, tl1;
+      tap_weights_x3(r0.ys, r0.xs, th0, th1, tl0, tl1);
+      bk[kb] = __builtin_bit_cast(bf16x8, g == 0 ? th0 : th1);
+      bk[2 * (NP - 1) + kb] = __builtin_bit_cast(bf16x8, g == 0 ? tl0 : tl1);
+    } else {
+      u32x4 t0, t1;
+      tap_weights<PREC>(r0.ys, r0.xs, t0, t1);
+      bk[kb] = __builtin_bit_cast(bf16x8, g == 0 ? t0 : t1);
+    }
     zt[kb] = f32x4{0.f, 0.f, 0.f, 0.f};
     zv[kb] = f32x4{0.f, 0.f, 0.f, 0.f};
     zc[kb] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -300,7 +338,7 @@ __global__ __launch_bounds__(64 * (NKW + 1), 4) void attn_tap_bwd_k_kernel(
 #pragma unroll
     for (int r = 0; r < 8; ++r) {
       const uint32_t c2 = *reinterpret_cast<const uint32_t*>(base + L::OFF_H + (16 * (r >> 2) + 4 * g + (r & 3)) * 32 + TAP_CHI * 2);
-      ndel[r] = Half<PREC>::lo(c2) + Half<PREC>::hi(c2);
+      ndel[r] = TapHalf<PREC>::lo(c2) + TapHalf<PREC>::hi(c2);
     }
 #endif
 #pragma unroll
@@ -364,8 +402,8 @@ __global__ __launch_bounds__(64 * (NKW + 1), 4) void attn_tap_bwd_k_kernel(
       u32x4 dsw, pw;
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        dsw[k] = Half<PREC>::pack2(ds[2 * k], ds[2 * k + 1]);
-        pw[k] = Half<PREC>::pack2(p[2 * k], p[2 * k + 1]);
+        dsw[k] = TapHalf<PREC>::pack2(ds[2 * k], ds[2 * k + 1]);
+        pw[k] = TapHalf<PREC>::pack2(p[2 * k], p[2 * k + 1]);
       }
       const bf16x8 ds8 = __builtin_bit_cast(bf16x8, dsw), p8 = __builtin_bit_cast(bf16x8, pw);
       zt[kb] = mfma16<PREC>(gt, ds8, zt[kb]);
@@ -374,6 +412,91 @@ __global__ __launch_bounds__(64 * (NKW + 1), 4) void attn_tap_bwd_k_kernel(
         zc[kb] = mfma16<PREC>(tlo, ds8, zc[kb]);
         zc[kb] = mfma16<PREC>(thi, ds8, zc[kb]);
       }
+    }
+  };
+
+  // split mode: the same with every operand as (hi, lo); P and dS are split after the exponential
+  [[maybe_unused]] auto slab3 = [&](auto fit_tag, const char* base, int i0) {
+    constexpr bool FIT = decltype(fit_tag)::value;
+    bf16x8 qa[2][2], ha[2][2], gt[2], ht[2];     // [.][plane]
+#pragma unroll
+    for (int pl = 0; pl < 2; ++pl) {
+#pragma unroll
+      for (int rb = 0; rb < 2; ++rb) {
+        u32x4 v = {0u, 0u, 0u, 0u}, hv = {0u, 0u, 0u, 0u};
+        if (g < 2) {
+          v = *reinterpret_cast<const u32x4*>(base + pl * L::OFF_LO + a_row + rb * 512);
+          hv = *reinterpret_cast<const u32x4*>(base + pl * L::OFF_LO + L::OFF_H - L::OFF_G + a_row + rb * 512);
+        } else if (FIT) {
+          const int kind = pl * 2 * NCW * NRWD * 4;      // the window's lo parts
+          const uint32_t* w0 = reinterpret_cast<const uint32_t*>(win_b + kind + wq0 + 2 * i0) + 8 * rb;
+          const uint32_t* w1 = reinterpret_cast<const uint32_t*>(win_b + kind + wq1 + 2 * i0) + 8 * rb;
+          v[0] = w0[0]; v[1] = w0[1];
+          v[2] = w1[0]; v[3] = w1[1];
+        }
+        qa[rb][pl] = __builtin_bit_cast(bf16x8, v);
+        ha[rb][pl] = __builtin_bit_cast(bf16x8, hv);
+      }
+      gt[pl] = lds_tr8(base + pl * L::OFF_LO + L::OFF_G + t_off, 512);
+      ht[pl] = lds_tr8(base + pl * L::OFF_LO + L::OFF_H + t_off, 512);
+    }
+    bf16x8 thi = gt[0], tlo = gt[0];
+    if constexpr (FIT) {
+      const uint32_t* w0 = reinterpret_cast<const uint32_t*>(win_b + wth + 2 * i0);
+      const uint32_t* w1 = reinterpret_cast<const uint32_t*>(win_b + wtl + 2 * i0);
+      u32x4 a, b;
+      a[0] = w0[0]; a[1] = w0[1]; a[2] = w0[8]; a[3] = w0[9];
+      b[0] = w1[0]; b[1] = w1[1]; b[2] = w1[8]; b[3] = w1[9];
+      thi = __builtin_bit_cast(bf16x8, a);
+      tlo = __builtin_bit_cast(bf16x8, b);
+    }
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb) {
+      const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
+      const bf16x8 kh = bk[kb], kl = bk[2 * (NP - 1) + kb];
+      const f32x4 s0 = mfma16s4(qa[0][0], qa[0][1], kh, kl, z4);
+      const f32x4 s1 = mfma16s4(qa[1][0], qa[1][1], kh, kl, z4);
+      const f32x4 q0 = mfma16s(ha[0][0], ha[0][1], kh, kl, z4);
+      const f32x4 q1 = mfma16s(ha[1][0], ha[1][1], kh, kl, z4);
+      float p[8], ds[8];
+      if constexpr (!FIT) {
+        const TapRec rk = stash[16 * kb + li];
+        const float a = rk.a, tx = jrx + rk.b;
+        const float af = floorf(a), xf = floorf(tx);
+        const float fy = a - af, fx = tx - xf;
+        const bool dead = rk.ys < -50.0f;
+        const int xc = max(0, min((int)xf + d.x_off, d.Wp - 2));
+        const int yb = (int)af + d.y_off + i0 + 4 * g;
+        float pa = 0.f, pb = 0.f;
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+          const int y = max(0, min(yb + (r & 3) + 16 * (r >> 2), HpT - 2));
+          const float* c0p = tbl + (size_t)xc * HpT + y;
+          const float t00 = c0p[0], t01 = c0p[1], t10 = c0p[HpT], t11 = c0p[HpT + 1];
+          const float u0 = t00 + fy * (t01 - t00), u1 = t10 + fy * (t11 - t10);
+          const float sv = (r < 4 ? s0[r & 3] : s1[r & 3]) + (dead ? 0.f : u0 + fx * (u1 - u0));
+          p[r] = fast_exp2(sv);
+          ds[r] = p[r] * (r < 4 ? q0[r & 3] : q1[r & 3]);
+          pa += ds[r] * ((1.0f - fx) * (t01 - t00) + fx * (t11 - t10));
+          pb += ds[r] * (u1 - u0);
+        }
+        acc_a[kb] += dead ? 0.f : pa;
+        acc_b[kb] += dead ? 0.f : pb;
+      } else {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          p[r] = fast_exp2(s0[r]);
+          ds[r] = p[r] * q0[r];
+          p[4 + r] = fast_exp2(s1[r]);
+          ds[4 + r] = p[4 + r] * q1[r];
+        }
+      }
+      bf16x8 dh, dl, ph, pl;
+      split8v(ds, dh, dl);
+      split8v(p, ph, pl);
+      zt[kb] = mfma16s(gt[0], gt[1], dh, dl, zt[kb]);
+      zv[kb] = mfma16s(ht[0], ht[1], ph, pl, zv[kb]);
+      if constexpr (FIT) zc[kb] = mfma16s(thi, tlo, dh, dl, zc[kb]);
     }
   };
 
@@ -398,6 +521,15 @@ __global__ __launch_bounds__(64 * (NKW + 1), 4) void attn_tap_bwd_k_kernel(
     for (int kb = 0; kb < 2; ++kb) {
       if (g >= 2) {
         u32x4 cw = {0u, 0u, 0u, 0u};
+        if constexpr (X3) {
+          u32x4 cl = {0u, 0u, 0u, 0u};
+          if (!SLOW && mine) {
+            float tcol, trow;
+            chunk_coords(kb, tcol, trow);
+            tap_cell_half_x3(tcol, trow, g - 2, cw, cl);
+          }
+          bk[2 * (NP - 1) + kb] = __builtin_bit_cast(bf16x8, cl);
+        } else
         if (!SLOW && mine) {
           float tcol, trow;
           chunk_coords(kb, tcol, trow);
@@ -421,8 +553,10 @@ __global__ __launch_bounds__(64 * (NKW + 1), 4) void attn_tap_bwd_k_kernel(
       if (!mine) continue;
 #pragma unroll
       for (int u = 0; u < SPB; ++u)
-        if (SPB * st + u < nslab)
-          slab(std::integral_constant<bool, !SLOW>{}, smem + (e & 1) * L::BUF + u * L::SLAB, 32 * (SPB * st + u));
+        if (SPB * st + u < nslab) {
+          if constexpr (X3) slab3(std::integral_constant<bool, !SLOW>{}, smem + (e & 1) * L::BUF + u * L::SLAB, 32 * (SPB * st + u));
+          else slab(std::integral_constant<bool, !SLOW>{}, smem + (e & 1) * L::BUF + u * L::SLAB, 32 * (SPB * st + u));
+        }
     }
     // ---- the column's bias-position gradients out of Z: this lane holds chunk column c = g, rows 0..3 of its key ----
     if (!SLOW && mine) {
@@ -480,7 +614,7 @@ __global__ __launch_bounds__(64 * (NKW + 1), 4) void attn_tap_bwd_k_kernel(
 template <int PREC>
 int launch(const bevr_attn_desc& d, const void* G, const void* H, const void* tap_ws, const float* table_t, float* dkey_a,
            float* dkey_b, float* dkey_y, float* dkey_x, hipStream_t st TAP_DROP_PARAMS) {
-  typedef LdsK L;
+  typedef LdsKp<PREC> L;
   const int n_ph = d.n_prob * d.heads;
   const int n_tiles = d.Np / 32;
   const int n_wg_ph = (n_tiles + NKW - 1) / NKW;
@@ -499,6 +633,17 @@ int launch(const bevr_attn_desc& d, const void* G, const void* H, const void* ta
 
 }  // namespace
 
+#if BEVR_TAP_X3
+// the split-mode instantiations: this translation unit is attn_tap_bwd_k_x3.hip, entered from bevr_attn_tap_bwd_k
+int bevr_tap_bwd_k_x3(const bevr_attn_desc& d, const void* G, const void* H, const void* tap_ws, const float* table_t,
+                      float* dkey_a, float* dkey_b, float* dkey_y, float* dkey_x, hipStream_t st) {
+  return launch<BEVR_PREC_BF16X3>(d, G, H, tap_ws, table_t, dkey_a, dkey_b, dkey_y, dkey_x, st);
+}
+#else
+#if !BEVR_DROP
+int bevr_tap_bwd_k_x3(const bevr_attn_desc& d, const void* G, const void* H, const void* tap_ws, const float* table_t,
+                      float* dkey_a, float* dkey_b, float* dkey_y, float* dkey_x, hipStream_t st);     // attn_tap_bwd_k_x3.hip
+#endif
 #if BEVR_DROP
 extern "C" int bevr_attn_tap_bwd_k_dropout(const bevr_attn_desc* d, const void* G, const void* H, const void* tap_ws,
                                            const float* table_t, float* dkey_a, float* dkey_b, float* dkey_y,
@@ -518,5 +663,9 @@ extern "C" int bevr_attn_tap_bwd_k(const bevr_attn_desc* d, const void* G, const
   hipStream_t st = (hipStream_t)stream;
   if (d->precision == BEVR_PREC_BF16) return launch<BEVR_PREC_BF16>(*d, G, H, tap_ws, table_t, dkey_a, dkey_b, dkey_y, dkey_x, st TAP_DROP_ARGS);
   if (d->precision == BEVR_PREC_F16) return launch<BEVR_PREC_F16>(*d, G, H, tap_ws, table_t, dkey_a, dkey_b, dkey_y, dkey_x, st TAP_DROP_ARGS);
+#if !BEVR_DROP
+  if (d->precision == BEVR_PREC_BF16X3) return bevr_tap_bwd_k_x3(*d, G, H, tap_ws, table_t, dkey_a, dkey_b, dkey_y, dkey_x, st);
+#endif
   return BEVR_E_PRECISION;
 }
+#endif  // BEVR_TAP_X3

@@ -15,11 +15,15 @@
 
 namespace {
 
+// (split mode: every operand twice -- the fat NB = 4 instantiation gets the registers of 2 waves per SIMD)
+constexpr int tap_bwd_q_waves(int prec, int nb) { return tap_x3(prec) && nb == 4 ? 2 : 4; }
 template <int PREC, int NB>
-__global__ __launch_bounds__(512, 4) void attn_tap_bwd_q_kernel(
+__global__ __launch_bounds__(512, tap_bwd_q_waves(PREC, NB)) void attn_tap_bwd_q_kernel(
     bevr_attn_desc d, const char* __restrict__ G, const char* __restrict__ H, const char* __restrict__ tap_ws, const char* __restrict__ table_pair,
     float* __restrict__ dG, float* __restrict__ dtable TAP_DROP_PARAMS) {
-  typedef LdsT L;
+  typedef LdsTp<PREC> L;
+  constexpr bool X3 = tap_x3(PREC);
+  constexpr int NP = X3 ? 2 : 1;
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
   const int n_ph = d.n_prob * d.heads;
@@ -34,7 +38,7 @@ __global__ __launch_bounds__(512, 4) void attn_tap_bwd_q_kernel(
   const int Mp = d.S * d.Sp;
   const int nblk = (d.S + QB - 1) / QB;
   const int rows_img = nblk * QB;
-  const int img_bytes = rows_img * 32;
+  const int img_bytes = rows_img * 32 * NP;
   char* ring = smem + 2 * L::BUF;
   const char* tbl = table_pair + (size_t)hd * d.Wp * d.Hp * 8;
   const float rx = (float)(d.Wt - 1) / (2.0f * (float)(d.S - 1));
@@ -48,8 +52,8 @@ __global__ __launch_bounds__(512, 4) void attn_tap_bwd_q_kernel(
   }
 
   const int blk0 = wave * NB;
-  bf16x8 bop[NB];     // lanes 0..31 G[q][8 kg ..], lanes 32..63 the chunk's table side
-  bf16x8 hop[NB];     // lanes 0..31 H[q][8 kg ..], lanes 32..63 zero
+  bf16x8 bop[NB * NP];     // lanes 0..31 G[q][8 kg ..], lanes 32..63 the chunk's table side (split mode: [NB + nb] the lo parts)
+  bf16x8 hop[NB * NP];     // lanes 0..31 H[q][8 kg ..], lanes 32..63 zero
   f32x4 ytap[NB], ycell[NB];
   size_t mqv[NB];
 #pragma unroll
@@ -66,6 +70,19 @@ __global__ __launch_bounds__(512, 4) void attn_tap_bwd_q_kernel(
     hop[nb] = __builtin_bit_cast(bf16x8, hh);
     ytap[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
     ycell[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  if constexpr (X3) {   // the lo planes of G and H
+    const size_t g_lo = (size_t)n_ph * Mp * TAP_SLOTS * 2;
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb) {
+      u32x4 g = {0u, 0u, 0u, 0u}, hh = {0u, 0u, 0u, 0u};
+      if (kg < 2) {
+        g = *reinterpret_cast<const u32x4*>(G + g_lo + (mqv[nb] * TAP_SLOTS + 8 * kg) * 2);
+        hh = *reinterpret_cast<const u32x4*>(H + g_lo + (mqv[nb] * TAP_SLOTS + 8 * kg) * 2);
+      }
+      bop[NB * (NP - 1) + nb] = __builtin_bit_cast(bf16x8, g);
+      hop[NB * (NP - 1) + nb] = __builtin_bit_cast(bf16x8, hh);
+    }
   }
 #if BEVR_DROP
   // dropout: dS = P (keep ? D dP : 0 - delta).  The MFMA gives x = D dP - delta (D dP = w . H + H[TAP_ONE], -delta in slots
@@ -120,7 +137,7 @@ __global__ __launch_bounds__(512, 4) void attn_tap_bwd_q_kernel(
 #if BEVR_DROP
   auto tile = [&](const char* base, int t, uint32_t kh) {
 #else
-  auto tile = [&](const char* base, int t) {
+  [[maybe_unused]] auto tile = [&](const char* base, int t) {
 #endif
     const bf16x8 a0 = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(base + a_off + t * 1024));
     const bf16x8 a1 = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(base + a_off + t * 1024 + 512));
@@ -143,16 +160,48 @@ __global__ __launch_bounds__(512, 4) void attn_tap_bwd_q_kernel(
         ds[4 + k] = fast_exp2(s1[k]) * (tap_drop_keep8(hrow[nb], kh, 4 + k, drop_thr) ? p1[k] : ndel[nb]);
       }
 #pragma unroll
-      for (int k = 0; k < 4; ++k) dsw[k] = Half<PREC>::pack2(ds[2 * k], ds[2 * k + 1]);
+      for (int k = 0; k < 4; ++k) dsw[k] = TapHalf<PREC>::pack2(ds[2 * k], ds[2 * k + 1]);
 #else
-      dsw[0] = Half<PREC>::pack2(fast_exp2(s0[0]) * p0[0], fast_exp2(s0[1]) * p0[1]);
-      dsw[1] = Half<PREC>::pack2(fast_exp2(s0[2]) * p0[2], fast_exp2(s0[3]) * p0[3]);
-      dsw[2] = Half<PREC>::pack2(fast_exp2(s1[0]) * p1[0], fast_exp2(s1[1]) * p1[1]);
-      dsw[3] = Half<PREC>::pack2(fast_exp2(s1[2]) * p1[2], fast_exp2(s1[3]) * p1[3]);
+      dsw[0] = TapHalf<PREC>::pack2(fast_exp2(s0[0]) * p0[0], fast_exp2(s0[1]) * p0[1]);
+      dsw[1] = TapHalf<PREC>::pack2(fast_exp2(s0[2]) * p0[2], fast_exp2(s0[3]) * p0[3]);
+      dsw[2] = TapHalf<PREC>::pack2(fast_exp2(s1[0]) * p1[0], fast_exp2(s1[1]) * p1[1]);
+      dsw[3] = TapHalf<PREC>::pack2(fast_exp2(s1[2]) * p1[2], fast_exp2(s1[3]) * p1[3]);
 #endif
       const bf16x8 ds8 = __builtin_bit_cast(bf16x8, dsw);
       ytap[nb] = mfma16<PREC>(wt, ds8, ytap[nb]);
       ycell[nb] = mfma16<PREC>(wct, ds8, ycell[nb]);
+    }
+  };
+
+  // split mode: the same with every operand as (hi, lo); dS is split after the product
+  [[maybe_unused]] auto tile3 = [&](const char* base, int t) {
+    bf16x8 a0[2], a1[2], wt[2], wct[2];
+#pragma unroll
+    for (int pl = 0; pl < 2; ++pl) {
+      a0[pl] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(base + pl * L::OFF_LO + a_off + t * 1024));
+      a1[pl] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(base + pl * L::OFF_LO + a_off + t * 1024 + 512));
+      wt[pl] = lds_tr8(base + pl * L::OFF_LO + L::OFF_TAPS + t_off + t * 1024, 512);
+      wct[pl] = lds_tr8(base + pl * L::OFF_LO + L::OFF_CELLS + t_off + t * 1024, 512);
+    }
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb) {
+      if (NB > 1 && blk0 + nb >= nblk) continue;
+      const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
+      const bf16x8 bh = bop[nb], bl = bop[NB * (NP - 1) + nb], hh = hop[nb], hl = hop[NB * (NP - 1) + nb];
+      const f32x4 s0 = mfma16s4(a0[0], a0[1], bh, bl, z4);
+      const f32x4 s1 = mfma16s4(a1[0], a1[1], bh, bl, z4);
+      const f32x4 p0 = mfma16s(a0[0], a0[1], hh, hl, z4);
+      const f32x4 p1 = mfma16s(a1[0], a1[1], hh, hl, z4);
+      float ds[8];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        ds[k] = fast_exp2(s0[k]) * p0[k];
+        ds[4 + k] = fast_exp2(s1[k]) * p1[k];
+      }
+      bf16x8 dh, dl;
+      split8v(ds, dh, dl);
+      ytap[nb] = mfma16s(wt[0], wt[1], dh, dl, ytap[nb]);
+      ycell[nb] = mfma16s(wct[0], wct[1], dh, dl, ycell[nb]);
     }
   };
 
@@ -176,12 +225,18 @@ __global__ __launch_bounds__(512, 4) void attn_tap_bwd_q_kernel(
 #pragma unroll
           for (int nb = 0; nb < NB; ++nb)
             bop[nb] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(img + min(blk0 + nb, nblk - 1) * 512));
+          if constexpr (X3) {
+#pragma unroll
+            for (int nb = 0; nb < NB; ++nb)
+              bop[NB * (NP - 1) + nb] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(img + rows_img * 32 + min(blk0 + nb, nblk - 1) * 512));
+          }
         }
       }
 #if BEVR_DROP
       tile(base, t, tap_drop_key0(key0 + (uint32_t)__builtin_amdgcn_readfirstlane((int)ct[3]) + 32u * t, kg));
 #else
-      tile(base, t);
+      if constexpr (X3) tile3(base, t);
+      else tile(base, t);
 #endif
     }
   }
@@ -197,11 +252,11 @@ __global__ __launch_bounds__(512, 4) void attn_tap_bwd_q_kernel(
 template <int PREC>
 int launch(const bevr_attn_desc& d, const void* G, const void* H, const void* tap_ws,
            const float* table_pair, float* dG, float* dtable, hipStream_t st TAP_DROP_PARAMS) {
-  typedef LdsT L;
+  typedef LdsTp<PREC> L;
   const int n_ph = d.n_prob * d.heads;
   const int grid = ((n_ph + 7) / 8) * 8 * d.S;
   const int nblk = (d.S + QB - 1) / QB;
-  const size_t lds = 2 * L::BUF + (size_t)L::RING * nblk * QB * 32;
+  const size_t lds = 2 * L::BUF + (size_t)L::RING * nblk * QB * 32 * (tap_x3(PREC) ? 2 : 1);
   if (lds > 160 * 1024 || nblk > 28) return BEVR_E_SHAPE;
   const int nb = nblk <= 7 ? 1 : nblk <= 14 ? 2 : 4;
   const int n_cw = (nblk + nb - 1) / nb;
@@ -218,6 +273,17 @@ int launch(const bevr_attn_desc& d, const void* G, const void* H, const void* ta
 
 }  // namespace
 
+#if BEVR_TAP_X3
+// the split-mode instantiations: this translation unit is attn_tap_bwd_q_x3.hip, entered from bevr_attn_tap_bwd_q
+int bevr_tap_bwd_q_x3(const bevr_attn_desc& d, const void* G, const void* H, const void* tap_ws, const float* table_pair,
+                      float* dG, float* dtable, hipStream_t st) {
+  return launch<BEVR_PREC_BF16X3>(d, G, H, tap_ws, table_pair, dG, dtable, st);
+}
+#else
+#if !BEVR_DROP
+int bevr_tap_bwd_q_x3(const bevr_attn_desc& d, const void* G, const void* H, const void* tap_ws, const float* table_pair,
+                      float* dG, float* dtable, hipStream_t st);     // attn_tap_bwd_q_x3.hip
+#endif
 #if BEVR_DROP
 extern "C" int bevr_attn_tap_bwd_q_dropout(const bevr_attn_desc* d, const void* G, const void* H, const void* tap_ws,
                                            const float* table_pair, float* dG, float* dtable, unsigned key0,
@@ -236,5 +302,9 @@ extern "C" int bevr_attn_tap_bwd_q(const bevr_attn_desc* d, const void* G, const
   hipStream_t st = (hipStream_t)stream;
   if (d->precision == BEVR_PREC_BF16) return launch<BEVR_PREC_BF16>(*d, G, H, tap_ws, table_pair, dG, dtable, st TAP_DROP_ARGS);
   if (d->precision == BEVR_PREC_F16) return launch<BEVR_PREC_F16>(*d, G, H, tap_ws, table_pair, dG, dtable, st TAP_DROP_ARGS);
+#if !BEVR_DROP
+  if (d->precision == BEVR_PREC_BF16X3) return bevr_tap_bwd_q_x3(*d, G, H, tap_ws, table_pair, dG, dtable, st);
+#endif
   return BEVR_E_PRECISION;
 }
+#endif  // BEVR_TAP_X3

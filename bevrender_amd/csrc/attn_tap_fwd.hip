@@ -31,15 +31,19 @@ namespace {
 #else
 #define TAP_FWD_WAVES(NB_) ((NB_) == 4 ? 4 : 6)
 #endif
+// (split mode: every operand twice -- 4 waves per SIMD, the fat NB = 4 instantiation 2)
+constexpr int tap_fwd_waves(int prec, int nb) { return tap_x3(prec) ? (nb == 4 ? 2 : 4) : TAP_FWD_WAVES(nb); }
 template <int PREC, int NB, bool EXACT>
-__global__ __launch_bounds__(512, TAP_FWD_WAVES(NB)) void attn_tap_fwd_kernel(
+__global__ __launch_bounds__(512, tap_fwd_waves(PREC, NB)) void attn_tap_fwd_kernel(
     bevr_attn_desc d, const char* __restrict__ G, const char* __restrict__ tap_ws,
     const char* __restrict__ table_pair, float* __restrict__ mref, float* __restrict__ R, int* __restrict__ flags
 #if BEVR_DROP
     , float* __restrict__ lsum TAP_DROP_PARAMS
 #endif
     ) {
-  typedef LdsT L;
+  typedef LdsTp<PREC> L;
+  constexpr bool X3 = tap_x3(PREC);
+  constexpr int NP = X3 ? 2 : 1;
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
   const int n_ph = d.n_prob * d.heads;
@@ -57,7 +61,7 @@ __global__ __launch_bounds__(512, TAP_FWD_WAVES(NB)) void attn_tap_fwd_kernel(
   const int Mp = d.S * d.Sp;
   const int nblk = (d.S + QB - 1) / QB;
   const int rows_img = nblk * QB;
-  const int img_bytes = rows_img * 32;
+  const int img_bytes = rows_img * 32 * NP;
   char* ring = smem + 2 * L::BUF;
   const char* tbl = table_pair + (size_t)hd * d.Wp * d.Hp * 8;
   const float rx = (float)(d.Wt - 1) / (2.0f * (float)(d.S - 1));
@@ -72,7 +76,9 @@ __global__ __launch_bounds__(512, TAP_FWD_WAVES(NB)) void attn_tap_fwd_kernel(
 
   // ---- row-block waves ------------------------------------------------------------------------------------
   const int blk0 = wave * NB;
-  bf16x8 bop[NB];     // B operand: lanes 0..31 G[q][8 kg ..] (constant), lanes 32..63 the chunk's table side (per origin)
+  // B operand: lanes 0..31 G[q][8 kg ..] (constant), lanes 32..63 the chunk's table side (per origin); split mode: [NB + nb]
+  // the lo parts
+  bf16x8 bop[NB * NP];
   f32x4 r[NB];        // R[slot 4 kg + e][q]
   float sh[NB];       // EXACT: the running maximum relative to mref
   size_t mqv[NB];
@@ -86,6 +92,15 @@ __global__ __launch_bounds__(512, TAP_FWD_WAVES(NB)) void attn_tap_fwd_kernel(
     bop[nb] = __builtin_bit_cast(bf16x8, g);
     r[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
     sh[nb] = -3.0e38f;
+  }
+  if constexpr (X3) {   // G's lo plane
+    const size_t g_lo = (size_t)n_ph * Mp * TAP_SLOTS * 2;
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb) {
+      u32x4 gl = {0u, 0u, 0u, 0u};
+      if (kg < 2) gl = *reinterpret_cast<const u32x4*>(G + g_lo + (mqv[nb] * TAP_SLOTS + 8 * kg) * 2);
+      bop[NB * (NP - 1) + nb] = __builtin_bit_cast(bf16x8, gl);
+    }
   }
 #if BEVR_DROP
   uint32_t hrow[NB];  // the row part of the keep hash, out of the key loop
@@ -101,16 +116,16 @@ __global__ __launch_bounds__(512, TAP_FWD_WAVES(NB)) void attn_tap_fwd_kernel(
   const int t_off = L::OFF_TAPS + (4 * kg + (li >> 2)) * 32 + (lane & 3) * 8;             // + tile * 1024, second block + 512
   const int i_off = li * 32 + (kg & 1) * 16;                                             // in a table image, + block * 512
   // the B operand exists once per tile slot of an emission (their chunk origins may differ); lanes 0..31 of both hold G
-  bf16x8 bop1[NB];
+  bf16x8 bop1[NB * NP];
 #pragma unroll
-  for (int nb = 0; nb < NB; ++nb) bop1[nb] = bop[nb];
+  for (int nb = 0; nb < NB * NP; ++nb) bop1[nb] = bop[nb];
   int have0 = 0, have1 = 0;      // allocation numbers of the table images in bop / bop1 (0: the zeroed image)
 
   // one 32-key tile against one row block: S^T (two 16-key sub-tiles) -> weights -> R += w^T P
 #if BEVR_DROP
   auto tile = [&](const bf16x8& a0, const bf16x8& a1, const bf16x8& wt, const bf16x8& b, int nb, uint32_t kh) {
 #else
-  auto tile = [&](const bf16x8& a0, const bf16x8& a1, const bf16x8& wt, const bf16x8& b, int nb) {
+  [[maybe_unused]] auto tile = [&](const bf16x8& a0, const bf16x8& a1, const bf16x8& wt, const bf16x8& b, int nb) {
 #endif
     const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
     f32x4 s0 = mfma16<PREC>(a0, b, z4);
@@ -146,14 +161,41 @@ __global__ __launch_bounds__(512, TAP_FWD_WAVES(NB)) void attn_tap_fwd_kernel(
       asm("" : "+v"(p[k]));
     }
 #pragma unroll
-    for (int k = 0; k < 4; ++k) pw[k] = Half<PREC>::pack2(p[2 * k], p[2 * k + 1]);
+    for (int k = 0; k < 4; ++k) pw[k] = TapHalf<PREC>::pack2(p[2 * k], p[2 * k + 1]);
 #else
-    pw[0] = Half<PREC>::pack2(fast_exp2(s0[0]), fast_exp2(s0[1]));
-    pw[1] = Half<PREC>::pack2(fast_exp2(s0[2]), fast_exp2(s0[3]));
-    pw[2] = Half<PREC>::pack2(fast_exp2(s1[0]), fast_exp2(s1[1]));
-    pw[3] = Half<PREC>::pack2(fast_exp2(s1[2]), fast_exp2(s1[3]));
+    pw[0] = TapHalf<PREC>::pack2(fast_exp2(s0[0]), fast_exp2(s0[1]));
+    pw[1] = TapHalf<PREC>::pack2(fast_exp2(s0[2]), fast_exp2(s0[3]));
+    pw[2] = TapHalf<PREC>::pack2(fast_exp2(s1[0]), fast_exp2(s1[1]));
+    pw[3] = TapHalf<PREC>::pack2(fast_exp2(s1[2]), fast_exp2(s1[3]));
 #endif
     r[nb] = mfma16<PREC>(wt, __builtin_bit_cast(bf16x8, pw), r[nb]);
+  };
+
+  // split mode: the same with every operand as (hi, lo)
+  [[maybe_unused]] auto tile3 = [&](const bf16x8 (&a0)[2], const bf16x8 (&a1)[2], const bf16x8 (&wt)[2], const bf16x8& bh,
+                                    const bf16x8& bl, int nb) {
+    const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
+    f32x4 s0 = mfma16s4(a0[0], a0[1], bh, bl, z4);
+    f32x4 s1 = mfma16s4(a1[0], a1[1], bh, bl, z4);
+    if constexpr (EXACT) {
+      float tm = fmaxf(fmaxf(fmaxf(s0[0], s0[1]), fmaxf(s0[2], s0[3])), fmaxf(fmaxf(s1[0], s1[1]), fmaxf(s1[2], s1[3])));
+      tm = fmaxf(tm, __shfl_xor(tm, 16));
+      tm = fmaxf(tm, __shfl_xor(tm, 32));
+      const float mn = fmaxf(sh[nb], tm);
+      r[nb] *= fast_exp2(sh[nb] - mn);
+      sh[nb] = mn;
+      s0 -= mn;
+      s1 -= mn;
+    }
+    float p[8];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      p[k] = fast_exp2(s0[k]);
+      p[4 + k] = fast_exp2(s1[k]);
+    }
+    bf16x8 ph8, pl8;
+    split8v(p, ph8, pl8);
+    r[nb] = mfma16s(wt[0], wt[1], ph8, pl8, r[nb]);
   };
 
   for (int e = 0;; ++e) {
@@ -170,6 +212,11 @@ __global__ __launch_bounds__(512, TAP_FWD_WAVES(NB)) void attn_tap_fwd_kernel(
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb)
           bop[nb] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(img + min(blk0 + nb, nblk - 1) * 512));
+        if constexpr (X3) {
+#pragma unroll
+          for (int nb = 0; nb < NB; ++nb)
+            bop[NB + nb] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(img + rows_img * 32 + min(blk0 + nb, nblk - 1) * 512));
+        }
       }
     }
     if (al1 != have1) {
@@ -179,9 +226,32 @@ __global__ __launch_bounds__(512, TAP_FWD_WAVES(NB)) void attn_tap_fwd_kernel(
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb)
           bop1[nb] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(img + min(blk0 + nb, nblk - 1) * 512));
+        if constexpr (X3) {
+#pragma unroll
+          for (int nb = 0; nb < NB; ++nb)
+            bop1[NB + nb] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(img + rows_img * 32 + min(blk0 + nb, nblk - 1) * 512));
+        }
       }
     }
     // both tile slots, unconditionally: a slot without live keys holds masked keys only (weight 0)
+    if constexpr (X3) {
+      bf16x8 a[4][2], wt[2][2];
+#pragma unroll
+      for (int pl = 0; pl < 2; ++pl) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          a[k][pl] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(base + pl * L::OFF_LO + a_off + 512 * k));
+        wt[0][pl] = lds_tr8(base + pl * L::OFF_LO + t_off, 512);
+        wt[1][pl] = lds_tr8(base + pl * L::OFF_LO + t_off + 1024, 512);
+      }
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb) {
+        if (NB > 1 && blk0 + nb >= nblk) continue;
+        tile3(a[0], a[1], wt[0], bop[nb], bop[NB * (NP - 1) + nb], nb);
+        tile3(a[2], a[3], wt[1], bop1[nb], bop1[NB * (NP - 1) + nb], nb);
+      }
+      continue;
+    }
     const bf16x8 a00 = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(base + a_off));
     const bf16x8 a01 = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(base + a_off + 512));
     const bf16x8 a10 = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(base + a_off + 1024));
@@ -241,11 +311,11 @@ int launch(const bevr_attn_desc& d, const void* G, const void* tap_ws, const flo
            , float* lsum TAP_DROP_PARAMS
 #endif
            ) {
-  typedef LdsT L;
+  typedef LdsTp<PREC> L;
   const int n_ph = d.n_prob * d.heads;
   const int grid = ((n_ph + 7) / 8) * 8 * d.S;
   const int nblk = (d.S + QB - 1) / QB;
-  const size_t lds = 2 * L::BUF + (size_t)L::RING * nblk * QB * 32;
+  const size_t lds = 2 * L::BUF + (size_t)L::RING * nblk * QB * 32 * (tap_x3(PREC) ? 2 : 1);
   if (lds > 160 * 1024) return BEVR_E_SHAPE;
   const int nb = nblk <= 7 ? 1 : nblk <= 14 ? 2 : 4;      // row blocks per wave: at most 7 row-block waves + the producer
   if (nblk > 28) return BEVR_E_SHAPE;
@@ -272,6 +342,17 @@ int launch(const bevr_attn_desc& d, const void* G, const void* tap_ws, const flo
 
 }  // namespace
 
+#if BEVR_TAP_X3
+// the split-mode instantiations: this translation unit is attn_tap_fwd_x3.hip, entered from bevr_attn_tap_fwd
+int bevr_tap_fwd_x3(const bevr_attn_desc& d, const void* G, const void* tap_ws, const float* table_pair, float* mref,
+                    float* R, int* flags, hipStream_t st) {
+  return launch<BEVR_PREC_BF16X3>(d, G, tap_ws, table_pair, mref, R, flags, st);
+}
+#else
+#if !BEVR_DROP
+int bevr_tap_fwd_x3(const bevr_attn_desc& d, const void* G, const void* tap_ws, const float* table_pair, float* mref,
+                    float* R, int* flags, hipStream_t st);     // attn_tap_fwd_x3.hip
+#endif
 #if BEVR_DROP
 extern "C" int bevr_attn_tap_fwd_dropout(const bevr_attn_desc* d, const void* G, const void* tap_ws,
                                          const float* table_pair, float* mref, float* R, float* lsum, int* flags,
@@ -290,5 +371,9 @@ extern "C" int bevr_attn_tap_fwd(const bevr_attn_desc* d, const void* G, const v
   hipStream_t st = (hipStream_t)stream;
   if (d->precision == BEVR_PREC_BF16) return launch<BEVR_PREC_BF16>(*d, G, tap_ws, table_pair, mref, R, flags, st BEVR_TAP_FWD_DROP_ARGS);
   if (d->precision == BEVR_PREC_F16) return launch<BEVR_PREC_F16>(*d, G, tap_ws, table_pair, mref, R, flags, st BEVR_TAP_FWD_DROP_ARGS);
+#if !BEVR_DROP
+  if (d->precision == BEVR_PREC_BF16X3) return bevr_tap_fwd_x3(*d, G, tap_ws, table_pair, mref, R, flags, st);
+#endif
   return BEVR_E_PRECISION;
 }
+#endif  // BEVR_TAP_X3

@@ -144,7 +144,9 @@ class SCADeformableAttention(nn.Module):
         passes True.  Only then, in the bf16 operand mode and with the offsets inside the tanh range (_pinned_keys_tap),
         does the segment run on the TAP kernels, which never form K and V and are exact only for keys that sample inside
         the top-left 4 x 3 feature pixels (csrc/attn_tap.h; the DEBUG build traps on a key outside them).  Without the
-        promise a caller's own reference_points / split stay on the cell kernels.
+        promise a caller's own reference_points / split stay on the cell kernels.  In the split-bf16 mode (no fused K | V
+        source) the same segment runs on the split-mode tap kernels when BEVR_TAP_X3=1 (ops.tap_supported): only the
+        scattered keys are sampled and projected then.
         Attention dropout (training mode, attn_drop_rate > 0): the keep mask lives in the region kernels and in the tap
         kernels.  A split that runs on the tap kernels is kept (scattered keys: region dropout kernels, pinned keys: tap
         dropout kernels, one mask); any other split is dropped and every key runs on the region kernels."""
@@ -187,6 +189,16 @@ class SCADeformableAttention(nn.Module):
                                    tap_source="pinned" if (split_is_pinned and cell_split is not None
                                                            and self._pinned_keys_tap(S, Hi, Wi)) else False,
                                    attn_drop=drop, concat_views=True)
+        elif (x.is_cuda and drop is None and split_is_pinned and cell_split is not None
+              and self.precision == ops._lib.PREC_BF16X3 and self._pinned_keys_tap(S, Hi, Wi)):
+            # split-bf16 mode: the scattered keys alone are sampled and projected; the pinned keys go through the tap
+            # kernels, which need the 12 pixels' source only (ops.attention_core, tap_pix) -- their feature-map and
+            # proj_k / proj_v gradients come through the 12-pixel F.linear there
+            xs = ops.sample_features(xf, pos[:, :cell_split].contiguous(), g)        # (B*V, cell_split, C)
+            kv = F.linear(xs, Wkv, bkv)
+            o = ops.attention_core(query, None, None, pos, self.rpe_table, heads=self.n_heads, groups=g, views=V,
+                                   precision=self.precision, kv=kv, cell_split=cell_split, tap_source="pinned",
+                                   tap_pix=(xf.permute(0, 2, 3, 1), Wkv, bkv), concat_views=True)
         else:
             xs = ops.sample_features(xf, pos, g)                                     # (B*V, N, C)
             kv = F.linear(xs, Wkv, bkv)

@@ -917,7 +917,7 @@ class _AttnCore(torch.autograd.Function):
 def attention_core(query: torch.Tensor, kproj: Optional[torch.Tensor], vproj: Optional[torch.Tensor], pos: torch.Tensor,
                    rpe_table: torch.Tensor, *, heads: int, groups: int, views: int, precision: int,
                    kv: Optional[torch.Tensor] = None, cell_split: Optional[int] = None, kv_source=None,
-                   tap_source=None, attn_drop=None, concat_views: bool = False) -> torch.Tensor:
+                   tap_source=None, attn_drop=None, concat_views: bool = False, tap_pix=None) -> torch.Tensor:
     """Fused attention of the BEV query against sampled keys.
 
     query (B, C, S, S) layer-normed BEV query (used raw as Q); kproj, vproj (B*views, N, C) projected
@@ -934,6 +934,13 @@ def attention_core(query: torch.Tensor, kproj: Optional[torch.Tensor], vproj: Op
     pixels of `feat` (the caller's contract: the projector-pinned keys, tap_supported) and go through the TAP kernels
     (csrc/attn_tap.h): their K and V are never formed -- the logits come from G = Q Kpix^T (12 pixels), the output from
     O = Rn Vpix, both thin GEMMs here -- and the segment is merged with the region kernels' through (O, LSE).
+    tap_pix = (feat, Wkv, bkv) (with tap_source and cell_split, WITHOUT kv_source): the tap segment beside projected rows --
+    the route of the split-bf16 mode (BEVR_PREC_BF16X3), which has no fused K | V source.  `kv` (or kproj / vproj) then
+    holds the projected rows of the scattered keys [0, cell_split) ONLY, (B*views, cell_split, 2C); `pos` still holds all N
+    keys; the pinned keys [cell_split, N) are never sampled or projected: feat (B*views, Hi, Wi, C) (any strides; only its
+    top-left 4 x 3 pixels are read) and Wkv / bkv give G = Q Kpix^T, Gb and O = Rn Vpix + bv as with kv_source.  The
+    scattered segment runs through the region kernels in the precision's own layout and the two segments merge through
+    (O, LSE) in float.  No attention dropout on this route (ValueError): the caller keeps every key in `kv` then.
     attn_drop = (p, seed): dropout on the softmax weights (the reference's attn_drop, :402-409): a weight is kept with
     probability 1 - p (p rounded to 1/65536) and scaled by 1 / (1 - p); the mask is the function dropout_keep_mask of
     (seed, problem-head, query, key) that the forward and backward kernels share.  With tap_source (and a call the tap
@@ -958,8 +965,10 @@ def attention_core(query: torch.Tensor, kproj: Optional[torch.Tensor], vproj: Op
         if not 0 < thr < 65536:
             raise ValueError("attention dropout probability must lie in (0, 1)")
         drop = (thr, int(attn_drop[1]) & 0xFFFFFFFF)
-        if not (tap_source and cell_split is not None and kv_source is not None and tap_supported(precision, groups)
-                and 16 * ((S + 15) // 16) <= 448):
+        if tap_pix is not None:
+            raise ValueError("tap_pix has no attention dropout: pass every key's projected rows and no tap segment")
+        if not (tap_source and cell_split is not None and kv_source is not None
+                and tap_supported(precision, groups, dropout=True) and 16 * ((S + 15) // 16) <= 448):
             cell_split, tap_source = None, None
     if kv_source is not None:
         if kv is not None or kproj is not None or vproj is not None:
@@ -978,6 +987,13 @@ def attention_core(query: torch.Tensor, kproj: Optional[torch.Tensor], vproj: Op
         Bp, N, C2 = kv.shape
         if C2 != 2 * Cc:
             raise ValueError(f"K | V rows must have 2 x {Cc} channels, got {C2}")
+        if tap_pix is not None:
+            if not tap_source or cell_split is None or N != int(cell_split) or pos.shape[0] != Bp:
+                raise ValueError("tap_pix needs tap_source, cell_split and the projected rows of the keys [0, cell_split) alone")
+            N = pos.shape[1]
+            feat, Wkv, bkv = tap_pix
+            if feat.shape[0] != Bp or feat.shape[-1] != Cc or tuple(Wkv.shape) != (2 * Cc, Cc):
+                raise ValueError("tap_pix shapes: feat (B*views, Hi, Wi, C), Wkv (2C, C), bkv (2C,)")
     c = Cc // heads
     split = N if cell_split is None else int(cell_split)
     if not 0 <= split <= N:
@@ -994,8 +1010,11 @@ def attention_core(query: torch.Tensor, kproj: Optional[torch.Tensor], vproj: Op
         if not ok:
             tap_source, split = None, N
     tap = bool(tap_source) and split < N
-    if tap and (kv_source is None or not tap_supported(precision, groups) or 16 * ((S + 15) // 16) > 448):
-        raise ValueError("tap_source needs kv_source, groups == 1, a 16-bit operand mode and S <= 448")
+    if tap and ((kv_source is None and tap_pix is None) or not tap_supported(precision, groups, dropout=drop is not None)
+                or 16 * ((S + 15) // 16) > 448):
+        raise ValueError("tap_source needs kv_source or tap_pix, groups == 1, a precision tap_supported accepts and S <= 448")
+    if tap_pix is not None and not tap:
+        raise ValueError("tap_pix needs a tap segment: 0 <= cell_split < N")
     geom = AttnGeom(n_prob=Bp, q_div=views, heads=heads, groups=groups, S=S, N=split if tap else N, Wt=Wt, precision=precision)
     f32_layout = precision in (_lib.PREC_F32, _lib.PREC_BF16X3)
     if not tap and split < N and (geom.Sp > 480 or (f32_layout and geom.Sp > 224) or (N - split) > 8 * 100 * 1024):
@@ -1018,7 +1037,9 @@ def attention_core(query: torch.Tensor, kproj: Optional[torch.Tensor], vproj: Op
     V = views
     Hi, Wi = feat.shape[1], feat.shape[2]
     O_r = LSE_r = None
-    if split > 0:
+    if split > 0 and tap_pix is not None:
+        O_r, LSE_r = _AttnCore.apply(Qp, kv.float(), a[:, :split], b[:, :split], Tt, geom, split, None, None, None, None, None)
+    elif split > 0:
         O_r, LSE_r = _AttnCore.apply(Qp, None, a[:, :split], b[:, :split], Tt, geom, split, feat,
                                      pos[:, :split].float().contiguous(), Wkv, bkv, drop)
     # the 12 pixels' K | V rows, without the bias: (B', 12, 2C); rows the image does not have are zero (zero padding)
@@ -1075,6 +1096,9 @@ TAP_HEADROOM_F16 = 8.0                            # fp16 operands: the weights 2
                                                   # flagged and recomputed with an online maximum (the EXACT pass)
 
 
+TAP_X3_DEFAULT = "0"                              # BEVR_TAP_X3 when unset (tap_supported)
+
+
 def tap_headroom(precision: int) -> float:
     return TAP_HEADROOM_F16 if precision == _lib.PREC_F16 else TAP_HEADROOM
 LN2 = 0.6931471805599453
@@ -1093,6 +1117,36 @@ def _set_offset(G16: torch.Tensor, c: torch.Tensor) -> torch.Tensor:
     G16[..., 12] = hi
     G16[..., 13] = lo
     return hi.float() + lo.float()
+
+
+def _set_offset_x3(planes: torch.Tensor, c: torch.Tensor) -> torch.Tensor:
+    """Split mode (include/bevrender_hip.h, "TAP entry points in BEVR_PREC_BF16X3"): slots 12, 13 of the (hi, lo) planes <-
+    the four bf16 parts of the row offset c, slot 12 = (p0, p1), slot 13 = (p2, p3); returns their sum (float): what the
+    kernels add to the row's logits."""
+    r = c.float()
+    parts = []
+    for _ in range(4):
+        p = r.to(torch.bfloat16)
+        parts.append(p)
+        r = r - p.float()
+    planes[0][..., 12], planes[1][..., 12] = parts[0], parts[1]
+    planes[0][..., 13], planes[1][..., 13] = parts[2], parts[3]
+    return ((parts[3].float() + parts[2].float()) + parts[1].float()) + parts[0].float()
+
+
+def tap_split_rows(rows: torch.Tensor, c: Optional[torch.Tensor] = None, dead: float = 0.0):
+    """The G / H operand of the tap entry points in BEVR_PREC_BF16X3, as include/bevrender_hip.h words it: rows (..., 12)
+    float -> planes (2, ..., 16) bf16, plane 0 = hi = bf16(x), plane 1 = lo = bf16(x - hi) in slots 0..11; the row offset
+    c (...) in four bf16 parts in slots 12, 13 (_set_offset_x3; c = None: zero); slot 14 = (dead, 0) -- -1e30 for G, the
+    logit of a masked key; slot 15 zero.  Returns (planes, c as the kernels add it).  Plain torch: runs on any device."""
+    rows = rows.float()
+    planes = torch.zeros((2,) + tuple(rows.shape[:-1]) + (TAP_SLOTS,), device=rows.device, dtype=torch.bfloat16)
+    hi = rows.to(torch.bfloat16)
+    planes[0][..., :TAP_N] = hi
+    planes[1][..., :TAP_N] = (rows - hi.float()).to(torch.bfloat16)
+    planes[0][..., 14] = dead
+    c_eff = None if c is None else _set_offset_x3(planes, c)
+    return planes, c_eff
 
 
 class _TapAttn(torch.autograd.Function):
@@ -1124,14 +1178,21 @@ class _TapAttn(torch.autograd.Function):
                    "bevr_attn_tap_prep")
         Ttc = Tt.contiguous()
         pair = torch.stack((Ttc[..., :-1], Ttc[..., 1:]), dim=-1).contiguous()
-        G16 = torch.zeros(P, h, Mp, TAP_SLOTS, device=dev, dtype=ed)
-        G16[..., :TAP_N] = G
-        G16[..., 14] = _neg_big(ed)
+        x3 = geom.precision == _lib.PREC_BF16X3
         # static softmax reference: an upper bound of the row's logits (the tap weights and the 4 bias taps are convex
         # weights up to their 16-bit rounding) minus the headroom -- no weight can overflow, nothing is tracked in the loop
         tmax = Ttc.amax(-1).amax(-1).clamp_min(0.0)       # two stages: see _AttnCore.forward
-        ub = 1.01 * (G16[..., :TAP_N].float().amax(-1).clamp_min(0.0) + tmax[None, :, None]) + 0.01
-        mref = (-_set_offset(G16, tap_headroom(geom.precision) - ub)).contiguous()
+        if x3:
+            # split mode: (hi, lo) planes of the float rows, the offset in four parts (tap_split_rows)
+            ub = 1.01 * (G.float().amax(-1).clamp_min(0.0) + tmax[None, :, None]) + 0.01
+            G16, c_eff = tap_split_rows(G, tap_headroom(geom.precision) - ub, _neg_big(torch.bfloat16))
+            mref = (-c_eff).contiguous()
+        else:
+            G16 = torch.zeros(P, h, Mp, TAP_SLOTS, device=dev, dtype=ed)
+            G16[..., :TAP_N] = G
+            G16[..., 14] = _neg_big(ed)
+            ub = 1.01 * (G16[..., :TAP_N].float().amax(-1).clamp_min(0.0) + tmax[None, :, None]) + 0.01
+            mref = (-_set_offset(G16, tap_headroom(geom.precision) - ub)).contiguous()
         # zeros: the kernels work in 16-row blocks and never touch the rows past the last block of a column
         R = torch.zeros(P, h, Mp, TAP_SLOTS, device=dev, dtype=torch.float32)
         flags = torch.zeros(P * h, geom.S, device=dev, dtype=torch.int32)
@@ -1179,7 +1240,8 @@ class _TapAttn(torch.autograd.Function):
         P, h, Mp = geom.n_prob, geom.heads, geom.Mp
         d = geom.desc()
         valid = (torch.arange(Mp, device=dev) % geom.Sp) < geom.S
-        H16 = torch.zeros(P, h, Mp, TAP_SLOTS, device=dev, dtype=ed)
+        x3 = geom.precision == _lib.PREC_BF16X3
+        H16 = None if x3 else torch.zeros(P, h, Mp, TAP_SLOTS, device=dev, dtype=ed)
         sdo = None
         if ed == torch.float16:
             # fp16 has 5 exponent bits and the reference trains without a loss scaler: the cotangents of a mean-type loss
@@ -1197,6 +1259,16 @@ class _TapAttn(torch.autograd.Function):
             dRn = None if dRn is None else dRn * sdo
             dLSE = None if dLSE is None else dLSE * sdo
             dmass = None if dmass is None else dmass * sdo
+        if x3:
+            # split mode (no dropout here): the planes first, delta from hi + lo -- the H values the kernel contracts
+            H16, _ = tap_split_rows(torch.zeros_like(Rn) if dRn is None else dRn * LN2)
+            delta = (Rn * (H16[0][..., :TAP_N].float() + H16[1][..., :TAP_N].float())).sum(-1)
+            if dLSE is not None:
+                delta = delta - dLSE
+            _set_offset_x3(H16, -delta)
+            Gq = G16.clone()
+            _set_offset_x3(Gq, torch.where(valid, -LSE, torch.full_like(LSE, _neg_big(ed))))
+            return _TapAttn._backward_launch(geom, d, L, drop, Gq, H16, ws, pair, Ttc, valid, sdo)
         if dRn is not None:
             H16[..., :TAP_N] = dRn * (LN2 * Dk)
         if dmass is not None:
@@ -1211,6 +1283,13 @@ class _TapAttn(torch.autograd.Function):
         _set_offset(H16, -delta)
         Gq = G16.clone()
         _set_offset(Gq, torch.where(valid, -LSE, torch.full_like(LSE, _neg_big(ed))))
+        return _TapAttn._backward_launch(geom, d, L, drop, Gq, H16, ws, pair, Ttc, valid, sdo)
+
+    @staticmethod
+    def _backward_launch(geom, d, L, drop, Gq, H16, ws, pair, Ttc, valid, sdo):
+        """The two backward launches on prepared operands (either operand format) and the gradients out of them."""
+        dev = Ttc.device
+        P, h, Mp = geom.n_prob, geom.heads, geom.Mp
         dG = torch.zeros(P, h, Mp, TAP_SLOTS, device=dev, dtype=torch.float32)     # rows past the last 16-row block: never written
         dT = torch.zeros_like(Ttc)
         dk = [torch.zeros(P, geom.Np, device=dev, dtype=torch.float32) for _ in range(4)]
@@ -1235,10 +1314,18 @@ class _TapAttn(torch.autograd.Function):
         return dGo, da, db, dy, dx, dT, None, None
 
 
-def tap_supported(precision: int, groups: int) -> bool:
+def tap_supported(precision: int, groups: int, dropout: bool = False) -> bool:
     """The 16-bit operand modes (fp16 since round 5: headroom 8 and a power-of-two scale on the cotangents, see
-    _TapAttn); BEVR_TAP=0 keeps the pinned keys on the cell kernels."""
-    return precision in (_lib.PREC_BF16, _lib.PREC_F16) and groups == 1 and os.environ.get("BEVR_TAP", "1") != "0"
+    _TapAttn); BEVR_TAP=0 keeps the pinned keys on the cell kernels.  The split-bf16 mode (BEVR_PREC_BF16X3:
+    csrc/attn_tap_*_x3.hip, operands by tap_split_rows) without attention dropout (`dropout`: the call has a keep mask --
+    the tap dropout kernels are 16-bit only) when BEVR_TAP_X3=1; BEVR_TAP_X3=0 is that mode's earlier routing, every key
+    through the region / cell kernels.  The switch's default is TAP_X3_DEFAULT: off until the SCA block is MEASURED faster
+    on the new route (tools/ab_sca_x3.py)."""
+    if groups != 1 or os.environ.get("BEVR_TAP", "1") == "0":
+        return False
+    if precision == _lib.PREC_BF16X3:
+        return not dropout and os.environ.get("BEVR_TAP_X3", TAP_X3_DEFAULT) != "0"
+    return precision in (_lib.PREC_BF16, _lib.PREC_F16)
 
 
 def kv_source_supported(C: int, heads: int, groups: int, precision: int) -> bool:

@@ -58,7 +58,9 @@ extern "C" {
  *    Added since, without a new version (nothing a version-6 caller uses changed): bevr_attn_tap_fwd_dropout,
  *    bevr_attn_tap_bwd_q_dropout, bevr_attn_tap_bwd_k_dropout (attention dropout on the tap entry points);
  *    bevr_attn_gather_fwd_rows (the gather forward over a row range of every BEV column: BEV sides above 224), and
- *    bevr_attn_gather_fwd accepts BEVR_PREC_F16 where it returned BEVR_E_PRECISION. */
+ *    bevr_attn_gather_fwd accepts BEVR_PREC_F16 where it returned BEVR_E_PRECISION;
+ *    bevr_attn_tap_fwd, bevr_attn_tap_bwd_q and bevr_attn_tap_bwd_k accept BEVR_PREC_BF16X3 where they returned
+ *    BEVR_E_PRECISION (operand format: "TAP entry points in BEVR_PREC_BF16X3" below). */
 #define BEVR_ABI_VERSION 6
 
 enum {
@@ -255,7 +257,8 @@ int bevr_attn_cell_bwd_k(const bevr_attn_desc* d, const void* Q, const void* Qt,
  *   output  O_q     = sum_t Rn[t][q] Vpix_t + bv,                    Rn = R / R[15],  R[t][q] = sum_n w_t(n) P[n][q]
  * The caller forms G, Gb (thin GEMMs) before and O after the launch, and merges the segment with the other keys of the
  * same softmax through (mref, R[15]): the segment's log2-sum-exp is mref[q] + log2 R[15][q].
- * Geometry, table, descriptor (groups == 1, precision BEVR_PREC_BF16 or BEVR_PREC_F16) as above; keys cell-sorted for
+ * Geometry, table, descriptor (groups == 1, precision BEVR_PREC_BF16 or BEVR_PREC_F16 -- E below; BEVR_PREC_BF16X3 with
+ * the operand format at the end of this comment) as above; keys cell-sorted for
  * speed (any key set is handled: a 32-key run that does not fit one table chunk is processed in several masked passes).
  *   key_a, key_b, key_y, key_x [n_prob][Np] float: table coordinates as above; sampling position in FEATURE PIXELS
  *       ys = (py + 1)/2 (Hi - 1), xs likewise (ys < 3 and xs < 2 or outside the image: the caller's contract)
@@ -274,6 +277,24 @@ int bevr_attn_cell_bwd_k(const bevr_attn_desc* d, const void* Q, const void* Qt,
  *       recomputed with an online maximum and its rows' mref are replaced.
  *   R   [n_prob][heads][Mp][16] float (written; rows 12, 13 equal row 15)   flags [n_prob*heads][S] int32, ZEROED by the
  *       caller (scratch)
+ *
+ * TAP entry points in BEVR_PREC_BF16X3 (bevr_attn_tap_fwd, _bwd_q, _bwd_k; the _dropout entry points and BEVR_PREC_F32
+ * return BEVR_E_PRECISION; bevr_attn_tap_prep and bevr_attn_tap_ws_bytes do not look at the precision).  The CALLER
+ * splits G and H; the kernels split what they form themselves (tap and bias-cell weights, the table's chunk, P and dS)
+ * and multiply in three bf16 products, lo hi + hi lo + hi hi (the logit contraction in all four), everything per pair in f32.  tap_ws, tables, mref, R,
+ * flags, dG, dtable, dkey_* are as in the 16-bit modes (float).
+ *   G, H  [2][n_prob][heads][Mp][16] bf16: plane 0 = hi, plane 1 = lo (the lo plane n_prob * heads * Mp * 32 bytes behind
+ *       the hi plane), both round-to-nearest-even:
+ *         slots 0..11: x = the float tap value,  hi = bf16(x), lo = bf16(x - hi)      (hi + lo = x to 2^-17 relative)
+ *         slots 12, 13: the row offset c (G: Gb - mref in bevr_attn_tap_fwd, Gb - LSE in the backward; H: Hc) in FOUR
+ *           parts, p0 = bf16(c), p1 = bf16(c - p0), p2 = bf16(c - p0 - p1), p3 = bf16(c - p0 - p1 - p2):
+ *           slot 12 = (hi p0, lo p1), slot 13 = (hi p2, lo p3).  The key side holds 1 = (hi 1, lo 0) in both slots, so
+ *           the product adds p0 + p1 + p2 + p3 = c to the float's last bit: the large constant part of every logit does
+ *           not go through the three-term product's 2^-16
+ *         slot 14: G hi = -1e30 (the logit of a masked key), lo = 0; H zero.   slot 15: zero
+ *       (bevrender_amd/ops.py:tap_split_rows is this builder.)
+ *   mref as above: the reference AS THE KERNEL SEES IT, Gb - (p0 + p1 + p2 + p3).  The weights 2^(S - mref) are split into
+ *       bf16 hi + lo before the R product: headroom <= 100 as for BEVR_PREC_BF16 (bf16 has the float's exponent range).
  * ---------------------------------------------------------------------------------------------- */
 size_t bevr_attn_tap_ws_bytes(const bevr_attn_desc* d);
 int bevr_attn_tap_prep(const bevr_attn_desc* d, const float* key_a, const float* key_b, const float* key_y,

@@ -1,0 +1,98 @@
+"""A/B of the SCA block in the split-bf16 mode (BEVR_PREC_BF16X3) at the benchmark geometry: forward + backward of
+SpatialCrossAttn (S = 200, 6 views, D = 5, 64 x 176 features, B samples), the pinned keys on the split-mode tap kernels
+(BEVR_TAP_X3=1, ops.attention_core(tap_pix=...)) against the earlier routing (BEVR_TAP_X3=0: every key sampled, projected
+and sent through the region / cell kernels).  The two routes alternate in ONE process (the switch is read per call), HIP
+events around each step, one warm-up step per route; medians with min and max.
+
+    B=8 ITERS=5 python tools/ab_sca_x3.py [out.json]"""
+import json
+import math
+import os
+import statistics
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from bevrender_amd import _lib, ops  # noqa: E402
+from bevrender_amd.model.SCA import SpatialCrossAttn  # noqa: E402
+from bevrender_amd.model.bev_cmr_proj import BEV2CameraProjector  # noqa: E402
+
+DEV = "cuda"
+
+
+def ring_rig(V, img_w, img_h):
+    """bench.py's rig: V cameras on a ring (yaw 360 v / V, pitch 0, 1.5 m up), fx = fy = 0.8 W."""
+    R0 = np.array([[0, 0, 1], [-1, 0, 0], [0, -1, 0]], dtype=np.float64)
+    T, K = [], []
+    for v in range(V):
+        a = 2 * math.pi * v / V
+        Rz = np.array([[math.cos(a), -math.sin(a), 0], [math.sin(a), math.cos(a), 0], [0, 0, 1]])
+        M = np.eye(4)
+        M[:3, :3] = Rz @ R0
+        M[:3, 3] = (0, 0, 1.5)
+        T.append(M)
+        K.append(np.array([[0.8 * img_w, 0, img_w / 2, 0], [0, 0.8 * img_w, img_h / 2, 0], [0, 0, 1, 0]]))
+    return T, K
+
+
+def main():
+    B, iters = int(os.environ.get("B", "8")), max(5, int(os.environ.get("ITERS", "5")))
+    S, D, V, C, h, img_w, img_h = 200, 5, 6, 64, 2, 704, 256
+    Hi, Wi = img_h // 4, img_w // 4
+    T, K = ring_rig(V, img_w, img_h)
+    proj = BEV2CameraProjector(imu_to_rgb={0: T}, K={0: K}, vehicle_type_code=0, img_width=img_w, img_height=img_h,
+                               ori_img_width=img_w, ori_img_height=img_h, device=DEV)
+    sca = SpatialCrossAttn({"X": 50, "Y": 50, "Z": 2}, proj, S, D, -1.0, C, h, 1, 1, 3, B, True, n_views=V,
+                           precision=_lib.PREC_BF16X3)
+    gen = torch.Generator().manual_seed(11)
+    with torch.no_grad():
+        for prm in sca.parameters():
+            prm.copy_(torch.randn(prm.shape, generator=gen) * (0.3 if prm.dim() == 1 else 1.0 / math.sqrt(max(1, prm[0].numel()))))
+    sca = sca.to(DEV)
+    q = torch.randn(B, C, S, S, generator=gen).to(DEV).requires_grad_(True)
+    x = torch.randn(B * V, C, Hi, Wi, generator=gen).to(DEV).requires_grad_(True)
+    cot = torch.randn(B, C, S, S, generator=gen).to(DEV)
+    times = {"tap_x3": [], "parent_route": []}
+    kernels = {}
+
+    def step(tag, sw, record):
+        os.environ["BEVR_TAP_X3"] = sw
+        for t in list(sca.parameters()) + [q, x]:
+            t.grad = None
+        if record:
+            ops.KERNEL_TIMER.start()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out, _ = sca(q, x, torch.tensor(0), None, False)
+        out.backward(cot)
+        e1.record()
+        torch.cuda.synchronize()
+        if record:
+            kernels[tag] = {k: round(v["ms"], 2) for k, v in ops.KERNEL_TIMER.stop().items()}
+        return e0.elapsed_time(e1)
+
+    for it in range(iters + 1):
+        for tag, sw in (("tap_x3", "1"), ("parent_route", "0")):
+            ms = step(tag, sw, False)
+            if it > 0:
+                times[tag].append(ms)
+    for tag, sw in (("tap_x3", "1"), ("parent_route", "0")):       # one more step of each with per-kernel events
+        step(tag, sw, True)
+    res = {"what": "SCA block forward + backward, bf16x3, S=200, 6 views, B=%d; routes alternating in one process" % B,
+           "iters": iters}
+    for tag, v in times.items():
+        res[tag] = {"median_ms": round(statistics.median(v), 1), "min_ms": round(min(v), 1), "max_ms": round(max(v), 1),
+                    "all_ms": [round(t, 1) for t in v]}
+    res["ratio_new_over_parent"] = round(res["tap_x3"]["median_ms"] / res["parent_route"]["median_ms"], 3)
+    res["kernels_ms_one_step"] = kernels
+    print(json.dumps(res, indent=1))
+    if len(sys.argv) > 1:
+        with open(sys.argv[1], "w") as f:
+            json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()

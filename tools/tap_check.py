@@ -1,6 +1,8 @@
 """Tap kernels (csrc/attn_tap*.hip) against a float64 restatement of their definition, and their timing at the benchmark's
 shape.   python tools/tap_check.py check        small random cases, forward (+ backward when built)
-         B=2 python tools/tap_check.py time     S=200, 65 984 keys per problem, B samples x 6 views x 2 heads"""
+         B=2 python tools/tap_check.py time     S=200, 65 984 keys per problem, B samples x 6 views x 2 heads
+         B=2 python tools/tap_check.py time x3  the same in the split-bf16 mode (BEVR_PREC_BF16X3), alternated with the
+                                                cell kernels in that mode on the same keys and the bf16 tap kernels"""
 import ctypes as C
 import os
 import sys
@@ -29,6 +31,37 @@ def tap_w(ys, xs, dtype=torch.float64):
     return w
 
 
+X3 = _lib.PREC_BF16X3
+MIMIC_X3 = "x3"      # `mimic` of the split mode: a value as the kernels' (hi, lo) bf16 pair carries it
+
+
+def _mim(x, mimic):
+    """x (float64) rounded as operand mode `mimic` holds it: a 16-bit dtype, or MIMIC_X3 = bf16(x) + bf16(x - bf16(x))."""
+    x = x.float()
+    if mimic == MIMIC_X3:
+        hi = x.to(torch.bfloat16).float()
+        return (hi.double() + (x - hi).to(torch.bfloat16).double())
+    return x.to(mimic).double()
+
+
+def header_split(rows, c, dead=0.0):
+    """The G / H operand of the tap entry points in BEVR_PREC_BF16X3 from the words of include/bevrender_hip.h alone
+    ("TAP entry points in BEVR_PREC_BF16X3"): rows (..., 16) float with slots 0..11 the values, c (...) the row offset ->
+    planes (2, ..., 16) bf16 and the offset as the kernels add it (p0 + p1 + p2 + p3)."""
+    rows = rows.float()
+    pl = torch.zeros((2,) + tuple(rows.shape), device=rows.device, dtype=torch.bfloat16)
+    hi = rows[..., :12].to(torch.bfloat16)
+    pl[0][..., :12] = hi
+    pl[1][..., :12] = (rows[..., :12] - hi.float()).to(torch.bfloat16)
+    pl[0][..., 14] = dead
+    r, parts = c.float(), []
+    for _ in range(4):
+        parts.append(r.to(torch.bfloat16))
+        r = r - parts[-1].float()
+    pl[0][..., 12], pl[1][..., 12], pl[0][..., 13], pl[1][..., 13] = parts
+    return pl.contiguous(), ((parts[3].float() + parts[2].float()) + parts[1].float()) + parts[0].float()
+
+
 def bias_ref(T2, a, b, S, Wt, j, mimic=None):
     """T2 (h, Ht, Wt) float64, a, b (N,) -> bias (h, S rows i, N) for BEV column j: bilinear at (i + a, j rx + b), zeros outside."""
     h, Ht, _ = T2.shape
@@ -44,7 +77,7 @@ def bias_ref(T2, a, b, S, Wt, j, mimic=None):
             yy, xx = (y0 + dy).long(), (x0 + dx).long()
             wgt = (fy if dy else 1 - fy) * (fx if dx else 1 - fx)
             if mimic is not None:
-                wgt = wgt.float().to(mimic).double()
+                wgt = _mim(wgt, mimic)
             ok = (yy >= 0) & (yy < Ht) & (xx >= 0) & (xx < Wt)
             v = T2[:, yy.clamp(0, Ht - 1), xx.clamp(0, Wt - 1)]
             out += torch.where(ok, wgt, torch.zeros_like(wgt))[None] * v
@@ -60,8 +93,8 @@ def reference(G, Gb, a, b, ys, xs, T2, S, Wt, N, mimic=None):
     Gbd = Gb.double().reshape(P, h, S, Sp)[:, :, :, :S]
     w = tap_w(ys[:, :N], xs[:, :N])
     if mimic is not None:
-        w = w.float().to(mimic).double()
-        T2 = T2.float().to(mimic).double()
+        w = _mim(w, mimic)
+        T2 = _mim(T2, mimic)
     Rn = torch.zeros(P, h, S, S, 16, dtype=torch.float64, device=G.device)
     LSE = torch.zeros(P, h, S, S, dtype=torch.float64, device=G.device)
     for p in range(P):
@@ -111,26 +144,39 @@ def set_offset(G, c):
     return hi.float() + lo.float()
 
 
-def make_case(P, h, S, N, Wt, spread=(5.0, 2.5), gscale=4.0, seed=0, prec=_lib.PREC_BF16, sort=True, n_dead_logit=False):
-    gen = torch.Generator(device=dev).manual_seed(seed)
-    ed = torch.bfloat16 if prec == _lib.PREC_BF16 else torch.float16
-    geom = ops.AttnGeom(n_prob=P, q_div=1, heads=h, groups=1, S=S, N=N, Wt=Wt, precision=prec)
-    a = (S - 1) + (torch.rand(P, N, device=dev, generator=gen) * 2 - 1) * spread[0]
-    b = (Wt - 1) / 2.0 + (torch.rand(P, N, device=dev, generator=gen) * 2 - 1) * spread[1]
-    ys = (torch.rand(P, N, device=dev, generator=gen) * 2 - 1) * 1.6
-    xs = (torch.rand(P, N, device=dev, generator=gen) * 2 - 1) * 0.45
+def draw_keys(P, S, N, Wt, spread, sort, gen):
+    """The keys of a case, drawn on the generator's device: table coordinates around the table's centre, sampling
+    positions inside the tap grid; cell-sorted with `sort`."""
+    gd = gen.device
+    a = (S - 1) + (torch.rand(P, N, device=gd, generator=gen) * 2 - 1) * spread[0]
+    b = (Wt - 1) / 2.0 + (torch.rand(P, N, device=gd, generator=gen) * 2 - 1) * spread[1]
+    ys = (torch.rand(P, N, device=gd, generator=gen) * 2 - 1) * 1.6
+    xs = (torch.rand(P, N, device=gd, generator=gen) * 2 - 1) * 0.45
     if sort:
         order = ops.cell_order(a, b)
         a, b, ys, xs = (t.gather(1, order) for t in (a, b, ys, xs))
+    return a, b, ys, xs
+
+
+def make_case(P, h, S, N, Wt, spread=(5.0, 2.5), gscale=4.0, seed=0, prec=_lib.PREC_BF16, sort=True, n_dead_logit=False,
+              host_rng=False):
+    """host_rng: draw with a CPU generator (the same numbers on a machine without a GPU: draw_keys with
+    torch.Generator().manual_seed(seed) gives this case's keys there)."""
+    gd = "cpu" if host_rng else dev
+    gen = torch.Generator(device=gd).manual_seed(seed)
+    # (split mode: G stays float -- run_fwd / run_bwd_* split it as the header words it, header_split)
+    ed = torch.bfloat16 if prec == _lib.PREC_BF16 else torch.float32 if prec == X3 else torch.float16
+    geom = ops.AttnGeom(n_prob=P, q_div=1, heads=h, groups=1, S=S, N=N, Wt=Wt, precision=prec)
+    a, b, ys, xs = (t.to(dev) for t in draw_keys(P, S, N, Wt, spread, sort, gen))
     pad = geom.Np - N
     a, b, ys, xs = (torch.nn.functional.pad(t, (0, pad)).contiguous() for t in (a, b, ys, xs))
     G = torch.zeros(P, h, geom.Mp, 16, device=dev)
-    G[..., :12] = torch.randn(P, h, geom.Mp, 12, device=dev, generator=gen) * gscale
+    G[..., :12] = torch.randn(P, h, geom.Mp, 12, device=gd, generator=gen).to(dev) * gscale
     valid = (torch.arange(geom.Mp, device=dev) % geom.Sp) < S
     G = G * valid[None, None, :, None]
-    G[..., 14] = -1.0e30 if prec == _lib.PREC_BF16 else -60000.0
-    Gb = torch.randn(P, h, geom.Mp, device=dev, generator=gen) * valid
-    T = torch.randn(h, 2 * S - 1, Wt, device=dev, generator=gen) * 0.5
+    G[..., 14] = -1.0e30 if prec in (_lib.PREC_BF16, X3) else -60000.0
+    Gb = torch.randn(P, h, geom.Mp, device=gd, generator=gen).to(dev) * valid
+    T = torch.randn(h, 2 * S - 1, Wt, device=gd, generator=gen).to(dev) * 0.5
     return geom, a, b, ys, xs, G.to(ed), Gb.contiguous(), T
 
 
@@ -144,8 +190,12 @@ def run_fwd(geom, a, b, ys, xs, G, Gb, T, headroom=64.0, timer=None):
                                     ops._stream()), "tap_prep")
     tmax = (T.float() * ops.LOG2E).amax((1, 2)).clamp_min(0)                                 # per head
     U = G[..., :12].float().amax(-1).clamp_min(0) * 1.01 + Gb + tmax[None, :, None] * 1.01 + 0.01
-    G = G.clone()
-    mref = (Gb - set_offset(G, Gb - (U - headroom))).contiguous()      # the reference the kernel works against
+    if geom.precision == X3:
+        G, c_eff = header_split(G, Gb - (U - headroom), dead=-1.0e30)
+        mref = (Gb - c_eff).contiguous()
+    else:
+        G = G.clone()
+        mref = (Gb - set_offset(G, Gb - (U - headroom))).contiguous()      # the reference the kernel works against
     R = torch.empty(geom.n_prob, geom.heads, geom.Mp, 16, device=dev, dtype=torch.float32)
     flags = torch.zeros(geom.n_prob * geom.heads, geom.S, device=dev, dtype=torch.int32)
     args = (C.byref(d), ops._ptr(G), ops._ptr(ws), ops._ptr(pair), ops._ptr(mref), ops._ptr(R),
@@ -165,9 +215,12 @@ def run_fwd(geom, a, b, ys, xs, G, Gb, T, headroom=64.0, timer=None):
 def run_bwd_q(geom, G, Gc, H, Hc, ws, pair, timer=None):
     L = _lib.lib()
     d = geom.desc()
-    G, H = G.clone(), H.clone()
-    set_offset(G, Gc)
-    set_offset(H, Hc)
+    if geom.precision == X3:
+        G, H = header_split(G, Gc, dead=-1.0e30)[0], header_split(H, Hc)[0]
+    else:
+        G, H = G.clone(), H.clone()
+        set_offset(G, Gc)
+        set_offset(H, Hc)
     dG = torch.empty(geom.n_prob, geom.heads, geom.Mp, 16, device=dev, dtype=torch.float32)
     dT = torch.zeros(geom.heads, geom.Wp, geom.Hp + 1, device=dev, dtype=torch.float32)
     args = (C.byref(d), ops._ptr(G), ops._ptr(H), ops._ptr(ws), ops._ptr(pair), ops._ptr(dG), ops._ptr(dT), ops._stream())
@@ -184,9 +237,12 @@ def run_bwd_q(geom, G, Gc, H, Hc, ws, pair, timer=None):
 def run_bwd_k(geom, G, Gc, H, Hc, ws, Tt, timer=None):
     L = _lib.lib()
     d = geom.desc()
-    G, H = G.clone(), H.clone()
-    set_offset(G, Gc)
-    set_offset(H, Hc)
+    if geom.precision == X3:
+        G, H = header_split(G, Gc, dead=-1.0e30)[0], header_split(H, Hc)[0]
+    else:
+        G, H = G.clone(), H.clone()
+        set_offset(G, Gc)
+        set_offset(H, Hc)
     outs = [torch.zeros(geom.n_prob, geom.Np, device=dev, dtype=torch.float32) for _ in range(4)]
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
@@ -214,6 +270,7 @@ def header_table(T, geom):
 def check_case(name, **kw):
     headroom = kw.pop("headroom", 64.0)
     from_header = kw.pop("from_header", False)
+    h_cols = kw.pop("h_cols", None)       # BEV columns that carry the backward's cotangent (default: all)
     geom, a, b, ys, xs, G, Gb, T = make_case(**kw)
     R, mref, flags, _, _ = run_fwd(geom, a, b, ys, xs, G, Gb, T, headroom)
     torch.cuda.synchronize()
@@ -223,11 +280,13 @@ def check_case(name, **kw):
     l = Rg[..., 15]
     Rn_got = Rg / l[..., None]
     lse_got = mr + torch.log2(l)
-    mim = torch.bfloat16 if geom.precision == _lib.PREC_BF16 else torch.float16
+    mim = torch.bfloat16 if geom.precision == _lib.PREC_BF16 else MIMIC_X3 if geom.precision == X3 else torch.float16
     T2 = T.double() * ops.LOG2E
     out = {}
     for tag, mm in (("exact", None), ("mimic", mim)):
-        Rn, LSE = reference(G.float(), Gb, a, b, ys, xs, T2, S, geom.Wt, geom.N, mm)
+        # (split mode: the kernels see G as hi + lo of the float, the mimic takes that pair)
+        Gin = _mim(G.double(), mm).float() if mm == MIMIC_X3 else G.float()
+        Rn, LSE = reference(Gin, Gb, a, b, ys, xs, T2, S, geom.Wt, geom.N, mm)
         sel = [t for t in range(16) if t not in (12, 13)]
         out[tag] = ((Rn_got[..., sel] - Rn[..., sel]).abs().max().item(), (lse_got - LSE).abs().max().item())
     print(f"{name:28s} flagged {int(flags.sum())}  Rn err exact {out['exact'][0]:.2e} mimic {out['mimic'][0]:.2e}   "
@@ -239,9 +298,14 @@ def check_case(name, **kw):
     H = torch.zeros(geom.n_prob, geom.heads, geom.Mp, 16, device=dev)
     H[..., :12] = torch.randn(geom.n_prob, geom.heads, geom.Mp, 12, device=dev, generator=gen)
     H = (H * valid[None, None, :, None]).to(ed)
+    if h_cols is not None:
+        col = torch.zeros(S, dtype=torch.bool, device=dev)
+        col[torch.tensor(list(h_cols), device=dev)] = True
+        valid = valid & col.repeat_interleave(Sp)
+        H = H * valid[None, None, :, None].to(ed)
     Hc = (torch.randn(geom.n_prob, geom.heads, geom.Mp, device=dev, generator=gen) * valid).contiguous()
     _, LSE = reference(G.float(), Gb, a, b, ys, xs, T2, S, geom.Wt, geom.N, None)
-    lse_p = torch.full((geom.n_prob, geom.heads, S, Sp), 1.0e30 if geom.precision == _lib.PREC_BF16 else 30000.0, device=dev, dtype=torch.float64)
+    lse_p = torch.full((geom.n_prob, geom.heads, S, Sp), 1.0e30 if geom.precision in (_lib.PREC_BF16, X3) else 30000.0, device=dev, dtype=torch.float64)
     lse_p[:, :, :, :S] = LSE
     Gc = (Gb.double() - lse_p.reshape(geom.n_prob, geom.heads, geom.Mp)).float().contiguous()
     _, _, _, ws, pair = run_fwd(geom, a, b, ys, xs, G, Gb, T, headroom)
@@ -258,7 +322,65 @@ def check_case(name, **kw):
     out.update(flagged=int(flags.sum()), dG=relerr(dGg[..., :12], wdG[..., :12]), dGb=relerr(dGg[..., 15], wdG[..., 15]),
                dtable=relerr(dTg, wdT), da=relerr(da, wda), db=relerr(db, wdb), dys=relerr(dy, wdy), dxs=relerr(dx, wdx),
                dead=Rn_got[..., 14].abs().max().item())
+    # per-key position gradients (got, want) and the keys, for callers that judge them key by key
+    out["keys"] = dict(geom=geom, a=a[:, :geom.N], b=b[:, :geom.N], ys=ys[:, :geom.N], xs=xs[:, :geom.N],
+                       da=(da, wda), db=(db, wdb), dys=(dy, wdy), dxs=(dx, wdx))
     return out
+
+
+def time_x3():
+    """The three tap kernels in the split mode against the cell kernels in that mode on the SAME keys (what those keys ran
+    on before), and the bf16 tap kernels as the upper reference: alternated in one process, ITERS rounds (>= 5), median
+    [min, max] per kernel.  The cell side runs through ops._AttnCore on K | V rows of the keys (every key in its cell
+    segment) and is timed by ops.KERNEL_TIMER's events."""
+    import statistics
+    B = int(os.environ.get("B", "2"))
+    iters = max(5, int(os.environ.get("ITERS", "5")))
+    S, h, D, V = 200, 2, 5, 6
+    N = int(os.environ.get("N", "65984"))
+    cases = {p: make_case(P=B * V, h=h, S=S, N=N, Wt=2 * S * D - 1, prec=p) for p in (X3, _lib.PREC_BF16)}
+    t = {}
+
+    def tap_round(tag, prec):
+        geom, a, b, ys, xs, G, Gb, T = cases[prec]
+        tf, tq, tk = t.setdefault(tag + " fwd", []), t.setdefault(tag + " bwd_q", []), t.setdefault(tag + " bwd_k", [])
+        R, mref, flags, ws, pair = run_fwd(geom, a, b, ys, xs, G, Gb, T, timer=tf)
+        lse = (mref + torch.log2(R[..., 15].clamp_min(1e-37)))
+        gen = torch.Generator(device=dev).manual_seed(3)
+        H = (torch.randn(G.shape, device=dev, generator=gen) * (torch.arange(16, device=dev) < 12)).to(G.dtype)
+        Hc = torch.randn(Gb.shape, device=dev, generator=gen)
+        run_bwd_q(geom, G, (Gb - lse).contiguous(), H, Hc, ws, pair, timer=tq)
+        run_bwd_k(geom, G, (Gb - lse).contiguous(), H, Hc, ws, ops.pack_table(T.float(), geom).contiguous(), timer=tk)
+
+    geom, a, b, ys, xs, G, Gb, T = cases[X3]
+    C_ = 64
+    gen = torch.Generator(device=dev).manual_seed(11)
+    Qp = torch.randn(B, h, geom.Mp, ops.HEAD_DIM, device=dev, generator=gen) * 0.3
+    kv = torch.randn(B * V, N, 2 * C_, device=dev, generator=gen)
+    cgeom = ops.AttnGeom(n_prob=B * V, q_div=V, heads=h, groups=1, S=S, N=N, Wt=2 * S * D - 1, precision=X3)
+    Tt = ops.pack_table(T.float(), cgeom)
+
+    def cell_round():
+        q = Qp.clone().requires_grad_(True)
+        k = kv.clone().requires_grad_(True)
+        ops.KERNEL_TIMER.start()
+        O, _ = ops._AttnCore.apply(q, k, a[:, :N].contiguous(), b[:, :N].contiguous(), Tt, cgeom, 0, None, None, None, None, None)
+        O.square().sum().backward()
+        for name, r in ops.KERNEL_TIMER.stop().items():
+            if name.startswith("bevr_attn_cell"):
+                t.setdefault("cell x3 " + name[len("bevr_attn_cell_"):], []).append(r["ms"])
+
+    for it in range(iters + 1):
+        tap_round("tap x3", X3)
+        cell_round()
+        tap_round("tap bf16", _lib.PREC_BF16)
+        if it == 0:
+            t.clear()            # warm-up round
+    print(f"S={S} N={N} problems={B * V} heads={h}: ms per launch, median [min, max] of {iters}")
+    for k_ in sorted(t):
+        v = t[k_]
+        print(f"  {k_:18s} {statistics.median(v):8.2f} [{min(v):.2f}, {max(v):.2f}]")
+    return t
 
 
 def main():
@@ -270,6 +392,8 @@ def main():
         check_case("S=40 (3 blocks) N=1000", P=1, h=1, S=40, N=1000, Wt=2 * 40 * 5 - 1, seed=3)
         check_case("big logits (exact pass)", P=1, h=2, S=16, N=300, Wt=2 * 16 * 3 - 1, gscale=200.0, seed=4)
         check_case("fp16", P=1, h=2, S=24, N=400, Wt=2 * 24 * 3 - 1, seed=5, prec=_lib.PREC_F16, gscale=2.0, headroom=8.0)
+    elif len(sys.argv) > 2 and sys.argv[2] == "x3":
+        time_x3()
     else:
         B = int(os.environ.get("B", "2"))
         S, h, D, V = 200, 2, 5, 6
