@@ -159,52 +159,57 @@ class SCADeformableAttention(nn.Module):
         N = pos.shape[3]
         pos = pos.reshape(B * V * g, N, 2)
         drop = attention_dropout(self)      # (p, seed) in training mode with attn_drop_rate > 0, else None
-        if drop is not None and not (split_is_pinned and self._pinned_keys_tap(S, Hi, Wi) and x.is_cuda
-                                     and ops.kv_source_supported(C, self.n_heads, g, self.precision)):
-            # the keep mask lives in the region and the tap kernels: the pinned keys keep their segment when it runs on the
-            # tap kernels, otherwise every key goes to the region kernels
-            cell_split = None
-        if cell_split is not None and cell_split < N and g == 1:
+        Wt = self.rpe_table.shape[-1]
+        pinned = split_is_pinned and self._pinned_keys_tap(S, Hi, Wi)
+        if not (cell_split is not None and cell_split < N and g == 1):
             # groups > 1: a key is one row of K built from all groups' samples, so the groups cannot be ordered
             # independently; the split is simply not used then
+            cell_split = None
+        # the K | V source, each condition once: the fused source where the kernel covers the call; the tap segment beside
+        # projected rows in the split-bf16 mode (no fused source there; no keep mask on that route); else projected rows
+        source = "kv"
+        if x.is_cuda and ops.kv_source_supported(C, self.n_heads, g, self.precision):
+            source = "kv_source"
+        elif x.is_cuda and pinned and cell_split is not None and drop is None and self.precision == ops._lib.PREC_BF16X3:
+            source = "tap_pix"
+        tap_source = False
+        if cell_split is not None:
+            # what becomes of the split is ops.attention_route's decision: the pinned keys on the tap kernels (with or
+            # without a keep mask), any keys on the cell kernels, or -- the keep mask lives in the region and the tap
+            # kernels only -- dropped, every key on the region kernels
+            route = ops.attention_route(self.precision, g, S, Wt, N, cell_split, "pinned" if pinned and source != "kv" else False,
+                                        drop is not None, source, C, self.n_heads)
+            tap_source = "pinned" if route.tap else False
+            cell_split = cell_split if route.split < N else None
+        if cell_split is not None:
             n_tail = min(CELL_TAIL, max(0, N - cell_split - 1024))
             with torch.no_grad():
-                a, b = ops.key_coords(pos[:, cell_split:], S, self.rpe_table.shape[-1], N - cell_split)
+                a, b = ops.key_coords(pos[:, cell_split:], S, Wt, N - cell_split)
                 dyn = ops.cell_order(a, b, n_tail)
             pos = torch.cat((pos[:, :cell_split], pos[:, cell_split:].gather(1, dyn[..., None].expand(-1, -1, 2))), 1)
             cell_split = cell_split + n_tail      # the keys of the sparsest cells join the region segment (ops.cell_order)
-        else:
-            cell_split = None
         # proj_k and proj_v as ONE GEMM over the sampled features (same arithmetic per output column; the features are
         # read once instead of twice)
         Wkv = torch.cat((self.proj_k.weight.flatten(1), self.proj_v.weight.flatten(1)), 0)
         bkv = torch.cat((self.proj_k.bias, self.proj_v.bias), 0)
         xf = x.reshape(B * V, C, Hi, Wi)
-        if x.is_cuda and ops.kv_source_supported(C, self.n_heads, g, self.precision):
+        if source == "kv_source":
             # sampling, projection and operand packing as one kernel (csrc/kvproj.hip): neither the sampled features
             # nor the projected rows reach HBM.  The channels-last view of the backbone's output is read as it is
             feat = (xf if xf.dtype == torch.bfloat16 else xf.float()).permute(0, 2, 3, 1).contiguous()
-            o = ops.attention_core(query, None, None, pos, self.rpe_table, heads=self.n_heads, groups=g, views=V,
-                                   precision=self.precision, kv_source=(feat, Wkv, bkv), cell_split=cell_split,
-                                   tap_source="pinned" if (split_is_pinned and cell_split is not None
-                                                           and self._pinned_keys_tap(S, Hi, Wi)) else False,
-                                   attn_drop=drop, concat_views=True)
-        elif (x.is_cuda and drop is None and split_is_pinned and cell_split is not None
-              and self.precision == ops._lib.PREC_BF16X3 and self._pinned_keys_tap(S, Hi, Wi)):
+            src = dict(kv_source=(feat, Wkv, bkv))
+        elif source == "tap_pix":
             # split-bf16 mode: the scattered keys alone are sampled and projected; the pinned keys go through the tap
             # kernels, which need the 12 pixels' source only (ops.attention_core, tap_pix) -- their feature-map and
             # proj_k / proj_v gradients come through the 12-pixel F.linear there
             xs = ops.sample_features(xf, pos[:, :cell_split].contiguous(), g)        # (B*V, cell_split, C)
-            kv = F.linear(xs, Wkv, bkv)
-            o = ops.attention_core(query, None, None, pos, self.rpe_table, heads=self.n_heads, groups=g, views=V,
-                                   precision=self.precision, kv=kv, cell_split=cell_split, tap_source="pinned",
-                                   tap_pix=(xf.permute(0, 2, 3, 1), Wkv, bkv), concat_views=True)
+            src = dict(kv=F.linear(xs, Wkv, bkv), tap_pix=(xf.permute(0, 2, 3, 1), Wkv, bkv))
         else:
             xs = ops.sample_features(xf, pos, g)                                     # (B*V, N, C)
-            kv = F.linear(xs, Wkv, bkv)
-            o = ops.attention_core(query, None, None, pos, self.rpe_table, heads=self.n_heads, groups=g, views=V,
-                                   precision=self.precision, kv=kv, cell_split=cell_split, attn_drop=drop,
-                                   concat_views=True)
+            src = dict(kv=F.linear(xs, Wkv, bkv))
+        o = ops.attention_core(query, None, None, pos, self.rpe_table, heads=self.n_heads, groups=g, views=V,
+                               precision=self.precision, cell_split=cell_split, tap_source=tap_source, attn_drop=drop,
+                               concat_views=True, **src)
         # o: (B, S*S, V*C), the views side by side as proj_out contracts them (reference :415-420), written by the
         # attention's unpacking in one pass: no (B, V, M, C) -> (B, M, V C) permute copy in between
         out = ops.linear_rows(o, self.proj_out.weight.flatten(1), self.proj_out.bias)

@@ -12,6 +12,7 @@ import ctypes as C
 import math
 import os
 from dataclasses import dataclass, replace as dc_replace
+from types import SimpleNamespace
 from typing import Optional, Tuple
 
 import torch
@@ -175,7 +176,6 @@ class _MergeViews(torch.autograd.Function):
     @staticmethod
     def forward(ctx, O_r, L_r, O_c, L_c, S, c, views):
         _require_gpu(O_r, L_r, O_c, L_c)
-        L = _lib.lib()
         BV, h, Mp, hd = O_r.shape
         assert hd == HEAD_DIM and Mp % S == 0 and BV % views == 0
         two = O_c is not None
@@ -185,17 +185,14 @@ class _MergeViews(torch.autograd.Function):
             assert O_c.shape == O_r.shape and L_r.shape == L_c.shape == O_r.shape[:3]
         out = torch.empty(BV // views, S * S, views * h * c, device=O_r.device, dtype=torch.float32)
         nbytes = float((O_r.numel() * (2 if two else 1)) * S / (Mp // S) * c / HEAD_DIM * 4 + out.numel() * 4)
-        _lib.check(KERNEL_TIMER.run("bevr_merge_views_fwd", 0.0, L.bevr_merge_views_fwd, _ptr(O_r),
-                                    _ptr(L_r) if two else None, _ptr(O_c) if two else None, _ptr(L_c) if two else None,
-                                    _ptr(out), BV, views, h, S, Mp // S, c, _stream(), nbytes=nbytes),
-                   "bevr_merge_views_fwd")
+        _launch("bevr_merge_views_fwd", _ptr(O_r), _ptr(L_r) if two else None, _ptr(O_c) if two else None,
+                _ptr(L_c) if two else None, _ptr(out), BV, views, h, S, Mp // S, c, _stream(), flops=0.0, nbytes=nbytes)
         ctx.save_for_backward(*((O_r, L_r, O_c, L_c) if two else ()))
         ctx.dims = (BV, views, h, S, Mp // S, c, two)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        L = _lib.lib()
         BV, views, h, S, Sp, c, two = ctx.dims
         dout = dout.float().contiguous()
         dO_r = torch.empty(BV, h, S * Sp, HEAD_DIM, device=dout.device, dtype=torch.float32)
@@ -205,11 +202,10 @@ class _MergeViews(torch.autograd.Function):
         else:
             O_r = L_r = O_c = L_c = dO_c = dL_r = dL_c = None
         nbytes = float(dout.numel() * 4 * (5 if two else 2))
-        _lib.check(KERNEL_TIMER.run("bevr_merge_views_bwd", 0.0, L.bevr_merge_views_bwd, _ptr(dout), _ptr(O_r) if two else None,
-                                    _ptr(L_r) if two else None, _ptr(O_c) if two else None, _ptr(L_c) if two else None,
-                                    _ptr(dO_r), _ptr(dL_r) if two else None, _ptr(dO_c) if two else None,
-                                    _ptr(dL_c) if two else None, BV, views, h, S, Sp, c, _stream(), nbytes=nbytes),
-                   "bevr_merge_views_bwd")
+        _launch("bevr_merge_views_bwd", _ptr(dout), _ptr(O_r) if two else None, _ptr(L_r) if two else None,
+                _ptr(O_c) if two else None, _ptr(L_c) if two else None, _ptr(dO_r), _ptr(dL_r) if two else None,
+                _ptr(dO_c) if two else None, _ptr(dL_c) if two else None, BV, views, h, S, Sp, c, _stream(), flops=0.0,
+                nbytes=nbytes)
         return dO_r, dL_r, dO_c, dL_c, None, None, None
 
 
@@ -219,7 +215,6 @@ class _MergeTap(torch.autograd.Function):
     @staticmethod
     def forward(ctx, O_r, L_r, Rn, L_c, Vp, bv, S, c, views):
         _require_gpu(O_r, L_r, Rn, L_c, Vp, bv)
-        L = _lib.lib()
         BV, h, Mp, hd = O_r.shape
         assert hd == HEAD_DIM and Mp % S == 0 and BV % views == 0 and Rn.shape == (BV, h, Mp, TAP_N)
         assert Vp.shape == (BV, h, TAP_N, HEAD_DIM) and bv.shape == (h, HEAD_DIM)
@@ -227,25 +222,23 @@ class _MergeTap(torch.autograd.Function):
         out = torch.empty(BV // views, S * S, views * h * c, device=O_r.device, dtype=torch.float32)
         live = S / (Mp // S)
         nbytes = float(O_r.numel() * live * (c / HEAD_DIM + TAP_N / HEAD_DIM) * 4 + out.numel() * 4)
-        _lib.check(KERNEL_TIMER.run("bevr_merge_views_fwd", 0.0, L.bevr_merge_tap_fwd, _ptr(O_r), _ptr(L_r), _ptr(Rn), _ptr(L_c),
-                                    _ptr(Vp), _ptr(bv), _ptr(out), BV, views, h, S, Mp // S, c, _stream(), nbytes=nbytes),
-                   "bevr_merge_tap_fwd")
+        _launch("bevr_merge_tap_fwd", _ptr(O_r), _ptr(L_r), _ptr(Rn), _ptr(L_c), _ptr(Vp), _ptr(bv), _ptr(out), BV, views, h, S,
+                Mp // S, c, _stream(), flops=0.0, nbytes=nbytes, timer="bevr_merge_views_fwd")
         ctx.save_for_backward(O_r, L_r, Rn, L_c, Vp, bv)
         ctx.dims = (BV, views, h, S, Mp // S, c)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        L = _lib.lib()
         BV, views, h, S, Sp, c = ctx.dims
         O_r, L_r, Rn, L_c, Vp, bv = ctx.saved_tensors
         dout = dout.float().contiguous()
         dO_r, dL_r, dRn, dL_c = torch.empty_like(O_r), torch.empty_like(L_r), torch.empty_like(Rn), torch.empty_like(L_c)
         dVp, dbv = torch.zeros_like(Vp), torch.zeros_like(bv)
         nbytes = float(dout.numel() * 4 * (3 + 2 * TAP_N / HEAD_DIM))
-        _lib.check(KERNEL_TIMER.run("bevr_merge_views_bwd", 0.0, L.bevr_merge_tap_bwd, _ptr(dout), _ptr(O_r), _ptr(L_r), _ptr(Rn),
-                                    _ptr(L_c), _ptr(Vp), _ptr(bv), _ptr(dO_r), _ptr(dL_r), _ptr(dRn), _ptr(dL_c), _ptr(dVp),
-                                    _ptr(dbv), BV, views, h, S, Sp, c, _stream(), nbytes=nbytes), "bevr_merge_tap_bwd")
+        _launch("bevr_merge_tap_bwd", _ptr(dout), _ptr(O_r), _ptr(L_r), _ptr(Rn), _ptr(L_c), _ptr(Vp), _ptr(bv), _ptr(dO_r),
+                _ptr(dL_r), _ptr(dRn), _ptr(dL_c), _ptr(dVp), _ptr(dbv), BV, views, h, S, Sp, c, _stream(), flops=0.0,
+                nbytes=nbytes, timer="bevr_merge_views_bwd")
         return dO_r, dL_r, dRn, dL_c, dVp, dbv, None, None, None
 
 
@@ -529,12 +522,121 @@ def dropout_keep_mask(seed: int, thr16: int, n_ph: int, S: int, N: int, device="
     return (x >> 16) >= thr16
 
 
-@dataclass
-class _Seg:
-    """One key segment of an attention call: keys [n0, n0 + geom.N) of the caller's arrays."""
-    cell: bool          # cell kernels (attn_cell_*.hip) or region kernels (attn_fwd.hip ...)
+def _launch(entry, *args, flops=None, nbytes=0.0, tag="", timer=None, label=None):
+    """One call of the C entry point `entry` (named once per call site) and the check of its return code.  flops given:
+    through KERNEL_TIMER.run under the timer name `timer` (default: the entry point's), else untimed -- the timer's
+    records are bench.py's roofline counts.  label: the name in the error message where it is not the entry point's."""
+    fn = getattr(_lib.lib(), entry)
+    rc = fn(*args) if flops is None else KERNEL_TIMER.run(timer or entry, flops, fn, *args, nbytes=nbytes, tag=tag)
+    _lib.check(rc, label or entry)
+
+
+class K:
+    """The attention kernels a route chooses among (include/bevrender_hip.h), each entry point spelled once."""
+    FWD, FWD_DROP = "bevr_attn_fwd", "bevr_attn_fwd_dropout"
+    GATHER, GATHER_ROWS = "bevr_attn_gather_fwd", "bevr_attn_gather_fwd_rows"
+    BWD_Q, BWD_Q_DROP, SLAB_BWD_Q = "bevr_attn_bwd_q", "bevr_attn_bwd_q_dropout", "bevr_attn_slab_bwd_q"
+    BWD_K, BWD_K_DROP = "bevr_attn_bwd_k", "bevr_attn_bwd_k_dropout"
+    CELL_FWD, CELL_BWD_Q, CELL_BWD_K = "bevr_attn_cell_fwd", "bevr_attn_cell_bwd_q", "bevr_attn_cell_bwd_k"
+    TAP_FWD, TAP_FWD_DROP = "bevr_attn_tap_fwd", "bevr_attn_tap_fwd_dropout"
+    TAP_BWD_Q, TAP_BWD_Q_DROP = "bevr_attn_tap_bwd_q", "bevr_attn_tap_bwd_q_dropout"
+    TAP_BWD_K, TAP_BWD_K_DROP = "bevr_attn_tap_bwd_k", "bevr_attn_tap_bwd_k_dropout"
+
+
+@dataclass(frozen=True)
+class KeySegment:
+    """One key segment of an attention call: keys [n0, n1) of the caller's arrays and the entry points that attend them."""
+    kind: str           # "region" (attn_fwd.hip ...: scattered keys), "cell" (attn_cell_*.hip) or "tap" (attn_tap*.hip)
     n0: int
-    geom: AttnGeom
+    n1: int
+    fwd: str
+    bwd_q: str
+    bwd_k: str
+
+
+@dataclass(frozen=True)
+class AttnRoute:
+    """What attention_route decides: everything about a call's kernels that is known before a tensor's data is touched."""
+    segments: Tuple[KeySegment, ...]    # in key order; their softmax is one (chained or merged through (O, LSE))
+    split: int              # the caller's cell_split as the call keeps it: keys [split, N) are still a segment of their own
+                            # (N: no split, or dropout / the tap check dropped it); the cell kernels' size limits join the
+                            # segments below without changing it
+    gather: Optional[str]   # the gather forward of the region segment: "whole", "bands" (gather_bands) or None
+    kn2: bool               # bevr_kv_project emits the largest squared K row norm (the gather forward's reference)
+    merge: str              # "merge_tap" (region + tap halves, the tap half's O formed on the way) or "merge_views"
+
+    @property
+    def tap(self) -> bool:
+        return self.segments[-1].kind == "tap"
+
+    @property
+    def n_core(self) -> int:
+        """keys [0, n_core) run on the region / cell kernels (_AttnCore): all of them, or those before a tap segment"""
+        return self.segments[-1].n0 if self.tap else self.segments[-1].n1
+
+
+def attention_route(precision: int, groups: int, S: int, Wt: int, N: int, cell_split: Optional[int] = None,
+                    tap_source=False, dropout: bool = False, source: str = "kv", C: int = HEAD_DIM, heads: int = 1,
+                    keys_in_tap_grid=None) -> AttnRoute:
+    """Which kernels an attention_core call runs -- the one place that decides it, host only (no tensor is read).
+    precision, groups, S (BEV side), Wt (table width), N keys, cell_split, tap_source (False / True / "pinned") as
+    attention_core takes them; dropout: the call has a keep mask; source: "kv" (projected rows), "kv_source" or "tap_pix";
+    C, heads: the channels.  keys_in_tap_grid(split) -> bool: the ONE data-dependent input, "do the keys [split, N) all
+    sample inside the tap grid?" (a reduction and a host sync at the caller): called at most once, and only for
+    tap_source=True with dropout and a split that would otherwise be kept.  Raises attention_core's routing ValueErrors.
+    Reads the A/B switches itself (BEVR_KNORM, BEVR_MERGE_TAP) or through gather_supported, slab_supported,
+    tap_supported and kv_source_supported."""
+    if dropout:
+        if source == "tap_pix":
+            raise ValueError("tap_pix has no attention dropout: pass every key's projected rows and no tap segment")
+        if not (tap_source and cell_split is not None and source == "kv_source"
+                and tap_supported(precision, groups, dropout=True) and 16 * ((S + 15) // 16) <= 448):
+            cell_split, tap_source = None, None
+    if source == "kv_source" and not kv_source_supported(C, heads, groups, precision):
+        raise ValueError("kv_source needs a 16-bit operand mode, C % 16 == 0 and (C / groups) % 4 == 0")
+    split = N if cell_split is None else int(cell_split)
+    if not 0 <= split <= N:
+        raise ValueError("cell_split must lie in [0, N]")
+    if dropout and tap_source and tap_source != "pinned" and split < N:
+        # no region segment beside it (split == 0): the route dropout always took for such a call
+        if not (split > 0 and keys_in_tap_grid(split)):
+            tap_source, split = None, N
+    tap = bool(tap_source) and split < N
+    if tap and (source == "kv" or not tap_supported(precision, groups, dropout=dropout) or 16 * ((S + 15) // 16) > 448):
+        raise ValueError("tap_source needs kv_source or tap_pix, groups == 1, a precision tap_supported accepts and S <= 448")
+    if source == "tap_pix" and not tap:
+        raise ValueError("tap_pix needs a tap segment: 0 <= cell_split < N")
+    Sp = 32 * ((S + 31) // 32)
+    f32_layout = precision in (_lib.PREC_F32, _lib.PREC_BF16X3)
+    n_region = split
+    if not tap and split < N and (Sp > 480 or (f32_layout and Sp > 224) or (N - split) > 8 * 100 * 1024):
+        # the cell kernels run one wave per 32-row block of a BEV column + a producer wave, 16 at most; with f32-sized
+        # operands the 512-thread instantiation (the one without spills) ends at 7 row blocks + the producer; and the slow
+        # pass lists a segment's tiles in LDS (4 bytes per 32 keys next to the staging buffers): a segment beyond
+        # ~800 000 keys would not fit.  Such calls keep every key on the region kernels (any split is a valid result)
+        n_region = N
+    segs, gather = [], None
+    if n_region > 0:
+        if dropout:     # the keep mask lives in the query-tile kernels: no gather forward, no slab backward
+            segs.append(KeySegment("region", 0, n_region, K.FWD_DROP, K.BWD_Q_DROP, K.BWD_K_DROP))
+        else:
+            if gather_supported(precision, S):
+                gather = "whole" if len(gather_bands(S)) == 1 else "bands"
+            fwd = {None: K.FWD, "whole": K.GATHER, "bands": K.GATHER_ROWS}[gather]
+            bwd_q = K.SLAB_BWD_Q if slab_supported(precision, S, Wt) else K.BWD_Q
+            segs.append(KeySegment("region", 0, n_region, fwd, bwd_q, K.BWD_K))
+    if tap and dropout:
+        segs.append(KeySegment("tap", split, N, K.TAP_FWD_DROP, K.TAP_BWD_Q_DROP, K.TAP_BWD_K_DROP))
+    elif tap:
+        segs.append(KeySegment("tap", split, N, K.TAP_FWD, K.TAP_BWD_Q, K.TAP_BWD_K))
+    elif n_region < N:
+        segs.append(KeySegment("cell", n_region, N, K.CELL_FWD, K.CELL_BWD_Q, K.CELL_BWD_K))
+    # the static softmax reference of the gather forward needs the largest K row norm: out of the projection kernel
+    kn2 = source == "kv_source" and gather is not None and os.environ.get("BEVR_KNORM", "1") != "0"
+    # (the fused merge_tap assumes a kept mass of 1: no mask)
+    fused_merge = (tap and split > 0 and not dropout and (C // heads) % 4 == 0
+                   and os.environ.get("BEVR_MERGE_TAP", "1") != "0")
+    return AttnRoute(tuple(segs), split, gather, kn2, "merge_tap" if fused_merge else "merge_views")
 
 
 def gather_supported(precision, S) -> bool:
@@ -590,16 +692,137 @@ def backward_scales(bound: torch.Tensor, pmax_log2: torch.Tensor, f16: bool, dro
     return torch.stack((torch.exp2(e), torch.exp2(-e), zero, one, one, one, zero, zero)).float().contiguous()
 
 
+# ---- the routes: one function per launch signature, on the operand bundle `o` of _AttnCore / _TapAttn ----
+def _fwd_tile(name, o):
+    _launch(name, C.byref(o.desc), _ptr(o.Qe), _ptr(o.Ke), _ptr(o.Vt), _ptr(o.key_ws), _ptr(o.pair), _ptr(o.O), _ptr(o.LSE),
+            *o.drop, _stream(), flops=_attn_flops(o.g, 2), tag=_call_tag(o.g))
+
+
+def _fwd_cell(name, o):
+    chain = (_ptr(o.O), _ptr(o.LSE)) if o.chained else (None, None)      # (O, LSE) of the segment before this one
+    _launch(name, C.byref(o.desc), _ptr(o.Qe), _ptr(o.Ke), _ptr(o.Vt), _ptr(o.key_ws), _ptr(o.pair), *chain, _ptr(o.O),
+            _ptr(o.LSE), _stream(), flops=_attn_flops(o.g, 2), tag=_call_tag(o.g))
+
+
+def _fwd_gather(name, o):
+    g, Ttc = o.g, o.Ttc
+    pair_pk = o.pair.to(o.Qe.dtype)             # (h, Wp, Hp, 2) 16-bit: one dword per (column, row) entry
+    # Tt is the table in log2 units already; two-stage maximum (a reduction to `heads` outputs in one stage
+    # runs on `heads` workgroups: 0.6 ms for the 27 MB table)
+    tmax = torch.maximum(Ttc.amax(-1).amax(-1), -Ttc.amin(-1).amin(-1))
+    qn = torch.linalg.vector_norm(o.Qe, dim=-1, dtype=torch.float32)          # (B, h, Mp)
+    # static softmax reference: |Q_q . K_n| <= ||Q_q|| max_n ||K_n||, |bias| <= max |T2| (a convex combination;
+    # 1 % for the 16-bit rounding of operands and weights), minus the headroom
+    if o.kn2 is not None:      # of the unrounded rows: the rounding is inside the 1 % below
+        kmx = o.kn2.sqrt()
+    else:
+        kmx = torch.linalg.vector_norm(o.Ke[:, :, :g.N], dim=-1, dtype=torch.float32).amax(-1)    # (B', h)
+    ub = 1.01 * (qn.repeat_interleave(g.q_div, 0) * kmx[..., None] + tmax[None, :, None]) + 0.01
+    mref = (ub - tap_headroom(g.precision)).contiguous()
+    bands = gather_bands(g.S) if name == K.GATHER_ROWS else [()]
+    # scratch of one call's two passes: zeroed per call (per band)
+    gflags = torch.zeros(len(bands), g.n_prob * g.heads * g.S, device=o.O.device, dtype=torch.int32)
+    for bi, rows in enumerate(bands):       # rows = (row0, n_rows); (the timer's name is the route's, whichever entry point runs it)
+        flops = _attn_flops(g, 2) * rows[1] / g.S if rows else _attn_flops(g, 2)
+        _launch(name, C.byref(o.desc), _ptr(o.Qe), _ptr(o.Ke), _ptr(o.Ve), _ptr(o.key_ws), _ptr(pair_pk), _ptr(mref),
+                _ptr(o.O), _ptr(o.LSE), _ptr(gflags[bi]), *rows, _stream(), flops=flops, tag=_call_tag(g), timer=K.GATHER)
+
+
+def _bwd_q_tile(name, o):
+    _launch(name, C.byref(o.desc), _ptr(o.Qe), _ptr(o.Ke), _ptr(o.Kt), _ptr(o.Ve), _ptr(o.key_ws), _ptr(o.pair), _ptr(o.dOe),
+            _ptr(o.LSE), _ptr(o.delta), _ptr(o.gscale), _ptr(o.dQ), _ptr(o.dT), *o.drop, _stream(),
+            flops=_attn_flops(o.g, 3), tag=_call_tag(o.g))
+
+
+def _bwd_q_slab(name, o):
+    g, Ke, Ve = o.g, o.Ke, o.Ve
+    # keys sorted by table column b per problem-group; K and V rows gathered into that order (softmax and its
+    # gradients do not depend on the order of the keys; dK / dV come from the key-side kernel in the caller's)
+    order = o.kb[:, :g.N].argsort(1)
+    hpg = g.heads // g.groups
+    idx = order.view(g.n_prob, g.groups, 1, g.N).expand(-1, -1, hpg, -1).reshape(g.n_prob, g.heads, g.N, 1)
+    idx = idx.expand(-1, -1, -1, HEAD_DIM)
+    Ks, Vs = Ke[:, :, :g.N].gather(2, idx), Ve[:, :, :g.N].gather(2, idx)
+    sws = torch.empty(_lib.lib().bevr_attn_slab_ws_bytes(C.byref(o.desc)), device=Ke.device, dtype=torch.uint8)
+    _launch("bevr_attn_slab_prep", C.byref(o.desc), _ptr(o.ka), _ptr(o.kb), _ptr(order.to(torch.int32).contiguous()),
+            _ptr(sws), _stream())
+    _launch(name, C.byref(o.desc), _ptr(o.Qe), _ptr(Ks), _ptr(Vs), _ptr(sws), _ptr(o.pair), _ptr(o.dOe), _ptr(o.LSE),
+            _ptr(o.delta), _ptr(o.gscale), _ptr(o.dQ), _ptr(o.dT), _stream(), flops=_attn_flops(g, 3), tag=_call_tag(g))
+
+
+def _bwd_k(name, o, *keys):
+    _launch(name, C.byref(o.desc), _ptr(o.Qe), _ptr(o.Qt), _ptr(o.Ke), _ptr(o.Ve), *keys, _ptr(o.pair), _ptr(o.dOe),
+            _ptr(o.dOt), _ptr(o.LSE), _ptr(o.delta), _ptr(o.gscale), _ptr(o.dK), _ptr(o.dV), _ptr(o.da), _ptr(o.db), *o.drop,
+            _stream(), flops=_attn_flops(o.g, 4), tag=_call_tag(o.g))
+
+
+def _bwd_k_tile(name, o):       # the keys' table coordinates themselves
+    _bwd_k(name, o, _ptr(o.ka), _ptr(o.kb))
+
+
+def _bwd_k_cell(name, o):       # the prepared per-tile boxes
+    _bwd_k(name, o, _ptr(o.key_ws))
+
+
+def _tap_fwd(name, o):          # o.lsum, o.drop: () without a keep mask
+    _launch(name, C.byref(o.desc), _ptr(o.G16), _ptr(o.ws), _ptr(o.pair), _ptr(o.mref), _ptr(o.R), *o.lsum, _ptr(o.flags),
+            *o.drop, _stream(), flops=_attn_flops(o.g, 2), tag=_call_tag(o.g))
+
+
+def _tap_bwd_q(name, o):
+    _launch(name, C.byref(o.desc), _ptr(o.Gq), _ptr(o.H16), _ptr(o.ws), _ptr(o.pair), _ptr(o.dG), _ptr(o.dT), *o.drop,
+            _stream(), flops=_attn_flops(o.g, 3), tag=_call_tag(o.g))
+
+
+def _tap_bwd_k(name, o):
+    _launch(name, C.byref(o.desc), _ptr(o.Gq), _ptr(o.H16), _ptr(o.ws), _ptr(o.Ttc), *[_ptr(t) for t in o.dk], *o.drop,
+            _stream(), flops=_attn_flops(o.g, 4), tag=_call_tag(o.g))
+
+
+_RUN = {K.FWD: _fwd_tile, K.FWD_DROP: _fwd_tile, K.GATHER: _fwd_gather, K.GATHER_ROWS: _fwd_gather, K.CELL_FWD: _fwd_cell,
+        K.BWD_Q: _bwd_q_tile, K.BWD_Q_DROP: _bwd_q_tile, K.CELL_BWD_Q: _bwd_q_tile, K.SLAB_BWD_Q: _bwd_q_slab,
+        K.BWD_K: _bwd_k_tile, K.BWD_K_DROP: _bwd_k_tile, K.CELL_BWD_K: _bwd_k_cell,
+        K.TAP_FWD: _tap_fwd, K.TAP_FWD_DROP: _tap_fwd, K.TAP_BWD_Q: _tap_bwd_q, K.TAP_BWD_Q_DROP: _tap_bwd_q,
+        K.TAP_BWD_K: _tap_bwd_k, K.TAP_BWD_K_DROP: _tap_bwd_k}
+
+
+def _run(name, o):
+    """the launch the route names, on the operands `o`"""
+    _RUN[name](name, o)
+
+
+def _kv_source_adjoint(dkv, feat, spos, Wkv, G, need_dfeat, need_dW, need_dbias):
+    """Adjoint of the fused K | V source in its unfused form: the projection's GEMMs on the float samples (recomputed:
+    the forward never wrote them) and the sampler's scatter.  dkv (B', N, 2C) -> (dfeat, dspos, dW, dbias).
+    Group gi's channels are sampled at group gi's positions: the map as B' G images of C / G channels (G > 1: a copy of
+    the feature map, small next to the rows; G == 1: every reshape below is a view and no .contiguous() copies), the
+    rows back to (B', N, C)."""
+    nb, Hi, Wi, Cc = feat.shape
+    fg = feat.reshape(nb, Hi, Wi, G, Cc // G).permute(0, 3, 1, 2, 4).reshape(nb * G, Hi, Wi, Cc // G).contiguous()
+    xs = _Sample.sample(fg, spos).reshape(nb, G, -1, Cc // G).permute(0, 2, 1, 3).reshape(nb, -1, Cc)     # (B', N, C) float
+    d2 = dkv.reshape(-1, dkv.shape[-1])
+    # the weight gradient as one GEMM per problem, summed: rocBLAS runs the single (2C x B'N) @ (B'N x C) product with
+    # its 1.7 M-long contraction at 2.2 ms per SCA call, the batched form at 0.57 (tools/prof_kv_adjoint.py)
+    dW = torch.bmm(dkv.transpose(1, 2), xs).sum(0) if need_dW else None
+    dbias = d2.sum(0) if need_dbias else None
+    dxs = (d2 @ Wkv.float()).reshape(nb, -1, G, Cc // G).permute(0, 2, 1, 3).reshape(nb * G, -1, Cc // G).contiguous()
+    del xs
+    dfg, dspos = _Sample.scatter(fg, spos, dxs, need_dfeat)
+    dfeat = None if dfg is None else dfg.reshape(nb, G, Hi, Wi, Cc // G).permute(0, 2, 3, 1, 4).reshape(feat.shape)
+    return dfeat, dspos, dW, dbias
+
+
 class _AttnCore(torch.autograd.Function):
     """O = softmax(Q K^T + bias(a, b, table)) V in packed layouts (all inputs float32).
 
     The keys may be split into two segments that share one softmax: keys [0, split) go through the region kernels
     (scattered keys: LDS table windows, per-pair bias gather), keys [split, N) through the cell kernels (keys the
     caller sorted by table cell: bias as an MFMA).  The forward chains the segments through (O, LSE) in place; the
-    backward passes of both use the final LSE and delta and accumulate into the same dQ and d(table)."""
+    backward passes of both use the final LSE and delta and accumulate into the same dQ and d(table).  Which segments
+    and which entry points: `route` (attention_route), executed here as it stands -- its tap segment is _TapAttn's."""
 
     @staticmethod
-    def forward(ctx, Qp, kv, key_a, key_b, Tt, geom: AttnGeom, split: int, feat=None, spos=None, Wkv=None, bkv=None,
+    def forward(ctx, Qp, kv, key_a, key_b, Tt, geom: AttnGeom, route: AttnRoute, feat=None, spos=None, Wkv=None, bkv=None,
                 drop=None):
         """kv (B', N, 2C) projected rows -- or None with the K | V SOURCE instead: feat (B', Hi, Wi, C) channels-last
         feature map (float or bf16), spos (B', N, 2) sampling positions, Wkv (2C, C), bkv (2C,) the proj_k | proj_v
@@ -625,13 +848,7 @@ class _AttnCore(torch.autograd.Function):
             N, C2 = kv.shape[1], kv.shape[-1]
         c = C2 // 2 // geom.heads
         dev = Qp.device
-        segs = []
-        if split > 0:
-            segs.append(_Seg(False, 0, dc_replace(geom, N=split)))
-        if split < N:
-            if ctx.drop:
-                raise _lib.BevrError("attention dropout runs on the region kernels: pass no cell segment")
-            segs.append(_Seg(True, split, dc_replace(geom, N=N - split)))
+        segs = [sg for sg in route.segments if sg.kind != "tap"]
         Ttc = Tt.contiguous()
         pair = torch.stack((Ttc[..., :-1], Ttc[..., 1:]), dim=-1).contiguous()   # (h, Wp, Hp, 2)
         # zeros: the rows past the grid are never written, and a merge with another segment multiplies them by weight 0
@@ -639,10 +856,10 @@ class _AttnCore(torch.autograd.Function):
         # plane 0: log2-sum-exp; plane 1: a bound of log2 of the row's largest softmax weight (rows past the grid: -inf here)
         LSE = torch.full((2, geom.n_prob, geom.heads, geom.Mp), float("-inf"), device=dev, dtype=torch.float32)
         need_bwd = any(ctx.needs_input_grad)
+        o = SimpleNamespace(Qe=Qe, pair=pair, Ttc=Ttc, O=O, LSE=LSE, drop=ctx.drop or ())
         saved = []
-        pair_pk = None
         for i, sg in enumerate(segs):
-            g = sg.geom
+            g = dc_replace(geom, N=sg.n1 - sg.n0)
             # K | V rows (B', N, 2 h c) float -> the kernels' per-head layouts in one pass (csrc/pack.hip); the
             # transposed K is only read by the backward.  A segment is a row range of the caller's array (row stride C2,
             # problem stride N rows): no copy.
@@ -655,69 +872,25 @@ class _AttnCore(torch.autograd.Function):
                 nb, Hi, Wi, Cc = feat.shape
                 # the largest squared K row norm per (problem, head), out of the projection kernel: the static softmax
                 # reference of the gather forward needs it (a pass over K otherwise)
-                if not sg.cell and not ctx.drop and gather_supported(g.precision, g.S) and os.environ.get("BEVR_KNORM", "1") != "0":
+                if route.kn2 and sg.kind == "region":
                     kn2 = torch.zeros(g.n_prob, g.heads, device=dev, dtype=torch.float32)
-                _lib.check(KERNEL_TIMER.run(
-                    "bevr_kv_project", 0.0, L.bevr_kv_project, _ptr(feat), int(feat.dtype == torch.bfloat16),
-                    C.c_void_p(spos.data_ptr() + sg.n0 * 8), N, _ptr(W_e), _ptr(b_f), nb, Hi, Wi, Cc, g.N, g.Np, g.heads, c,
-                    g.precision, _ptr(Ke), _ptr(Ve), _ptr(Kt), _ptr(Vt), _ptr(vn2) if need_bwd else None, _ptr(kn2),
-                    g.groups, _stream(),
-                    nbytes=float(feat.numel() * feat.element_size() + 8 * nb * g.N + (4 if need_bwd else 3) * Ke.numel() * 2)),
-                    "bevr_kv_project")
+                _launch("bevr_kv_project", _ptr(feat), int(feat.dtype == torch.bfloat16),
+                        C.c_void_p(spos.data_ptr() + sg.n0 * 8), N, _ptr(W_e), _ptr(b_f), nb, Hi, Wi, Cc, g.N, g.Np, g.heads, c,
+                        g.precision, _ptr(Ke), _ptr(Ve), _ptr(Kt), _ptr(Vt), _ptr(vn2) if need_bwd else None, _ptr(kn2),
+                        g.groups, _stream(), flops=0.0,
+                        nbytes=float(feat.numel() * feat.element_size() + 8 * nb * g.N + (4 if need_bwd else 3) * Ke.numel() * 2))
             else:
                 kp = kv.data_ptr() + sg.n0 * C2 * 4
-                _lib.check(L.bevr_pack_kv(C.c_void_p(kp), C.c_void_p(kp + 2 * C2), C2, N, g.n_prob, g.N, g.Np, g.heads, c,
-                                          g.precision, _ptr(Ke), _ptr(Ve), _ptr(Kt), _ptr(Vt), _stream()), "bevr_pack_kv")
-            ka = F.pad(key_a[:, sg.n0:sg.n0 + g.N], (0, g.Np - g.N)).contiguous()
-            kb = F.pad(key_b[:, sg.n0:sg.n0 + g.N], (0, g.Np - g.N)).contiguous()
+                _launch("bevr_pack_kv", C.c_void_p(kp), C.c_void_p(kp + 2 * C2), C2, N, g.n_prob, g.N, g.Np, g.heads, c,
+                        g.precision, _ptr(Ke), _ptr(Ve), _ptr(Kt), _ptr(Vt), _stream())
+            ka = F.pad(key_a[:, sg.n0:sg.n1], (0, g.Np - g.N)).contiguous()
+            kb = F.pad(key_b[:, sg.n0:sg.n1], (0, g.Np - g.N)).contiguous()
             d = g.desc()
             # per-key table coordinates + per-tile tap boxes, shared by the forward and the backward passes
             key_ws = torch.empty(L.bevr_attn_key_ws_bytes(C.byref(d)), device=dev, dtype=torch.uint8)
-            _lib.check(L.bevr_attn_key_prep(C.byref(d), _ptr(ka), _ptr(kb), _ptr(key_ws), _stream()), "bevr_attn_key_prep")
-            if sg.cell:
-                o_in = _ptr(O) if i > 0 else None
-                l_in = _ptr(LSE) if i > 0 else None
-                _lib.check(KERNEL_TIMER.run("bevr_attn_cell_fwd", _attn_flops(g, 2), L.bevr_attn_cell_fwd, C.byref(d),
-                                            _ptr(Qe), _ptr(Ke), _ptr(Vt), _ptr(key_ws), _ptr(pair), o_in, l_in, _ptr(O),
-                                            _ptr(LSE), _stream(), tag=_call_tag(g)), "bevr_attn_cell_fwd")
-            elif ctx.drop:
-                _lib.check(KERNEL_TIMER.run("bevr_attn_fwd_dropout", _attn_flops(g, 2), L.bevr_attn_fwd_dropout, C.byref(d),
-                                            _ptr(Qe), _ptr(Ke), _ptr(Vt), _ptr(key_ws), _ptr(pair), _ptr(O), _ptr(LSE),
-                                            ctx.drop[0], ctx.drop[1], _stream(), tag=_call_tag(g)), "bevr_attn_fwd_dropout")
-            elif gather_supported(g.precision, g.S):
-                if pair_pk is None:
-                    pair_pk = pair.to(ed)                   # (h, Wp, Hp, 2) 16-bit: one dword per (column, row) entry
-                    # Tt is the table in log2 units already; two-stage maximum (a reduction to `heads` outputs in one stage
-                    # runs on `heads` workgroups: 0.6 ms for the 27 MB table)
-                    tmax = torch.maximum(Ttc.amax(-1).amax(-1), -Ttc.amin(-1).amin(-1))
-                    qn = torch.linalg.vector_norm(Qe, dim=-1, dtype=torch.float32)          # (B, h, Mp)
-                # static softmax reference: |Q_q . K_n| <= ||Q_q|| max_n ||K_n||, |bias| <= max |T2| (a convex combination;
-                # 1 % for the 16-bit rounding of operands and weights), minus the headroom
-                if kn2 is not None:      # of the unrounded rows: the rounding is inside the 1 % below
-                    kmx = kn2.sqrt()
-                else:
-                    kmx = torch.linalg.vector_norm(Ke[:, :, :g.N], dim=-1, dtype=torch.float32).amax(-1)    # (B', h)
-                ub = 1.01 * (qn.repeat_interleave(g.q_div, 0) * kmx[..., None] + tmax[None, :, None]) + 0.01
-                mref = (ub - tap_headroom(g.precision)).contiguous()
-                bands = gather_bands(g.S)
-                # scratch of one call's two passes: zeroed per call (per band)
-                gflags = torch.zeros(len(bands), g.n_prob * g.heads * g.S, device=dev, dtype=torch.int32)
-                if len(bands) == 1:
-                    _lib.check(KERNEL_TIMER.run("bevr_attn_gather_fwd", _attn_flops(g, 2), L.bevr_attn_gather_fwd,
-                                                C.byref(d), _ptr(Qe), _ptr(Ke), _ptr(Ve), _ptr(key_ws), _ptr(pair_pk),
-                                                _ptr(mref), _ptr(O), _ptr(LSE), _ptr(gflags), _stream(),
-                                                tag=_call_tag(g)), "bevr_attn_gather_fwd")
-                else:       # (the timer's name is the route's, whichever entry point runs it)
-                    for bi, (r0, nr) in enumerate(bands):
-                        _lib.check(KERNEL_TIMER.run("bevr_attn_gather_fwd", _attn_flops(g, 2) * nr / g.S,
-                                                    L.bevr_attn_gather_fwd_rows, C.byref(d), _ptr(Qe), _ptr(Ke), _ptr(Ve),
-                                                    _ptr(key_ws), _ptr(pair_pk), _ptr(mref), _ptr(O), _ptr(LSE),
-                                                    _ptr(gflags[bi]), r0, nr, _stream(), tag=_call_tag(g)),
-                                   "bevr_attn_gather_fwd_rows")
-            else:
-                _lib.check(KERNEL_TIMER.run("bevr_attn_fwd", _attn_flops(g, 2), L.bevr_attn_fwd, C.byref(d), _ptr(Qe),
-                                            _ptr(Ke), _ptr(Vt), _ptr(key_ws), _ptr(pair), _ptr(O), _ptr(LSE),
-                                            _stream(), tag=_call_tag(g)), "bevr_attn_fwd")
+            _launch("bevr_attn_key_prep", C.byref(d), _ptr(ka), _ptr(kb), _ptr(key_ws), _stream())
+            o.__dict__.update(g=g, desc=d, Ke=Ke, Ve=Ve, Vt=Vt, key_ws=key_ws, kn2=kn2, chained=i > 0)
+            _run(sg.fwd, o)
             saved += [Ke, Ve, Kt, ka, kb, key_ws]
         ctx.geom = geom
         # split mode: the packed V is not readable as numbers; the norm bound of the backward's scales from the rows
@@ -742,7 +915,6 @@ class _AttnCore(torch.autograd.Function):
         if ctx.fused:
             src = saved[ctx.n_seg_saved:]
             saved = saved[:ctx.n_seg_saved]
-        L = _lib.lib()
         ed = _edtype(geom.precision)
         if dO is None:
             dO = torch.zeros_like(O)
@@ -769,9 +941,8 @@ class _AttnCore(torch.autograd.Function):
             pstats = torch.zeros(2, device=dev, dtype=torch.float32)
             dl_in = dLSE.float().contiguous() if dLSE is not None else None
             lse0 = LSE[0].contiguous() if dLSE is not None else None
-            _lib.check(L.bevr_attn_bwd_prep(_ptr(dO), _ptr(O), _ptr(sdo) if f16 else None, _ptr(dl_in), _ptr(lse0), _ptr(dOe),
-                                            _ptr(dOt_p), _ptr(delta), _ptr(pstats), geom.n_prob * geom.heads, geom.Mp,
-                                            geom.precision, _stream()), "bevr_attn_bwd_prep")
+            _launch("bevr_attn_bwd_prep", _ptr(dO), _ptr(O), _ptr(sdo) if f16 else None, _ptr(dl_in), _ptr(lse0), _ptr(dOe),
+                    _ptr(dOt_p), _ptr(delta), _ptr(pstats), geom.n_prob * geom.heads, geom.Mp, geom.precision, _stream())
             dOr = None
         else:
             if f16:
@@ -812,69 +983,24 @@ class _AttnCore(torch.autograd.Function):
             bound = (dOr.norm(dim=-1).max() * vmax + delta.abs().max()).clamp_min(1e-30)
         pmax_log2 = (LSE[1].max() + 0.05).clamp(-60.0, 0.0)
         gscale = backward_scales(bound, pmax_log2, f16, ctx.drop[0] if ctx.drop else 0)
+        o = SimpleNamespace(Qe=Qe, Qt=Qt, pair=pair, dOe=dOe, dOt=dOt, LSE=LSE, delta=delta, gscale=gscale, dQ=dQ, dT=dT,
+                            drop=ctx.drop or ())
         das, dbs = [], []
         for i, sg in enumerate(ctx.segs):
-            g = sg.geom
-            Ke, Ve, Kt, ka, kb, key_ws = saved[6 * i:6 * i + 6]
-            d = g.desc()
-            if sg.cell:
-                _lib.check(KERNEL_TIMER.run("bevr_attn_cell_bwd_q", _attn_flops(g, 3), L.bevr_attn_cell_bwd_q, C.byref(d),
-                                            _ptr(Qe), _ptr(Ke), _ptr(Kt), _ptr(Ve), _ptr(key_ws), _ptr(pair), _ptr(dOe),
-                                            _ptr(LSE), _ptr(delta), _ptr(gscale), _ptr(dQ), _ptr(dT), _stream(),
-                                            tag=_call_tag(g)), "bevr_attn_cell_bwd_q")
-            elif ctx.drop:
-                _lib.check(KERNEL_TIMER.run("bevr_attn_bwd_q_dropout", _attn_flops(g, 3), L.bevr_attn_bwd_q_dropout,
-                                            C.byref(d), _ptr(Qe), _ptr(Ke), _ptr(Kt), _ptr(Ve), _ptr(key_ws), _ptr(pair),
-                                            _ptr(dOe), _ptr(LSE), _ptr(delta), _ptr(gscale), _ptr(dQ), _ptr(dT),
-                                            ctx.drop[0], ctx.drop[1], _stream(), tag=_call_tag(g)), "bevr_attn_bwd_q_dropout")
-            elif slab_supported(g.precision, g.S, g.Wt):
-                # keys sorted by table column b per problem-group; K and V rows gathered into that order (softmax and its
-                # gradients do not depend on the order of the keys; dK / dV come from the key-side kernel in the caller's)
-                order = kb[:, :g.N].argsort(1)
-                hpg = g.heads // g.groups
-                idx = order.view(g.n_prob, g.groups, 1, g.N).expand(-1, -1, hpg, -1).reshape(g.n_prob, g.heads, g.N, 1)
-                idx = idx.expand(-1, -1, -1, HEAD_DIM)
-                Ks, Vs = Ke[:, :, :g.N].gather(2, idx), Ve[:, :, :g.N].gather(2, idx)
-                sws = torch.empty(L.bevr_attn_slab_ws_bytes(C.byref(d)), device=dev, dtype=torch.uint8)
-                _lib.check(L.bevr_attn_slab_prep(C.byref(d), _ptr(ka), _ptr(kb), _ptr(order.to(torch.int32).contiguous()),
-                                                 _ptr(sws), _stream()), "bevr_attn_slab_prep")
-                _lib.check(KERNEL_TIMER.run("bevr_attn_slab_bwd_q", _attn_flops(g, 3), L.bevr_attn_slab_bwd_q, C.byref(d),
-                                            _ptr(Qe), _ptr(Ks), _ptr(Vs), _ptr(sws), _ptr(pair), _ptr(dOe), _ptr(LSE),
-                                            _ptr(delta), _ptr(gscale), _ptr(dQ), _ptr(dT), _stream(),
-                                            tag=_call_tag(g)), "bevr_attn_slab_bwd_q")
-                del Ks, Vs, sws
-            else:
-                _lib.check(KERNEL_TIMER.run("bevr_attn_bwd_q", _attn_flops(g, 3), L.bevr_attn_bwd_q, C.byref(d), _ptr(Qe),
-                                            _ptr(Ke), _ptr(Kt), _ptr(Ve), _ptr(key_ws), _ptr(pair), _ptr(dOe),
-                                            _ptr(LSE), _ptr(delta), _ptr(gscale), _ptr(dQ), _ptr(dT), _stream(),
-                                            tag=_call_tag(g)), "bevr_attn_bwd_q")
-            del Kt
-            dK = torch.empty(g.n_prob, g.heads, g.Np, HEAD_DIM, device=dev, dtype=torch.float32)
-            dV = torch.empty_like(dK)
-            da = torch.zeros_like(ka)
-            db = torch.zeros_like(kb)
-            if sg.cell:
-                _lib.check(KERNEL_TIMER.run("bevr_attn_cell_bwd_k", _attn_flops(g, 4), L.bevr_attn_cell_bwd_k, C.byref(d),
-                                            _ptr(Qe), _ptr(Qt), _ptr(Ke), _ptr(Ve), _ptr(key_ws), _ptr(pair), _ptr(dOe),
-                                            _ptr(dOt), _ptr(LSE), _ptr(delta), _ptr(gscale), _ptr(dK), _ptr(dV),
-                                            _ptr(da), _ptr(db), _stream(), tag=_call_tag(g)), "bevr_attn_cell_bwd_k")
-            elif ctx.drop:
-                _lib.check(KERNEL_TIMER.run("bevr_attn_bwd_k_dropout", _attn_flops(g, 4), L.bevr_attn_bwd_k_dropout,
-                                            C.byref(d), _ptr(Qe), _ptr(Qt), _ptr(Ke), _ptr(Ve), _ptr(ka), _ptr(kb), _ptr(pair),
-                                            _ptr(dOe), _ptr(dOt), _ptr(LSE), _ptr(delta), _ptr(gscale), _ptr(dK), _ptr(dV),
-                                            _ptr(da), _ptr(db), ctx.drop[0], ctx.drop[1], _stream(),
-                                            tag=_call_tag(g)), "bevr_attn_bwd_k_dropout")
-            else:
-                _lib.check(KERNEL_TIMER.run("bevr_attn_bwd_k", _attn_flops(g, 4), L.bevr_attn_bwd_k, C.byref(d), _ptr(Qe),
-                                            _ptr(Qt), _ptr(Ke), _ptr(Ve), _ptr(ka), _ptr(kb), _ptr(pair), _ptr(dOe),
-                                            _ptr(dOt), _ptr(LSE), _ptr(delta), _ptr(gscale), _ptr(dK), _ptr(dV),
-                                            _ptr(da), _ptr(db), _stream(), tag=_call_tag(g)), "bevr_attn_bwd_k")
+            g = dc_replace(geom, N=sg.n1 - sg.n0)
+            o.Ke, o.Ve, o.Kt, o.ka, o.kb, o.key_ws = saved[6 * i:6 * i + 6]
+            o.g, o.desc = g, g.desc()
+            _run(sg.bwd_q, o)
+            o.dK = torch.empty(g.n_prob, g.heads, g.Np, HEAD_DIM, device=dev, dtype=torch.float32)
+            o.dV = torch.empty_like(o.dK)
+            o.da, o.db = torch.zeros_like(o.ka), torch.zeros_like(o.kb)
+            _run(sg.bwd_k, o)
             # gradients of the row layout back to K | V rows (the adjoint of the packing), into the segment's rows
             kp = dkv.data_ptr() + sg.n0 * C2 * 4
-            _lib.check(L.bevr_unpack_dkv(_ptr(dK), _ptr(dV), C.c_void_p(kp), C.c_void_p(kp + 2 * C2), C2, N, g.n_prob,
-                                         g.N, g.Np, g.heads, C2 // 2 // g.heads, _stream()), "bevr_unpack_dkv")
-            das.append(da[:, :g.N])
-            dbs.append(db[:, :g.N])
+            _launch("bevr_unpack_dkv", _ptr(o.dK), _ptr(o.dV), C.c_void_p(kp), C.c_void_p(kp + 2 * C2), C2, N, g.n_prob,
+                    g.N, g.Np, g.heads, C2 // 2 // g.heads, _stream())
+            das.append(o.da[:, :g.N])
+            dbs.append(o.db[:, :g.N])
         if geom.q_div > 1:  # the views of one sample share the query: sum their query gradients
             dQ = dQ.reshape(geom.n_prob // geom.q_div, geom.q_div, geom.heads, geom.Mp, HEAD_DIM).sum(1)
         da = das[0] if len(das) == 1 else torch.cat(das, 1)
@@ -884,33 +1010,8 @@ class _AttnCore(torch.autograd.Function):
             dQ, dkv, da, db, dT = dQ * inv, dkv * inv, da * inv, db * inv, dT * inv
         if not ctx.fused:
             return dQ, dkv, da, db, dT, None, None, None, None, None, None, None
-        # adjoint of the fused K | V source in its unfused form: the projection's GEMMs on the float samples (recomputed:
-        # the forward never wrote them) and the sampler's scatter
-        feat, spos, Wkv = src[0], src[1], src[2]
-        G = geom.groups
-        if G > 1:
-            # group gi's channels sampled at group gi's positions: the map as B' G images of C / G channels (a copy of the
-            # feature map: small next to the rows), the rows back to (B', N, C)
-            nb, Hi, Wi, Cc = feat.shape
-            fg = feat.reshape(nb, Hi, Wi, G, Cc // G).permute(0, 3, 1, 2, 4).reshape(nb * G, Hi, Wi, Cc // G).contiguous()
-            xs = _Sample.sample(fg, spos).reshape(nb, G, -1, Cc // G).permute(0, 2, 1, 3).reshape(nb, -1, Cc)
-            d2 = dkv.reshape(-1, dkv.shape[-1])
-            dW = torch.bmm(dkv.transpose(1, 2), xs).sum(0) if ctx.needs_input_grad[9] else None
-            dbias = d2.sum(0) if ctx.has_bias and ctx.needs_input_grad[10] else None
-            dxs = (d2 @ Wkv.float()).reshape(nb, -1, G, Cc // G).permute(0, 2, 1, 3).reshape(nb * G, -1, Cc // G).contiguous()
-            del xs
-            dfg, dspos = _Sample.scatter(fg, spos, dxs, ctx.needs_input_grad[7])
-            dfeat = None if dfg is None else dfg.reshape(nb, G, Hi, Wi, Cc // G).permute(0, 2, 3, 1, 4).reshape(feat.shape)
-            return dQ, None, da, db, dT, None, None, dfeat, dspos, dW, dbias, None
-        xs = _Sample.sample(feat, spos)                                              # (B', N, C) float
-        d2 = dkv.reshape(-1, dkv.shape[-1])
-        # the weight gradient as one GEMM per problem, summed: rocBLAS runs the single (2C x B'N) @ (B'N x C) product with
-        # its 1.7 M-long contraction at 2.2 ms per SCA call, the batched form at 0.57 (tools/prof_kv_adjoint.py)
-        dW = torch.bmm(dkv.transpose(1, 2), xs).sum(0) if ctx.needs_input_grad[9] else None
-        dbias = d2.sum(0) if ctx.has_bias and ctx.needs_input_grad[10] else None
-        dxs = (d2 @ Wkv.float()).reshape(xs.shape)
-        del xs
-        dfeat, dspos = _Sample.scatter(feat, spos, dxs, ctx.needs_input_grad[7])
+        dfeat, dspos, dW, dbias = _kv_source_adjoint(dkv, src[0], src[1], src[2], geom.groups, ctx.needs_input_grad[7],
+                                                     ctx.needs_input_grad[9], ctx.has_bias and ctx.needs_input_grad[10])
         return dQ, None, da, db, dT, None, None, dfeat, dspos, dW, dbias, None
 
 
@@ -965,17 +1066,11 @@ def attention_core(query: torch.Tensor, kproj: Optional[torch.Tensor], vproj: Op
         if not 0 < thr < 65536:
             raise ValueError("attention dropout probability must lie in (0, 1)")
         drop = (thr, int(attn_drop[1]) & 0xFFFFFFFF)
-        if tap_pix is not None:
-            raise ValueError("tap_pix has no attention dropout: pass every key's projected rows and no tap segment")
-        if not (tap_source and cell_split is not None and kv_source is not None
-                and tap_supported(precision, groups, dropout=True) and 16 * ((S + 15) // 16) <= 448):
-            cell_split, tap_source = None, None
+    # ---- the arguments: one source, its shapes ----
     if kv_source is not None:
         if kv is not None or kproj is not None or vproj is not None:
             raise ValueError("pass kv_source alone")
-        feat, Wkv, bkv = kv_source
-        if not kv_source_supported(Cc, heads, groups, precision):
-            raise ValueError("kv_source needs a 16-bit operand mode, C % 16 == 0 and (C / groups) % 4 == 0")
+        source, (feat, Wkv, bkv) = "kv_source", kv_source
         Bp, N = feat.shape[0], pos.shape[1]
         if pos.shape[0] != Bp * groups or feat.shape[-1] != Cc or tuple(Wkv.shape) != (2 * Cc, Cc):
             raise ValueError("kv_source shapes: feat (B*views, Hi, Wi, C), pos (B*views*groups, N, 2), Wkv (2C, C)")
@@ -987,6 +1082,7 @@ def attention_core(query: torch.Tensor, kproj: Optional[torch.Tensor], vproj: Op
         Bp, N, C2 = kv.shape
         if C2 != 2 * Cc:
             raise ValueError(f"K | V rows must have 2 x {Cc} channels, got {C2}")
+        source = "kv" if tap_pix is None else "tap_pix"
         if tap_pix is not None:
             if not tap_source or cell_split is None or N != int(cell_split) or pos.shape[0] != Bp:
                 raise ValueError("tap_pix needs tap_source, cell_split and the projected rows of the keys [0, cell_split) alone")
@@ -994,54 +1090,36 @@ def attention_core(query: torch.Tensor, kproj: Optional[torch.Tensor], vproj: Op
             feat, Wkv, bkv = tap_pix
             if feat.shape[0] != Bp or feat.shape[-1] != Cc or tuple(Wkv.shape) != (2 * Cc, Cc):
                 raise ValueError("tap_pix shapes: feat (B*views, Hi, Wi, C), Wkv (2C, C), bkv (2C,)")
-    c = Cc // heads
-    split = N if cell_split is None else int(cell_split)
-    if not 0 <= split <= N:
-        raise ValueError("cell_split must lie in [0, N]")
     Wt = rpe_table.shape[-1]
     if rpe_table.shape[-2] != 2 * S - 1:
         raise ValueError("rpe_table height must be 2S-1")
-    if drop is not None and tap_source and tap_source != "pinned" and split < N:
-        ok = split > 0          # no region segment beside it: the route dropout always took for such a call
-        if ok:
-            ky = (pos[:, split:, 0].float() + 1.0) * (0.5 * (feat.shape[1] - 1))
-            kx = (pos[:, split:, 1].float() + 1.0) * (0.5 * (feat.shape[2] - 1))
-            ok = bool(((ky < TAP_R - 1) & (kx < TAP_C - 1)).all())      # csrc/attn_tap_prep.hip: the tap contract
-        if not ok:
-            tap_source, split = None, N
-    tap = bool(tap_source) and split < N
-    if tap and ((kv_source is None and tap_pix is None) or not tap_supported(precision, groups, dropout=drop is not None)
-                or 16 * ((S + 15) // 16) > 448):
-        raise ValueError("tap_source needs kv_source or tap_pix, groups == 1, a precision tap_supported accepts and S <= 448")
-    if tap_pix is not None and not tap:
-        raise ValueError("tap_pix needs a tap segment: 0 <= cell_split < N")
-    geom = AttnGeom(n_prob=Bp, q_div=views, heads=heads, groups=groups, S=S, N=split if tap else N, Wt=Wt, precision=precision)
-    f32_layout = precision in (_lib.PREC_F32, _lib.PREC_BF16X3)
-    if not tap and split < N and (geom.Sp > 480 or (f32_layout and geom.Sp > 224) or (N - split) > 8 * 100 * 1024):
-        # the cell kernels run one wave per 32-row block of a BEV column + a producer wave, 16 at most; with f32-sized
-        # operands the 512-thread instantiation (the one without spills) ends at 7 row blocks + the producer; and the slow
-        # pass lists a segment's tiles in LDS (4 bytes per 32 keys next to the staging buffers): a segment beyond
-        # ~800 000 keys would not fit.  Such calls keep every key on the region kernels (any split is a valid result)
-        split = N
+
+    def keys_in_tap_grid(split):        # csrc/attn_tap_prep.hip: the tap contract; one reduction and a host sync
+        ky = (pos[:, split:, 0].float() + 1.0) * (0.5 * (feat.shape[1] - 1))
+        kx = (pos[:, split:, 1].float() + 1.0) * (0.5 * (feat.shape[2] - 1))
+        return bool(((ky < TAP_R - 1) & (kx < TAP_C - 1)).all())
+    route = attention_route(precision, groups, S, Wt, N, cell_split, tap_source, drop is not None, source, Cc, heads,
+                            keys_in_tap_grid)
+    c = Cc // heads
+    n = route.n_core            # keys [0, n): region / cell kernels; keys [n, N): tap kernels (n == N: none)
+    geom = AttnGeom(n_prob=Bp, q_div=views, heads=heads, groups=groups, S=S, N=n, Wt=Wt, precision=precision)
     Qp = pack_query(query.float(), heads)
     a, b = key_coords(pos.float(), S, Wt, N)
     Tt = pack_table(rpe_table.float(), geom)
-    if not tap:
-        if kv_source is not None:
-            O, _ = _AttnCore.apply(Qp, None, a, b, Tt, geom, split, feat, pos.float(), Wkv, bkv, drop)
+    O_r = LSE_r = None
+    if n > 0:
+        a_r, b_r = (a, b) if n == N else (a[:, :n], b[:, :n])
+        if source == "kv_source":
+            spos = pos.float() if n == N else pos[:, :n].float().contiguous()
+            O_r, LSE_r = _AttnCore.apply(Qp, None, a_r, b_r, Tt, geom, route, feat, spos, Wkv, bkv, drop)
         else:
-            O, _ = _AttnCore.apply(Qp, kv.float(), a, b, Tt, geom, split, None, None, None, None, drop)
-        return _unpacked(O, S, c, views, concat_views)
+            O_r, LSE_r = _AttnCore.apply(Qp, kv.float(), a_r, b_r, Tt, geom, route, None, None, None, None, drop)
+    if not route.tap:
+        return _unpacked(O_r, S, c, views, concat_views)
 
-    # ---- keys [0, split): region kernels; keys [split, N): tap kernels; one softmax, merged through (O, LSE) ----
+    # ---- keys [0, n): region kernels; keys [n, N): tap kernels; one softmax, merged through (O, LSE) ----
     V = views
     Hi, Wi = feat.shape[1], feat.shape[2]
-    O_r = LSE_r = None
-    if split > 0 and tap_pix is not None:
-        O_r, LSE_r = _AttnCore.apply(Qp, kv.float(), a[:, :split], b[:, :split], Tt, geom, split, None, None, None, None, None)
-    elif split > 0:
-        O_r, LSE_r = _AttnCore.apply(Qp, None, a[:, :split], b[:, :split], Tt, geom, split, feat,
-                                     pos[:, :split].float().contiguous(), Wkv, bkv, drop)
     # the 12 pixels' K | V rows, without the bias: (B', 12, 2C); rows the image does not have are zero (zero padding)
     fpix = feat[:, :TAP_R, :TAP_C, :].float()
     fpix = F.pad(fpix, (0, 0, 0, TAP_C - fpix.shape[2], 0, TAP_R - fpix.shape[1])).reshape(Bp, TAP_N, Cc)
@@ -1051,29 +1129,19 @@ def attention_core(query: torch.Tensor, kproj: Optional[torch.Tensor], vproj: Op
     Kp = F.pad(kvp[..., :Cc].reshape(B, V, TAP_N, heads, c), (0, pad_c)).permute(0, 3, 4, 1, 2).reshape(B, heads, HEAD_DIM, V * TAP_N)
     G = torch.matmul(Qp, Kp).reshape(B, heads, geom.Mp, V, TAP_N).permute(0, 3, 1, 2, 4).reshape(Bp, heads, geom.Mp, TAP_N)
     Gb = torch.matmul(Qp[..., :c], bkv[:Cc].float().reshape(heads, c, 1)).squeeze(-1)                # (B, h, Mp)
-    tgeom = dc_replace(geom, N=N - split)
-    key_y = (pos[:, split:, 0].float() + 1.0) * (0.5 * (Hi - 1))
-    key_x = (pos[:, split:, 1].float() + 1.0) * (0.5 * (Wi - 1))
-    mass = None
-    if drop is not None:
-        # dropout acts on P after the softmax and Rn is linear in P: Rn' = sum_n keep D P w, the kept mass m' = sum_n keep D P
-        # (1 without dropout) multiplies bv, LSE is of all keys.  One mask for the whole call: the tap keys hash n = split + n'
-        Rn, mass, LSE_c = _TapAttn.apply(G, a[:, split:], b[:, split:], key_y, key_x, Tt, tgeom, (drop[0], drop[1], split))
-    else:
-        Rn, LSE_c = _TapAttn.apply(G, a[:, split:], b[:, split:], key_y, key_x, Tt, tgeom)
+    key_y = (pos[:, n:, 0].float() + 1.0) * (0.5 * (Hi - 1))
+    key_x = (pos[:, n:, 1].float() + 1.0) * (0.5 * (Wi - 1))
+    # dropout acts on P after the softmax and Rn is linear in P: Rn' = sum_n keep D P w, the kept mass m' = sum_n keep D P
+    # (1 without dropout) multiplies bv, LSE is of all keys.  One mask for the whole call: the tap keys hash n = split + n'
+    Rn, *mass, LSE_c = _TapAttn.apply(G, a[:, n:], b[:, n:], key_y, key_x, Tt, dc_replace(geom, N=N - n), route.segments[-1],
+                                      drop and (drop[0], drop[1], n))
     LSE_c = (LSE_c.reshape(B, V, heads, geom.Mp) + Gb[:, None]).reshape(Bp, heads, geom.Mp)
     Vp = F.pad(kvp[..., Cc:].reshape(Bp, TAP_N, heads, c), (0, pad_c)).permute(0, 2, 1, 3)          # (B', h, 12, 32)
     bv = F.pad(bkv[Cc:].float().reshape(1, heads, 1, c), (0, pad_c))
-    if mass is not None:
-        # (the fused merge_tap assumes a mass of 1)
-        O_c = torch.matmul(Rn, Vp) + mass[..., None] * bv
-        if O_r is None:
-            return _unpacked(O_c, S, c, views, concat_views)
-        return _unpacked(O_r, S, c, views, concat_views, LSE_r, O_c, LSE_c)
-    if O_r is not None and c % 4 == 0 and os.environ.get("BEVR_MERGE_TAP", "1") != "0":
+    if route.merge == "merge_tap":
         # the two halves of the softmax merged and unpacked in one pass, the tap half's O = Rn Vpix + bv formed on the way
         return merge_tap(O_r, LSE_r, Rn, LSE_c, Vp, bv.reshape(heads, HEAD_DIM), S, c, views if concat_views else 1)
-    O_c = torch.matmul(Rn, Vp) + bv
+    O_c = torch.matmul(Rn, Vp) + (mass[0][..., None] * bv if mass else bv)
     if O_r is None:
         return _unpacked(O_c, S, c, views, concat_views)
     # the two halves of the softmax merged and unpacked in one pass (csrc/merge.hip)
@@ -1109,44 +1177,53 @@ def _neg_big(ed):
     return -1.0e30 if ed == torch.bfloat16 else -30000.0
 
 
-def _set_offset(G16: torch.Tensor, c: torch.Tensor) -> torch.Tensor:
-    """slots 12, 13 of the packed operand <- hi, lo 16-bit parts of the row offset c; returns hi + lo (float): what the
-    kernels add to the row's logits."""
-    hi = c.to(G16.dtype)
-    lo = (c - hi.float()).to(G16.dtype)
-    G16[..., 12] = hi
-    G16[..., 13] = lo
-    return hi.float() + lo.float()
-
-
-def _set_offset_x3(planes: torch.Tensor, c: torch.Tensor) -> torch.Tensor:
-    """Split mode (include/bevrender_hip.h, "TAP entry points in BEVR_PREC_BF16X3"): slots 12, 13 of the (hi, lo) planes <-
-    the four bf16 parts of the row offset c, slot 12 = (p0, p1), slot 13 = (p2, p3); returns their sum (float): what the
-    kernels add to the row's logits."""
-    r = c.float()
-    parts = []
-    for _ in range(4):
-        p = r.to(torch.bfloat16)
-        parts.append(p)
+def _set_offset(op: torch.Tensor, c: torch.Tensor, x3: bool = False) -> torch.Tensor:
+    """slots 12, 13 of a G / H operand (_tap_operand) <- the row offset c in 16-bit parts; returns their sum (float): what
+    the kernels add to the row's logits.  The 16-bit pack: hi, lo in slots 12, 13.  Split mode (include/bevrender_hip.h,
+    "TAP entry points in BEVR_PREC_BF16X3"): four bf16 parts over the (hi, lo) planes, slot 12 = (p0, p1), slot 13 = (p2, p3)."""
+    dst = [(op[0], 12), (op[1], 12), (op[0], 13), (op[1], 13)] if x3 else [(op, 12), (op, 13)]
+    r, parts = c.float(), []
+    for t, slot in dst:
+        p = r.to(op.dtype)
+        t[..., slot] = p
+        parts.append(p.float())
         r = r - p.float()
-    planes[0][..., 12], planes[1][..., 12] = parts[0], parts[1]
-    planes[0][..., 13], planes[1][..., 13] = parts[2], parts[3]
-    return ((parts[3].float() + parts[2].float()) + parts[1].float()) + parts[0].float()
+    total = parts.pop()
+    while parts:            # the smallest parts first
+        total = total + parts.pop()
+    return total
+
+
+def _tap_operand(rows: torch.Tensor, x3: bool, ed=torch.bfloat16, dead: float = 0.0, slot15=None):
+    """The G / H operand of the tap entry points from rows (..., 12) float, in either format: the 16-bit pack (..., 16) of
+    dtype ed, or (x3) the split planes (2, ..., 16) bf16, plane 0 = hi = bf16(x), plane 1 = lo = bf16(x - hi).  Slots 0..11
+    the rows, 12 and 13 the row offset (zero here: _set_offset), slot 14 = dead (-1e30 for G, the logit of a masked key),
+    slot 15 = slot15 (H with dropout: the kept mass's cotangent) or zero.  Returns (operand, the rows as the kernels
+    contract them: rounded, or hi + lo)."""
+    rows = rows.float()
+    shape = tuple(rows.shape[:-1]) + (TAP_SLOTS,)
+    if x3:
+        op = torch.zeros((2,) + shape, device=rows.device, dtype=torch.bfloat16)
+        hi = rows.to(torch.bfloat16)
+        op[0][..., :TAP_N] = hi
+        op[1][..., :TAP_N] = (rows - hi.float()).to(torch.bfloat16)
+        main = op[0]
+    else:
+        main = op = torch.zeros(shape, device=rows.device, dtype=ed)
+        op[..., :TAP_N] = rows
+    main[..., 14] = dead
+    if slot15 is not None:
+        main[..., 15] = slot15
+    return op, (op[0][..., :TAP_N].float() + op[1][..., :TAP_N].float() if x3 else op[..., :TAP_N].float())
 
 
 def tap_split_rows(rows: torch.Tensor, c: Optional[torch.Tensor] = None, dead: float = 0.0):
     """The G / H operand of the tap entry points in BEVR_PREC_BF16X3, as include/bevrender_hip.h words it: rows (..., 12)
     float -> planes (2, ..., 16) bf16, plane 0 = hi = bf16(x), plane 1 = lo = bf16(x - hi) in slots 0..11; the row offset
-    c (...) in four bf16 parts in slots 12, 13 (_set_offset_x3; c = None: zero); slot 14 = (dead, 0) -- -1e30 for G, the
+    c (...) in four bf16 parts in slots 12, 13 (_set_offset; c = None: zero); slot 14 = (dead, 0) -- -1e30 for G, the
     logit of a masked key; slot 15 zero.  Returns (planes, c as the kernels add it).  Plain torch: runs on any device."""
-    rows = rows.float()
-    planes = torch.zeros((2,) + tuple(rows.shape[:-1]) + (TAP_SLOTS,), device=rows.device, dtype=torch.bfloat16)
-    hi = rows.to(torch.bfloat16)
-    planes[0][..., :TAP_N] = hi
-    planes[1][..., :TAP_N] = (rows - hi.float()).to(torch.bfloat16)
-    planes[0][..., 14] = dead
-    c_eff = None if c is None else _set_offset_x3(planes, c)
-    return planes, c_eff
+    planes, _ = _tap_operand(rows, True, dead=dead)
+    return planes, None if c is None else _set_offset(planes, c, True)
 
 
 class _TapAttn(torch.autograd.Function):
@@ -1156,7 +1233,8 @@ class _TapAttn(torch.autograd.Function):
         LSE[q]   = log2 sum_n 2^S[n][q]                 (P, h, Mp)
     Both outputs are differentiable (the caller turns Rn into O = Rn Vpix + bv and merges LSE with the other key segment
     of the same softmax in plain torch code).  G (P, h, Mp, 12) float: log2-domain logit per tap; key_a, key_b (P, N)
-    table coordinates, key_y, key_x (P, N) sampling positions in feature pixels; Tt the packed table (pack_table).
+    table coordinates, key_y, key_x (P, N) sampling positions in feature pixels; Tt the packed table (pack_table); seg the
+    route's tap segment (attention_route: its entry points).
     drop = (thr16, seed, key0): attention dropout (the tap dropout kernels; the mask is dropout_keep_mask's at key index
     key0 + n).  Three outputs then, all differentiable, with D = 65536 / (65536 - thr16):
         Rn'[q][t] = sum_n keep D softmax_n(S)[n][q] w_t(n),   m'[q] = sum_n keep D softmax_n(S)[n][q]   (P, h, Mp),
@@ -1164,7 +1242,7 @@ class _TapAttn(torch.autograd.Function):
     and the caller's output is O = Rn' Vpix + m' bv."""
 
     @staticmethod
-    def forward(ctx, G, key_a, key_b, key_y, key_x, Tt, geom: AttnGeom, drop=None):
+    def forward(ctx, G, key_a, key_b, key_y, key_x, Tt, geom: AttnGeom, seg: KeySegment, drop=None):
         _require_gpu(G, key_a, key_b, key_y, key_x, Tt)
         L = _lib.lib()
         ed = _edtype(geom.precision)
@@ -1174,144 +1252,94 @@ class _TapAttn(torch.autograd.Function):
         pad = geom.Np - geom.N
         ka, kb, ky, kx = (F.pad(t.float(), (0, pad)).contiguous() for t in (key_a, key_b, key_y, key_x))
         ws = torch.empty(L.bevr_attn_tap_ws_bytes(C.byref(d)), device=dev, dtype=torch.uint8)
-        _lib.check(L.bevr_attn_tap_prep(C.byref(d), _ptr(ka), _ptr(kb), _ptr(ky), _ptr(kx), _ptr(ws), _stream()),
-                   "bevr_attn_tap_prep")
+        _launch("bevr_attn_tap_prep", C.byref(d), _ptr(ka), _ptr(kb), _ptr(ky), _ptr(kx), _ptr(ws), _stream())
         Ttc = Tt.contiguous()
         pair = torch.stack((Ttc[..., :-1], Ttc[..., 1:]), dim=-1).contiguous()
         x3 = geom.precision == _lib.PREC_BF16X3
         # static softmax reference: an upper bound of the row's logits (the tap weights and the 4 bias taps are convex
         # weights up to their 16-bit rounding) minus the headroom -- no weight can overflow, nothing is tracked in the loop
-        tmax = Ttc.amax(-1).amax(-1).clamp_min(0.0)       # two stages: see _AttnCore.forward
-        if x3:
-            # split mode: (hi, lo) planes of the float rows, the offset in four parts (tap_split_rows)
-            ub = 1.01 * (G.float().amax(-1).clamp_min(0.0) + tmax[None, :, None]) + 0.01
-            G16, c_eff = tap_split_rows(G, tap_headroom(geom.precision) - ub, _neg_big(torch.bfloat16))
-            mref = (-c_eff).contiguous()
-        else:
-            G16 = torch.zeros(P, h, Mp, TAP_SLOTS, device=dev, dtype=ed)
-            G16[..., :TAP_N] = G
-            G16[..., 14] = _neg_big(ed)
-            ub = 1.01 * (G16[..., :TAP_N].float().amax(-1).clamp_min(0.0) + tmax[None, :, None]) + 0.01
-            mref = (-_set_offset(G16, tap_headroom(geom.precision) - ub)).contiguous()
+        tmax = Ttc.amax(-1).amax(-1).clamp_min(0.0)       # two stages: see _fwd_gather
+        G16, Gv = _tap_operand(G, x3, ed, _neg_big(torch.bfloat16 if x3 else ed))
+        # (the bound is taken of the rounded rows in the 16-bit pack, of the float rows themselves in split mode)
+        ub = 1.01 * ((G.float() if x3 else Gv).amax(-1).clamp_min(0.0) + tmax[None, :, None]) + 0.01
+        mref = (-_set_offset(G16, tap_headroom(geom.precision) - ub, x3)).contiguous()
         # zeros: the kernels work in 16-row blocks and never touch the rows past the last block of a column
         R = torch.zeros(P, h, Mp, TAP_SLOTS, device=dev, dtype=torch.float32)
         flags = torch.zeros(P * h, geom.S, device=dev, dtype=torch.int32)
         ctx.drop = drop if drop and drop[0] > 0 else None
         valid = (torch.arange(Mp, device=dev) % geom.Sp) < geom.S
-        if ctx.drop:
-            thr, seed, key0 = ctx.drop
-            lsum = torch.zeros(P, h, Mp, device=dev, dtype=torch.float32)
-            _lib.check(KERNEL_TIMER.run("bevr_attn_tap_fwd_dropout", _attn_flops(geom, 2), L.bevr_attn_tap_fwd_dropout,
-                                        C.byref(d), _ptr(G16), _ptr(ws), _ptr(pair), _ptr(mref), _ptr(R), _ptr(lsum),
-                                        _ptr(flags), key0, thr, seed, _stream(), tag=_call_tag(geom)),
-                       "bevr_attn_tap_fwd_dropout")
-            # R holds the kept weights (slot 15: the kept mass), lsum the row sum of all of them
-            l = torch.where(valid, lsum, torch.ones_like(mref))
-            LSE = torch.where(valid, mref + torch.log2(l), torch.zeros_like(mref))
-            sc = torch.where(valid, (65536.0 / (65536.0 - thr)) / l, torch.zeros_like(l))
-            Rn = R[..., :TAP_N] * sc[..., None]
-            mass = R[..., 15] * sc
-            ctx.geom = geom
-            ctx.save_for_backward(G16, Rn, LSE, ws, pair, Ttc, mass)
-            ctx.set_materialize_grads(False)
-            return Rn, mass, LSE
-        _lib.check(KERNEL_TIMER.run("bevr_attn_tap_fwd", _attn_flops(geom, 2), L.bevr_attn_tap_fwd, C.byref(d), _ptr(G16),
-                                    _ptr(ws), _ptr(pair), _ptr(mref), _ptr(R), _ptr(flags), _stream(), tag=_call_tag(geom)), "bevr_attn_tap_fwd")
+        # with a keep mask R holds the kept weights (slot 15: the kept mass) and lsum the row sum of all of them;
+        # without, slot 15 is that row sum
+        lsum = torch.zeros(P, h, Mp, device=dev, dtype=torch.float32) if ctx.drop else None
+        thr, seed, key0 = ctx.drop or (0, 0, 0)
+        _run(seg.fwd, SimpleNamespace(g=geom, desc=d, G16=G16, ws=ws, pair=pair, mref=mref, R=R, flags=flags,
+                                      lsum=(_ptr(lsum),) if ctx.drop else (), drop=(key0, thr, seed) if ctx.drop else ()))
         # rows past the grid: Rn = 0, LSE = 0 (finite: the caller's merge with the other key segment stays finite there)
-        l = torch.where(valid, R[..., 15], torch.ones_like(mref))
+        l = torch.where(valid, lsum if ctx.drop else R[..., 15], torch.ones_like(mref))
         LSE = torch.where(valid, mref + torch.log2(l), torch.zeros_like(mref))
-        Rn = torch.where(valid[:, None], R[..., :TAP_N] / l[..., None], torch.zeros_like(R[..., :TAP_N]))
-        ctx.geom = geom
-        ctx.save_for_backward(G16, Rn, LSE, ws, pair, Ttc)
+        if ctx.drop:
+            sc = torch.where(valid, (65536.0 / (65536.0 - thr)) / l, torch.zeros_like(l))
+            outs = (R[..., :TAP_N] * sc[..., None], R[..., 15] * sc, LSE)           # Rn', m', LSE
+        else:
+            outs = (torch.where(valid[:, None], R[..., :TAP_N] / l[..., None], torch.zeros_like(R[..., :TAP_N])), LSE)
+        ctx.geom, ctx.seg = geom, seg
+        ctx.save_for_backward(G16, outs[0], LSE, ws, pair, Ttc, *outs[1:-1])
         ctx.set_materialize_grads(False)
-        return Rn, LSE
+        return outs
 
     @staticmethod
     def backward(ctx, dRn, *rest):
         geom: AttnGeom = ctx.geom
         drop = ctx.drop
         dmass, dLSE = rest if drop else (None, rest[0])
-        G16, Rn, LSE, ws, pair, Ttc, *more = ctx.saved_tensors
+        G16, Rn, LSE, ws, pair, Ttc, *mass = ctx.saved_tensors
         # dropout: the kernels take D = 65536 / (65536 - thr) folded into H
         Dk = 65536.0 / (65536.0 - drop[0]) if drop else 1.0
-        L = _lib.lib()
         ed = G16.dtype
         dev = G16.device
         P, h, Mp = geom.n_prob, geom.heads, geom.Mp
-        d = geom.desc()
         valid = (torch.arange(Mp, device=dev) % geom.Sp) < geom.S
         x3 = geom.precision == _lib.PREC_BF16X3
-        H16 = None if x3 else torch.zeros(P, h, Mp, TAP_SLOTS, device=dev, dtype=ed)
         sdo = None
         if ed == torch.float16:
             # fp16 has 5 exponent bits and the reference trains without a loss scaler: the cotangents of a mean-type loss
             # (~1e-7 per element) would fall into fp16's subnormals as the H operand.  Every output is linear in
             # (dRn, dLSE): both are brought to ~2^8 with a power of two (exact) and the gradients scaled back.  No sync.
             big = torch.zeros((), device=dev)
-            if dRn is not None:
-                big = torch.maximum(big, dRn.abs().max())
-            if dLSE is not None:
-                big = torch.maximum(big, dLSE.abs().max())
-            if dmass is not None:
-                big = torch.maximum(big, dmass.abs().max())
+            for t in (dRn, dLSE, dmass):
+                if t is not None:
+                    big = torch.maximum(big, t.abs().max())
             # (dropout: the H operand carries D times the cotangent -- ceil(log2 D) binades of the room go to it)
             sdo = torch.exp2(torch.floor(8.0 - torch.log2(big.clamp_min(1e-30))) - math.ceil(math.log2(Dk)))
-            dRn = None if dRn is None else dRn * sdo
-            dLSE = None if dLSE is None else dLSE * sdo
-            dmass = None if dmass is None else dmass * sdo
-        if x3:
-            # split mode (no dropout here): the planes first, delta from hi + lo -- the H values the kernel contracts
-            H16, _ = tap_split_rows(torch.zeros_like(Rn) if dRn is None else dRn * LN2)
-            delta = (Rn * (H16[0][..., :TAP_N].float() + H16[1][..., :TAP_N].float())).sum(-1)
-            if dLSE is not None:
-                delta = delta - dLSE
-            _set_offset_x3(H16, -delta)
-            Gq = G16.clone()
-            _set_offset_x3(Gq, torch.where(valid, -LSE, torch.full_like(LSE, _neg_big(ed))))
-            return _TapAttn._backward_launch(geom, d, L, drop, Gq, H16, ws, pair, Ttc, valid, sdo)
-        if dRn is not None:
-            H16[..., :TAP_N] = dRn * (LN2 * Dk)
-        if dmass is not None:
-            H16[..., 15] = dmass * (LN2 * Dk)     # the cotangent of the kept mass: the droppable part of the constant
-        # delta from the values the kernel contracts (the rounded H): dS = P (dP - delta) then cancels where P -> 1
-        delta = (Rn * H16[..., :TAP_N].float()).sum(-1)
+            dRn, dLSE, dmass = (None if t is None else t * sdo for t in (dRn, dLSE, dmass))
+        # slot 15: the cotangent of the kept mass, the droppable part of the constant (absent without a mask)
+        H16, Hv = _tap_operand(torch.zeros_like(Rn) if dRn is None else dRn * (LN2 * Dk), x3, ed,
+                               slot15=None if dmass is None else dmass * (LN2 * Dk))
+        # delta from the values the kernel contracts (the rounded H; split mode: hi + lo): dS = P (dP - delta) then
+        # cancels where P -> 1
+        delta = (Rn * Hv).sum(-1)
         if drop:
             # delta = sum_n P keep (w . H + H_one) = (Rn' . H + m' H_one) / D  (Rn', m' carry D, and so does H)
-            delta = (delta + more[0] * H16[..., 15].float()) / Dk
+            delta = (delta + mass[0] * H16[..., 15].float()) / Dk
         if dLSE is not None:
             delta = delta - dLSE
-        _set_offset(H16, -delta)
+        _set_offset(H16, -delta, x3)
         Gq = G16.clone()
-        _set_offset(Gq, torch.where(valid, -LSE, torch.full_like(LSE, _neg_big(ed))))
-        return _TapAttn._backward_launch(geom, d, L, drop, Gq, H16, ws, pair, Ttc, valid, sdo)
-
-    @staticmethod
-    def _backward_launch(geom, d, L, drop, Gq, H16, ws, pair, Ttc, valid, sdo):
-        """The two backward launches on prepared operands (either operand format) and the gradients out of them."""
-        dev = Ttc.device
-        P, h, Mp = geom.n_prob, geom.heads, geom.Mp
+        _set_offset(Gq, torch.where(valid, -LSE, torch.full_like(LSE, _neg_big(ed))), x3)
+        # the two backward launches on the prepared operands (either format) and the gradients out of them
         dG = torch.zeros(P, h, Mp, TAP_SLOTS, device=dev, dtype=torch.float32)     # rows past the last 16-row block: never written
         dT = torch.zeros_like(Ttc)
         dk = [torch.zeros(P, geom.Np, device=dev, dtype=torch.float32) for _ in range(4)]
-        if drop:
-            thr, seed, key0 = drop
-            _lib.check(KERNEL_TIMER.run("bevr_attn_tap_bwd_q_dropout", _attn_flops(geom, 3), L.bevr_attn_tap_bwd_q_dropout,
-                                        C.byref(d), _ptr(Gq), _ptr(H16), _ptr(ws), _ptr(pair), _ptr(dG), _ptr(dT), key0, thr,
-                                        seed, _stream(), tag=_call_tag(geom)), "bevr_attn_tap_bwd_q_dropout")
-            _lib.check(KERNEL_TIMER.run("bevr_attn_tap_bwd_k_dropout", _attn_flops(geom, 4), L.bevr_attn_tap_bwd_k_dropout,
-                                        C.byref(d), _ptr(Gq), _ptr(H16), _ptr(ws), _ptr(Ttc), *[_ptr(t) for t in dk], key0,
-                                        thr, seed, _stream(), tag=_call_tag(geom)), "bevr_attn_tap_bwd_k_dropout")
-        else:
-            _lib.check(KERNEL_TIMER.run("bevr_attn_tap_bwd_q", _attn_flops(geom, 3), L.bevr_attn_tap_bwd_q, C.byref(d), _ptr(Gq),
-                                        _ptr(H16), _ptr(ws), _ptr(pair), _ptr(dG), _ptr(dT), _stream(), tag=_call_tag(geom)), "bevr_attn_tap_bwd_q")
-            _lib.check(KERNEL_TIMER.run("bevr_attn_tap_bwd_k", _attn_flops(geom, 4), L.bevr_attn_tap_bwd_k, C.byref(d), _ptr(Gq),
-                                        _ptr(H16), _ptr(ws), _ptr(Ttc), *[_ptr(t) for t in dk], _stream(), tag=_call_tag(geom)), "bevr_attn_tap_bwd_k")
+        o = SimpleNamespace(g=geom, desc=geom.desc(), Gq=Gq, H16=H16, ws=ws, pair=pair, Ttc=Ttc, dG=dG, dT=dT, dk=dk,
+                            drop=(drop[2], drop[0], drop[1]) if drop else ())
+        _run(ctx.seg.bwd_q, o)
+        _run(ctx.seg.bwd_k, o)
         da, db, dy, dx = (t[:, :geom.N] for t in dk)
         dGo = dG[..., :TAP_N] * valid[:, None]
         if sdo is not None:
             inv = 1.0 / sdo
             dGo, da, db, dy, dx, dT = dGo * inv, da * inv, db * inv, dy * inv, dx * inv, dT * inv
-        return dGo, da, db, dy, dx, dT, None, None
+        return dGo, da, db, dy, dx, dT, None, None, None
 
 
 def tap_supported(precision: int, groups: int, dropout: bool = False) -> bool:
@@ -1363,11 +1391,9 @@ class _Sample(torch.autograd.Function):
         # algorithmic (compulsory) HBM bytes: the feature map once, a position and an output row per key.  The 4 taps
         # of a key are NOT 4 HBM reads: neighbouring keys share them through L2 (SURVEY 8d counts the map once too)
         bf = feat.dtype == torch.bfloat16
-        fn = _lib.lib().bevr_sample_fwd_bf16 if bf else _lib.lib().bevr_sample_fwd
-        _lib.check(KERNEL_TIMER.run("bevr_sample_fwd", 0.0, fn, _ptr(feat), _ptr(pos),
-                                    _ptr(out), nb, Hi, Wi, Cc, N, _stream(),
-                                    nbytes=4.0 * nb * (Hi * Wi * Cc * (0.5 if bf else 1.0) + N * Cc + 2 * N)),
-                   "bevr_sample_fwd")
+        _launch("bevr_sample_fwd" + ("_bf16" if bf else ""), _ptr(feat), _ptr(pos), _ptr(out), nb, Hi, Wi, Cc, N, _stream(),
+                flops=0.0, nbytes=4.0 * nb * (Hi * Wi * Cc * (0.5 if bf else 1.0) + N * Cc + 2 * N),
+                timer="bevr_sample_fwd", label="bevr_sample_fwd")
         return out
 
     @staticmethod
@@ -1381,11 +1407,9 @@ class _Sample(torch.autograd.Function):
         # algorithmic (compulsory) HBM bytes: dout row, position and position gradient per key; the feature map read
         # once (position gradient) and its gradient written once.  What the scatter really costs is the atomic traffic
         # (4 taps x N x C floats leave L2 as memory-side atomics): bench.py reports that as `traffic` from the PMC counters
-        fn = _lib.lib().bevr_sample_bwd_bf16 if bf else _lib.lib().bevr_sample_bwd
-        _lib.check(KERNEL_TIMER.run("bevr_sample_bwd", 0.0, fn, _ptr(feat), _ptr(pos),
-                                    _ptr(dout), _ptr(dfeat), _ptr(dpos), nb, Hi, Wi, Cc, N, _stream(),
-                                    nbytes=4.0 * nb * (N * Cc + (1.5 if bf else 2.0) * Hi * Wi * Cc + 4 * N)),
-                   "bevr_sample_bwd")
+        _launch("bevr_sample_bwd" + ("_bf16" if bf else ""), _ptr(feat), _ptr(pos), _ptr(dout), _ptr(dfeat), _ptr(dpos), nb, Hi,
+                Wi, Cc, N, _stream(), flops=0.0, nbytes=4.0 * nb * (N * Cc + (1.5 if bf else 2.0) * Hi * Wi * Cc + 4 * N),
+                timer="bevr_sample_bwd", label="bevr_sample_bwd")
         # autograd wants the input's dtype; the cast is skipped when nobody reads the map's gradient
         return (dfeat.to(feat.dtype) if bf and need_dfeat else dfeat if not bf else None), dpos
 
@@ -1412,15 +1436,13 @@ def project_bev_grid(points_3d: torch.Tensor, cam_inv: torch.Tensor, Kmat: torch
     ncam, P = ci.shape[0], pts.shape[1]
     out = torch.empty(ncam, 2, P, device=pts.device, dtype=torch.float32)
     if gray_ref is None:
-        _lib.check(_lib.lib().bevr_project_bev_grid(_ptr(pts), _ptr(ci), _ptr(km), _ptr(out), ncam, P, img_w, img_h,
-                                                    _stream()), "bevr_project_bev_grid")
+        _launch("bevr_project_bev_grid", _ptr(pts), _ptr(ci), _ptr(km), _ptr(out), ncam, P, img_w, img_h, _stream())
         return out
     if gray_ref.dtype != torch.uint8 or gray_ref.dim() != 4 or gray_ref.shape[0] != ncam:
         raise ValueError("gray_ref must be a (ncam, C, H, W) uint8 tensor")
     ref = gray_ref.contiguous()
-    _lib.check(_lib.lib().bevr_project_bev_grid_masked(_ptr(pts), _ptr(ci), _ptr(km), _ptr(out), ncam, P, img_w, img_h,
-                                                       _ptr(ref), ref.shape[1], ref.shape[2], ref.shape[3], _stream()),
-               "bevr_project_bev_grid_masked")
+    _launch("bevr_project_bev_grid_masked", _ptr(pts), _ptr(ci), _ptr(km), _ptr(out), ncam, P, img_w, img_h, _ptr(ref),
+            ref.shape[1], ref.shape[2], ref.shape[3], _stream())
     return out
 
 
@@ -1447,9 +1469,8 @@ class _Corr(torch.autograd.Function):
         inc = torch.empty(n, device=cam.device, dtype=torch.float32)
         inm = torch.empty(m, device=cam.device, dtype=torch.float32)
         same = cam.data_ptr() == mp.data_ptr() and n == m
-        _lib.check(KERNEL_TIMER.run("bevr_corr_fwd", 0.0, _lib.lib().bevr_corr_fwd, _ptr(cam), _ptr(mp), _ptr(D), _ptr(inc),
-                                    _ptr(inm), n, m, E, int(normalize), _stream(),
-                                    nbytes=4.0 * E * (n if same else n + m)), "bevr_corr_fwd")
+        _launch("bevr_corr_fwd", _ptr(cam), _ptr(mp), _ptr(D), _ptr(inc), _ptr(inm), n, m, E, int(normalize), _stream(),
+                flops=0.0, nbytes=4.0 * E * (n if same else n + m))
         ctx.normalize = normalize
         ctx.save_for_backward(cam, mp, D, inc, inm)
         return D
@@ -1469,10 +1490,9 @@ class _Corr(torch.autograd.Function):
         dmap = dcam if same else torch.empty_like(mp)
         # algorithmic (compulsory) HBM bytes: both operands read once, both gradients written once; one matrix correlated
         # with itself (the retrieval losses): read once, and the two sides' SUM written once (csrc/corr.hip)
-        _lib.check(KERNEL_TIMER.run("bevr_corr_bwd", 0.0, _lib.lib().bevr_corr_bwd, _ptr(cam), _ptr(mp), _ptr(D),
-                                    _ptr(dD.contiguous()), _ptr(inc), _ptr(inm), _ptr(dcam), _ptr(dmap), n, m, E,
-                                    int(ctx.normalize), _stream(), nbytes=4.0 * E * (2 * n if same else 2 * (n + m))),
-                   "bevr_corr_bwd")
+        _launch("bevr_corr_bwd", _ptr(cam), _ptr(mp), _ptr(D), _ptr(dD.contiguous()), _ptr(inc), _ptr(inm), _ptr(dcam),
+                _ptr(dmap), n, m, E, int(ctx.normalize), _stream(), flops=0.0,
+                nbytes=4.0 * E * (2 * n if same else 2 * (n + m)))
         # summed (forward: one buffer for both sides, so `same`): dcam is the one input's whole gradient, handed over once
         return (dcam, None, None) if ctx.summed else (dcam, dmap, None)
 
@@ -1488,7 +1508,7 @@ def recall_rank(D: torch.Tensor) -> torch.Tensor:
     D = D.float().contiguous()
     n = D.shape[0]
     rank = torch.empty(n, device=D.device, dtype=torch.int32)
-    _lib.check(_lib.lib().bevr_recall_rank(_ptr(D), _ptr(rank), n, _stream()), "bevr_recall_rank")
+    _launch("bevr_recall_rank", _ptr(D), _ptr(rank), n, _stream())
     return rank
 
 
@@ -1513,12 +1533,10 @@ class _OffsetHead(torch.autograd.Function):
         prm = [None if t is None else t.detach().float().contiguous() for t in (w0, b0, gamma, beta, W3)]
         P = B * H * W
         out = torch.empty(g, B, H, W, dout, device=x.device, dtype=torch.float32)
-        L = _lib.lib()
         for gi in range(g):
             xp = C.c_void_p(x.data_ptr() + gi * cg * 4)
-            _lib.check(L.bevr_offset_head_fwd(xp, _ptr(prm[0]), _ptr(prm[1]), _ptr(prm[2]), _ptr(prm[3]), _ptr(prm[4]),
-                                              _ptr(out[gi]), P, cg, Cc, mx, dout, float(eps), _stream()),
-                       "bevr_offset_head_fwd")
+            _launch("bevr_offset_head_fwd", xp, _ptr(prm[0]), _ptr(prm[1]), _ptr(prm[2]), _ptr(prm[3]), _ptr(prm[4]),
+                    _ptr(out[gi]), P, cg, Cc, mx, dout, float(eps), _stream())
         ctx.save_for_backward(x, *[t for t in prm if t is not None])
         ctx.meta = (g, cg, mx, dout, float(eps), w0 is not None, b0 is not None)
         return out.permute(1, 0, 2, 3, 4).reshape(B * g, H, W, dout)
@@ -1538,13 +1556,11 @@ class _OffsetHead(torch.autograd.Function):
         dw0 = torch.zeros_like(w0) if has_w0 else None
         db0 = torch.zeros_like(b0) if has_b0 else None
         dga, dbe, dW3 = torch.zeros_like(gamma), torch.zeros_like(beta), torch.zeros_like(W3)
-        L = _lib.lib()
         for gi in range(g):
             xp = C.c_void_p(x.data_ptr() + gi * cg * 4)
             dxp = None if dx is None else C.c_void_p(dx.data_ptr() + gi * cg * 4)
-            _lib.check(L.bevr_offset_head_bwd(xp, _ptr(w0), _ptr(b0), _ptr(gamma), _ptr(beta), _ptr(W3), _ptr(do[gi]), dxp,
-                                              _ptr(dw0), _ptr(db0), _ptr(dga), _ptr(dbe), _ptr(dW3), P, cg, Cc, mx, dout,
-                                              eps, _stream()), "bevr_offset_head_bwd")
+            _launch("bevr_offset_head_bwd", xp, _ptr(w0), _ptr(b0), _ptr(gamma), _ptr(beta), _ptr(W3), _ptr(do[gi]), dxp,
+                    _ptr(dw0), _ptr(db0), _ptr(dga), _ptr(dbe), _ptr(dW3), P, cg, Cc, mx, dout, eps, _stream())
         return dx, dw0, db0, dga, dbe, dW3, None, None
 
 
@@ -1570,8 +1586,8 @@ class _LayerNorm(torch.autograd.Function):
         y = torch.empty_like(x)
         mean = torch.empty(rows, device=x.device, dtype=torch.float32)
         rstd = torch.empty_like(mean)
-        _lib.check(_lib.lib().bevr_layernorm_fwd(_ptr(x), _ptr(gamma), _ptr(beta), _ptr(y), _ptr(mean), _ptr(rstd), rows, Cc,
-                                                float(eps), _stream()), "bevr_layernorm_fwd")
+        _launch("bevr_layernorm_fwd", _ptr(x), _ptr(gamma), _ptr(beta), _ptr(y), _ptr(mean), _ptr(rstd), rows, Cc,
+                float(eps), _stream())
         ctx.save_for_backward(x, gamma, mean, rstd)
         return y
 
@@ -1583,8 +1599,8 @@ class _LayerNorm(torch.autograd.Function):
         dx = torch.empty_like(x)
         dg = torch.zeros(Cc, device=x.device, dtype=torch.float32)
         db = torch.zeros_like(dg)
-        _lib.check(_lib.lib().bevr_layernorm_bwd(_ptr(x), _ptr(gamma), _ptr(dy), _ptr(mean), _ptr(rstd), _ptr(dx), _ptr(dg),
-                                                _ptr(db), x.numel() // Cc, Cc, _stream()), "bevr_layernorm_bwd")
+        _launch("bevr_layernorm_bwd", _ptr(x), _ptr(gamma), _ptr(dy), _ptr(mean), _ptr(rstd), _ptr(dx), _ptr(dg), _ptr(db),
+                x.numel() // Cc, Cc, _stream())
         return dx, dg, db, None
 
 
@@ -1612,8 +1628,7 @@ class _KeyPositions(torch.autograd.Function):
         order = None if order is None else order.to(torch.int32).contiguous()
         pos = torch.empty(B, V, G, N, 2, device=off.device, dtype=torch.float32)
         ctx.args = (V, P, G, N, 1 if sca_SD else 0, S, D, 1 if use_tanh else 0, float(sy), float(sx))
-        _lib.check(_lib.lib().bevr_key_positions_fwd(_ptr(off), _ptr(ref), _ptr(order), _ptr(pos), *ctx.args, _stream()),
-                   "bevr_key_positions_fwd")
+        _launch("bevr_key_positions_fwd", _ptr(off), _ptr(ref), _ptr(order), _ptr(pos), *ctx.args, _stream())
         ctx.save_for_backward(off, ref, order)
         return pos
 
@@ -1621,8 +1636,8 @@ class _KeyPositions(torch.autograd.Function):
     def backward(ctx, dpos):
         off, ref, order = ctx.saved_tensors
         doff = torch.empty_like(off)
-        _lib.check(_lib.lib().bevr_key_positions_bwd(_ptr(off), _ptr(ref), _ptr(order), _ptr(dpos.float().contiguous()),
-                                                      _ptr(doff), *ctx.args, _stream()), "bevr_key_positions_bwd")
+        _launch("bevr_key_positions_bwd", _ptr(off), _ptr(ref), _ptr(order), _ptr(dpos.float().contiguous()), _ptr(doff),
+                *ctx.args, _stream())
         return doff, None, None, None, None, None, None, None, None
 
 
@@ -1646,8 +1661,7 @@ class _AffineWarp(torch.autograd.Function):
         img, theta = img.float().contiguous(), theta.float().contiguous()
         B, Cc, H, W = img.shape
         out = torch.empty_like(img)
-        _lib.check(_lib.lib().bevr_affine_warp_fwd(_ptr(img), _ptr(theta), _ptr(out), B, Cc, H, W, _stream()),
-                   "bevr_affine_warp_fwd")
+        _launch("bevr_affine_warp_fwd", _ptr(img), _ptr(theta), _ptr(out), B, Cc, H, W, _stream())
         ctx.save_for_backward(theta)
         return out
 
@@ -1657,8 +1671,7 @@ class _AffineWarp(torch.autograd.Function):
         dout = dout.float().contiguous()
         B, Cc, H, W = dout.shape
         dimg = torch.zeros_like(dout)
-        _lib.check(_lib.lib().bevr_affine_warp_bwd(_ptr(dout), _ptr(theta), _ptr(dimg), B, Cc, H, W, _stream()),
-                   "bevr_affine_warp_bwd")
+        _launch("bevr_affine_warp_bwd", _ptr(dout), _ptr(theta), _ptr(dimg), B, Cc, H, W, _stream())
         return dimg, None
 
 
@@ -1685,7 +1698,6 @@ class _DwConv(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, nhwc: bool):
         _require_gpu(x, weight)
-        L = _lib.lib()
         x = x.contiguous()
         w = weight.contiguous()
         if nhwc:
@@ -1694,8 +1706,8 @@ class _DwConv(torch.autograd.Function):
             B, Cc, H, W = x.shape
         k = w.shape[-1]
         y = torch.empty_like(x)
-        _lib.check(L.bevr_dwconv_fwd(_ptr(x), _ptr(w), _ptr(bias.contiguous()) if bias is not None else None, _ptr(y),
-                                     B, H, W, Cc, k, int(nhwc), 0, _stream()), "bevr_dwconv_fwd")
+        _launch("bevr_dwconv_fwd", _ptr(x), _ptr(w), _ptr(bias.contiguous()) if bias is not None else None, _ptr(y), B, H,
+                W, Cc, k, int(nhwc), 0, _stream())
         ctx.save_for_backward(x, w)
         ctx.meta = (B, H, W, Cc, k, nhwc, bias is not None)
         return y
@@ -1704,18 +1716,17 @@ class _DwConv(torch.autograd.Function):
     def backward(ctx, dy):
         x, w = ctx.saved_tensors
         B, H, W, Cc, k, nhwc, has_bias = ctx.meta
-        L = _lib.lib()
         dy = dy.contiguous()
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
-            _lib.check(L.bevr_dwconv_fwd(_ptr(dy), _ptr(w), None, _ptr(dx), B, H, W, Cc, k, int(nhwc), 1, _stream()),
-                       "bevr_dwconv_fwd(flip)")
+            _launch("bevr_dwconv_fwd", _ptr(dy), _ptr(w), None, _ptr(dx), B, H, W, Cc, k, int(nhwc), 1, _stream(),
+                    label="bevr_dwconv_fwd(flip)")
         if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]):
             dw = torch.zeros_like(w)
             db = torch.zeros(Cc, device=x.device, dtype=x.dtype) if has_bias else None
-            _lib.check(L.bevr_dwconv_bwd_w(_ptr(x), _ptr(dy), _ptr(dw), _ptr(db) if db is not None else None,
-                                           B, H, W, Cc, k, int(nhwc), _stream()), "bevr_dwconv_bwd_w")
+            _launch("bevr_dwconv_bwd_w", _ptr(x), _ptr(dy), _ptr(dw), _ptr(db) if db is not None else None, B, H, W, Cc, k,
+                    int(nhwc), _stream())
         return dx, dw, db, None
 
 
@@ -1725,36 +1736,33 @@ class _DwResGelu(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias):
         _require_gpu(x, weight)
-        L = _lib.lib()
         x, w = x.contiguous(), weight.contiguous()
         b = bias.contiguous() if bias is not None else None
         B, H, W, Cc = x.shape
         y = torch.empty_like(x)
-        _lib.check(L.bevr_dwconv_res_gelu(_ptr(x), _ptr(w), _ptr(b), None, _ptr(y), B, H, W, Cc, 3, 1, _stream()),
-                   "bevr_dwconv_res_gelu(1)")
+        _launch("bevr_dwconv_res_gelu", _ptr(x), _ptr(w), _ptr(b), None, _ptr(y), B, H, W, Cc, 3, 1, _stream(),
+                label="bevr_dwconv_res_gelu(1)")
         ctx.save_for_backward(x, w, b)
         return y
 
     @staticmethod
     def backward(ctx, dout):
         x, w, b = ctx.saved_tensors
-        L = _lib.lib()
         B, H, W, Cc = x.shape
         dout = dout.contiguous()
         # the gradient at the pre-activation x + conv(x) + bias, which is recomputed (one kernel) instead of saved
         g = torch.empty_like(x)
-        _lib.check(L.bevr_dwconv_res_gelu(_ptr(x), _ptr(w), _ptr(b), _ptr(dout), _ptr(g), B, H, W, Cc, 3, 2, _stream()),
-                   "bevr_dwconv_res_gelu(2)")
+        _launch("bevr_dwconv_res_gelu", _ptr(x), _ptr(w), _ptr(b), _ptr(dout), _ptr(g), B, H, W, Cc, 3, 2, _stream(),
+                label="bevr_dwconv_res_gelu(2)")
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
-            _lib.check(L.bevr_dwconv_res_gelu(_ptr(g), _ptr(w), None, None, _ptr(dx), B, H, W, Cc, 3, 3, _stream()),
-                       "bevr_dwconv_res_gelu(3)")
+            _launch("bevr_dwconv_res_gelu", _ptr(g), _ptr(w), None, None, _ptr(dx), B, H, W, Cc, 3, 3, _stream(),
+                    label="bevr_dwconv_res_gelu(3)")
         if ctx.needs_input_grad[1] or (b is not None and ctx.needs_input_grad[2]):
             dw = torch.zeros_like(w)
             db = torch.zeros(Cc, device=x.device, dtype=x.dtype) if b is not None else None
-            _lib.check(L.bevr_dwconv_bwd_w(_ptr(x), _ptr(g), _ptr(dw), _ptr(db), B, H, W, Cc, 3, 1, _stream()),
-                       "bevr_dwconv_bwd_w")
+            _launch("bevr_dwconv_bwd_w", _ptr(x), _ptr(g), _ptr(dw), _ptr(db), B, H, W, Cc, 3, 1, _stream())
         return dx, dw, db
 
 

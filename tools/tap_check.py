@@ -359,12 +359,13 @@ def time_x3():
     kv = torch.randn(B * V, N, 2 * C_, device=dev, generator=gen)
     cgeom = ops.AttnGeom(n_prob=B * V, q_div=V, heads=h, groups=1, S=S, N=N, Wt=2 * S * D - 1, precision=X3)
     Tt = ops.pack_table(T.float(), cgeom)
+    cell_route = ops.attention_route(X3, 1, S, cgeom.Wt, N, cell_split=0, C=C_, heads=h)       # every key in the cell segment
 
     def cell_round():
         q = Qp.clone().requires_grad_(True)
         k = kv.clone().requires_grad_(True)
         ops.KERNEL_TIMER.start()
-        O, _ = ops._AttnCore.apply(q, k, a[:, :N].contiguous(), b[:, :N].contiguous(), Tt, cgeom, 0, None, None, None, None, None)
+        O, _ = ops._AttnCore.apply(q, k, a[:, :N].contiguous(), b[:, :N].contiguous(), Tt, cgeom, cell_route, None, None, None, None, None)
         O.square().sum().backward()
         for name, r in ops.KERNEL_TIMER.stop().items():
             if name.startswith("bevr_attn_cell"):
