@@ -65,6 +65,8 @@ __device__ __forceinline__ float hat(float u) { return fmaxf(1.0f - fabsf(u), 0.
 
 // Bilinear weights of this lane's key over the chunk's cells.  tcol = tx - x0 (column coordinate relative to chunk
 // column 0: integer part = first tap column, fraction = fx), trow = a - A0 likewise.  A masked key passes tcol = -8.
+// (the 16-bit branch's formula and element order are restated by tap_cell_half in attn_tap.h, which packs through the tap
+// kernels' operand type: change the two together)
 template <int PREC> __device__ __forceinline__ CellFrag<PREC> cell_weights(float tcol, float trow, int h) {
   if constexpr (!is16(PREC)) {
     const float wy0 = hat((float)h - trow), wy1 = hat((float)(2 + h) - trow);

@@ -59,14 +59,23 @@ __host__ __device__ __forceinline__ size_t tap_ws_box_offset(const bevr_attn_des
 // slot TAP_CLO parts 2 and 3, all against w = 1 (hi image 1, lo image 0), so that hi lo + hi hi adds p0 + p1 + p2 + p3 = c
 // to the last bit of the float -- the logit's large constant part is exact, and the three-term product only has to carry
 // the tap and bias terms (a convex combination of 4 + 4 entries each, as in the region kernels' split mode).
-// The split instantiations live in translation units of their own (attn_tap_*_x3.hip: #define BEVR_TAP_X3 1 and #include
-// the kernel's source); in the 16-bit instantiations every `if constexpr (X3)` block is discarded.
-__host__ __device__ constexpr bool tap_x3(int prec) { return prec == BEVR_PREC_BF16X3; }
+// The kernels are written ONCE over an operand of NP images (TapOp below: NP = 1 in the 16-bit modes, 2 in split mode);
+// the split instantiations live in translation units of their own (attn_tap_*_x3.hip: #define BEVR_TAP_X3 1 and #include
+// the kernel's source).
+__host__ __device__ constexpr bool tap_split(int prec) { return prec == BEVR_PREC_BF16X3; }
 // the 16-bit arithmetic (conversions, packing) an operand mode's images are made with
-template <int PREC> using TapHalf = Half<tap_x3(PREC) ? BEVR_PREC_BF16 : PREC>;
+template <int PREC> using TapHalf = Half<tap_split(PREC) ? BEVR_PREC_BF16 : PREC>;
+template <int PREC> constexpr int tap_np = tap_split(PREC) ? 2 : 1;
 #ifndef BEVR_TAP_X3
 #define BEVR_TAP_X3 0
 #endif
+// entry points of the split-mode translation units (attn_tap_{fwd,bwd_q,bwd_k}_x3.hip), called from bevr_attn_tap_*
+int bevr_tap_fwd_x3(const bevr_attn_desc& d, const void* G, const void* tap_ws, const float* table_pair, float* mref,
+                    float* R, int* flags, hipStream_t st);
+int bevr_tap_bwd_q_x3(const bevr_attn_desc& d, const void* G, const void* H, const void* tap_ws, const float* table_pair,
+                      float* dG, float* dtable, hipStream_t st);
+int bevr_tap_bwd_k_x3(const bevr_attn_desc& d, const void* G, const void* H, const void* tap_ws, const float* table_t,
+                      float* dkey_a, float* dkey_b, float* dkey_y, float* dkey_x, hipStream_t st);
 
 template <int PREC> __device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c);
 template <> __device__ __forceinline__ f32x4 mfma16<BEVR_PREC_BF16>(bf16x8 a, bf16x8 b, f32x4 c) {
@@ -100,13 +109,44 @@ __device__ __forceinline__ Split2 split2(float x0, float x1) {
   return Split2{h, pack_bf16x2(x0 - __builtin_bit_cast(float, h << 16), x1 - __builtin_bit_cast(float, h & 0xffff0000u))};
 }
 #define TAP_SPLIT2(x0_, x1_, h_, l_) do { const Split2 sp_ = split2(x0_, x1_); (h_) = sp_.h; (l_) = sp_.l; } while (0)
-// eight floats (accumulator values of two 16-key sub-tiles) -> hi and lo B operands
-__device__ __forceinline__ void split8v(const float (&x)[8], bf16x8& h, bf16x8& l) {
-  u32x4 hw, lw;
+// One matrix operand of an operand mode: p[0] the image the 16-bit modes have, p[1] (split mode) the lo image
+template <int NP> struct TapOp { bf16x8 p[NP]; };
+template <int PREC> using TapOpP = TapOp<tap_np<PREC>>;
+// c += a b.  LOGIT: the contraction S = A . [G ; Tsh] (split mode: four terms)
+template <int PREC, bool LOGIT = false>
+__device__ __forceinline__ f32x4 tap_mm(const TapOpP<PREC>& a, const TapOpP<PREC>& b, f32x4 c) {
+  if constexpr (!tap_split(PREC)) return mfma16<PREC>(a.p[0], b.p[0], c);
+  else if constexpr (LOGIT) return mfma16s4(a.p[0], a.p[1], b.p[0], b.p[1], c);
+  else return mfma16s(a.p[0], a.p[1], b.p[0], b.p[1], c);
+}
+// two floats -> dword k of every image (split mode: the pair's hi parts and lo parts)
+template <int PREC> __device__ __forceinline__ void tap_pack2(float x0, float x1, int k, u32x4 (&w)[tap_np<PREC>]) {
+  if constexpr (tap_split(PREC)) TAP_SPLIT2(x0, x1, w[0][k], w[1][k]);
+  else w[0][k] = TapHalf<PREC>::pack2(x0, x1);
+}
+template <int NP> __device__ __forceinline__ TapOp<NP> tap_op(const u32x4 (&w)[NP]) {
+  TapOp<NP> o;
 #pragma unroll
-  for (int k = 0; k < 4; ++k) TAP_SPLIT2(x[2 * k], x[2 * k + 1], hw[k], lw[k]);
-  h = __builtin_bit_cast(bf16x8, hw);
-  l = __builtin_bit_cast(bf16x8, lw);
+  for (int pl = 0; pl < NP; ++pl) o.p[pl] = __builtin_bit_cast(bf16x8, w[pl]);
+  return o;
+}
+// eight floats (accumulator values of two 16-key sub-tiles, or eight weights) -> one operand register per image
+template <int PREC> __device__ __forceinline__ TapOpP<PREC> tap_pack8(const float (&x)[8]) {
+  u32x4 w[tap_np<PREC>];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) tap_pack2<PREC>(x[2 * k], x[2 * k + 1], k, w);
+  return tap_op(w);
+}
+// 16 bytes of every image at `p`, image pl `stride` bytes behind image pl - 1
+template <int NP> __device__ __forceinline__ TapOp<NP> tap_ld(const char* p, size_t stride) {
+  TapOp<NP> o;
+#pragma unroll
+  for (int pl = 0; pl < NP; ++pl) o.p[pl] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(p + pl * stride));
+  return o;
+}
+template <int NP> __device__ __forceinline__ void tap_st(char* p, size_t stride, const TapOp<NP>& o) {
+#pragma unroll
+  for (int pl = 0; pl < NP; ++pl) *reinterpret_cast<u32x4*>(p + pl * stride) = __builtin_bit_cast(u32x4, o.p[pl]);
 }
 
 // two transposed LDS reads (4 rows x 16 columns of 16-bit each, rows 32 B apart in a [key][16] image): element e of
@@ -118,10 +158,16 @@ __device__ __forceinline__ bf16x8 lds_tr8(const char* p, int off2) {
   const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp)(p + off2));
   return __builtin_bit_cast(bf16x8, __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7));
 }
+template <int NP> __device__ __forceinline__ TapOp<NP> tap_ld_tr(const char* p, int off2, int stride) {
+  TapOp<NP> o;
+#pragma unroll
+  for (int pl = 0; pl < NP; ++pl) o.p[pl] = lds_tr8(p + pl * stride, off2);
+  return o;
+}
 
-// the 16 tap slots of one key as 8 packed dwords
-__device__ __forceinline__ void tap_w16(float ys, float xs, float (&w)[TAP_SLOTS]) {
-  float wy[TAP_R], wx[TAP_C];
+// the 16 tap slots of one key: t[0] slots 0..7, t[1] slots 8..15
+template <int PREC> __device__ __forceinline__ void tap_weights(float ys, float xs, TapOpP<PREC> (&t)[2]) {
+  float wy[TAP_R], wx[TAP_C], w[2][8];
 #pragma unroll
   for (int r = 0; r < TAP_R; ++r) wy[r] = hat((float)r - ys);
 #pragma unroll
@@ -129,48 +175,27 @@ __device__ __forceinline__ void tap_w16(float ys, float xs, float (&w)[TAP_SLOTS
 #pragma unroll
   for (int r = 0; r < TAP_R; ++r)
 #pragma unroll
-    for (int c = 0; c < TAP_C; ++c) w[r * TAP_C + c] = wy[r] * wx[c];
-  w[TAP_CHI] = 1.0f;
-  w[TAP_CLO] = 1.0f;
-  w[TAP_DEAD] = ys < -50.0f ? 1.0f : 0.f;
-  w[TAP_ONE] = 1.0f;
-}
-template <int PREC> __device__ __forceinline__ void tap_weights(float ys, float xs, u32x4& lo, u32x4& hi8) {
-  float w[TAP_SLOTS];
-  tap_w16(ys, xs, w);
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    lo[k] = Half<PREC>::pack2(w[2 * k], w[2 * k + 1]);
-    hi8[k] = Half<PREC>::pack2(w[8 + 2 * k], w[8 + 2 * k + 1]);
-  }
-}
-// split mode: h0, h1 = slots 0..7, 8..15 of the hi image, l0, l1 of the lo image
-__device__ __forceinline__ void tap_weights_x3(float ys, float xs, u32x4& h0, u32x4& h1, u32x4& l0, u32x4& l1) {
-  float w[TAP_SLOTS];
-  tap_w16(ys, xs, w);
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    TAP_SPLIT2(w[2 * k], w[2 * k + 1], h0[k], l0[k]);
-    TAP_SPLIT2(w[8 + 2 * k], w[8 + 2 * k + 1], h1[k], l1[k]);
-  }
+    for (int c = 0; c < TAP_C; ++c) w[(r * TAP_C + c) >> 3][(r * TAP_C + c) & 7] = wy[r] * wx[c];
+  w[1][TAP_CHI - 8] = 1.0f;
+  w[1][TAP_CLO - 8] = 1.0f;
+  w[1][TAP_DEAD - 8] = ys < -50.0f ? 1.0f : 0.f;
+  w[1][TAP_ONE - 8] = 1.0f;
+  t[0] = tap_pack8<PREC>(w[0]);
+  t[1] = tap_pack8<PREC>(w[1]);
 }
 
-// the 16 cells of the bias chunk for one key (both lane halves of cell_weights: cells 0..7 | 8..15)
-template <int PREC> __device__ __forceinline__ void tap_cells(float tcol, float trow, u32x4& c0, u32x4& c1) {
-  c0 = __builtin_bit_cast(u32x4, cell_weights<PREC>(tcol, trow, 0).v);
-  c1 = __builtin_bit_cast(u32x4, cell_weights<PREC>(tcol, trow, 1).v);
-}
-
-// split mode: cells 8 hf .. 8 hf + 7 (the 16-bit modes' order: element e = column 2 hf + (e >> 2), row e & 3)
-__device__ __forceinline__ void tap_cell_half_x3(float tcol, float trow, int hf, u32x4& h, u32x4& l) {
+// cells 8 hf .. 8 hf + 7 of the bias chunk for one key, the arithmetic and the order of cell_weights (attn_cell.h):
+// element e = column 2 hf + (e >> 2), row e & 3
+template <int PREC> __device__ __forceinline__ TapOpP<PREC> tap_cell_half(float tcol, float trow, int hf) {
   const float wx0 = hat((float)(2 * hf) - tcol), wx1 = hat((float)(2 * hf + 1) - tcol);
-  float wy[4];
+  float w[8];
 #pragma unroll
-  for (int r = 0; r < 4; ++r) wy[r] = hat((float)r - trow);
-  TAP_SPLIT2(wx0 * wy[0], wx0 * wy[1], h[0], l[0]);
-  TAP_SPLIT2(wx0 * wy[2], wx0 * wy[3], h[1], l[1]);
-  TAP_SPLIT2(wx1 * wy[0], wx1 * wy[1], h[2], l[2]);
-  TAP_SPLIT2(wx1 * wy[2], wx1 * wy[3], h[3], l[3]);
+  for (int r = 0; r < 4; ++r) {
+    const float wy = hat((float)r - trow);
+    w[r] = wx0 * wy;
+    w[4 + r] = wx1 * wy;
+  }
+  return tap_pack8<PREC>(w);
 }
 
 // reductions inside a 32-lane half
@@ -226,7 +251,7 @@ template <int NP> struct LdsTn {
   static constexpr int RING = 4;
 };
 typedef LdsTn<1> LdsT;
-template <int PREC> using LdsTp = LdsTn<tap_x3(PREC) ? 2 : 1>;
+template <int PREC> using LdsTp = LdsTn<tap_np<PREC>>;
 
 __device__ __forceinline__ bool box_fits(const StepBox& sb, float jrx) {
   const int x0 = (int)floorf(jrx + sb.bmin), x1 = (int)floorf(jrx + sb.bmax) + 1;
@@ -241,7 +266,6 @@ __device__ __forceinline__ void tap_producer(const bevr_attn_desc& d, char* smem
                                              const TapRec* __restrict__ recs, const StepBox* __restrict__ box,
                                              const char* __restrict__ tbl, float jrx, int lane) {
   typedef LdsTp<PREC> L;
-  constexpr bool X3 = tap_x3(PREC);
   const int hi = lane >> 5;
   const int n_step = d.Np / KT;
   int alloc = 0, tag_x = 1 << 30, tag_a = 1 << 30;
@@ -252,45 +276,23 @@ __device__ __forceinline__ void tap_producer(const bevr_attn_desc& d, char* smem
   // the table side of chunk origin (x0, a0): image[row][cell 4 c + r] = T2[x0 + c][a0 + row + r], 16-bit
   // (split mode: img_bytes covers the hi rows and, rows_img * 32 behind them, the lo rows)
   auto build_image = [&](char* img, int x0, int a0) {
-    if constexpr (X3) {
-      for (int row = lane; row < rows_img; row += 64) {
-        const int yr0 = a0 + row + d.y_off;
-        const int e0 = max(0, min(yr0, d.Hp - 1)), e2 = max(0, min(yr0 + 2, d.Hp - 1));
-        u32x4 h0, h1, l0, l1;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          const int xc = max(0, min(x0 + c + d.x_off, d.Wp - 1));
-          const char* col = tbl + (size_t)xc * d.Hp * 8;
-          const f32x2 p0 = *reinterpret_cast<const f32x2*>(col + (size_t)e0 * 8);
-          const f32x2 p2 = *reinterpret_cast<const f32x2*>(col + (size_t)e2 * 8);
-          uint32_t u0, u1, v0, v1;
-          TAP_SPLIT2(p0[0], p0[1], u0, v0);
-          TAP_SPLIT2(p2[0], p2[1], u1, v1);
-          if (c < 2) { h0[2 * c] = u0; h0[2 * c + 1] = u1; l0[2 * c] = v0; l0[2 * c + 1] = v1; }
-          else { h1[2 * (c - 2)] = u0; h1[2 * (c - 2) + 1] = u1; l1[2 * (c - 2)] = v0; l1[2 * (c - 2) + 1] = v1; }
-        }
-        *reinterpret_cast<u32x4*>(img + row * 32) = h0;
-        *reinterpret_cast<u32x4*>(img + row * 32 + 16) = h1;
-        *reinterpret_cast<u32x4*>(img + rows_img * 32 + row * 32) = l0;
-        *reinterpret_cast<u32x4*>(img + rows_img * 32 + row * 32 + 16) = l1;
-      }
-    } else
     for (int row = lane; row < rows_img; row += 64) {
       const int yr0 = a0 + row + d.y_off;
       const int e0 = max(0, min(yr0, d.Hp - 1)), e2 = max(0, min(yr0 + 2, d.Hp - 1));
-      u32x4 w0, w1;
+      float w[2][8];     // cells 0..7 | 8..15 of the row
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
         const int xc = max(0, min(x0 + c + d.x_off, d.Wp - 1));
         const char* col = tbl + (size_t)xc * d.Hp * 8;
         const f32x2 p0 = *reinterpret_cast<const f32x2*>(col + (size_t)e0 * 8);
         const f32x2 p2 = *reinterpret_cast<const f32x2*>(col + (size_t)e2 * 8);
-        const uint32_t u0 = TapHalf<PREC>::pack2(p0[0], p0[1]), u1 = TapHalf<PREC>::pack2(p2[0], p2[1]);
-        if (c < 2) { w0[2 * c] = u0; w0[2 * c + 1] = u1; }
-        else { w1[2 * (c - 2)] = u0; w1[2 * (c - 2) + 1] = u1; }
+        w[c >> 1][4 * (c & 1)] = p0[0];
+        w[c >> 1][4 * (c & 1) + 1] = p0[1];
+        w[c >> 1][4 * (c & 1) + 2] = p2[0];
+        w[c >> 1][4 * (c & 1) + 3] = p2[1];
       }
-      *reinterpret_cast<u32x4*>(img + row * 32) = w0;
-      *reinterpret_cast<u32x4*>(img + row * 32 + 16) = w1;
+#pragma unroll
+      for (int k = 0; k < 2; ++k) tap_st(img + row * 32 + 16 * k, rows_img * 32, tap_pack8<PREC>(w[k]));
     }
   };
   // image 0 stands for "no chunk yet" (allocation numbers start at 1): finite values for the masked keys of a slot that
@@ -331,28 +333,13 @@ __device__ __forceinline__ void tap_producer(const bevr_attn_desc& d, char* smem
       const unsigned long long selm = __ballot(sel);
       const int ok0 = (selm & 0xffffffffull) != 0ull, ok1 = (selm >> 32) != 0ull;
       char* bb = smem + (e & 1) * L::BUF;
-      if constexpr (X3) {
-        u32x4 th[2], tl[2], ch[2], cl[2];
-        tap_weights_x3(sel ? rc.ys : TAP_YS_DEAD, rc.xs, th[0], th[1], tl[0], tl[1]);
-        const float tcol = sel ? (xf - (float)x0) + (tx - xf) : -8.0f;
-        tap_cell_half_x3(tcol, rc.a - (float)a0, 0, ch[0], cl[0]);
-        tap_cell_half_x3(tcol, rc.a - (float)a0, 1, ch[1], cl[1]);
+      TapOpP<PREC> t[2];
+      tap_weights<PREC>(sel ? rc.ys : TAP_YS_DEAD, rc.xs, t);
+      const float tcol = sel ? (xf - (float)x0) + (tx - xf) : -8.0f;
 #pragma unroll
-        for (int k = 0; k < 2; ++k) {
-          *reinterpret_cast<u32x4*>(bb + L::OFF_TAPS + lane * 32 + 16 * k) = th[k];
-          *reinterpret_cast<u32x4*>(bb + L::OFF_CELLS + lane * 32 + 16 * k) = ch[k];
-          *reinterpret_cast<u32x4*>(bb + L::OFF_LO + L::OFF_TAPS + lane * 32 + 16 * k) = tl[k];
-          *reinterpret_cast<u32x4*>(bb + L::OFF_LO + L::OFF_CELLS + lane * 32 + 16 * k) = cl[k];
-        }
-      } else {
-        u32x4 t0, t1, c0, c1;
-        tap_weights<PREC>(sel ? rc.ys : TAP_YS_DEAD, rc.xs, t0, t1);
-        const float tcol = sel ? (xf - (float)x0) + (tx - xf) : -8.0f;
-        tap_cells<PREC>(tcol, rc.a - (float)a0, c0, c1);
-        *reinterpret_cast<u32x4*>(bb + L::OFF_TAPS + lane * 32) = t0;
-        *reinterpret_cast<u32x4*>(bb + L::OFF_TAPS + lane * 32 + 16) = t1;
-        *reinterpret_cast<u32x4*>(bb + L::OFF_CELLS + lane * 32) = c0;
-        *reinterpret_cast<u32x4*>(bb + L::OFF_CELLS + lane * 32 + 16) = c1;
+      for (int k = 0; k < 2; ++k) {
+        tap_st(bb + L::OFF_TAPS + lane * 32 + 16 * k, L::OFF_LO, t[k]);
+        tap_st(bb + L::OFF_CELLS + lane * 32 + 16 * k, L::OFF_LO, tap_cell_half<PREC>(tcol, rc.a - (float)a0, k));
       }
       int al0 = alloc, al1 = alloc, ox0 = tag_x, oa0 = tag_a;
       if (ok0) {

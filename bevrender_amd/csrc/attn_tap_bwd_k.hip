@@ -36,9 +36,9 @@ template <int NP> struct LdsKn {
   static constexpr int BUF = SPB * SLAB;
 };
 typedef LdsKn<1> LdsK;
-template <int PREC> using LdsKp = LdsKn<tap_x3(PREC) ? 2 : 1>;
+template <int PREC> using LdsKp = LdsKn<tap_np<PREC>>;
 // (split mode: every operand twice -- the registers of 2 waves per SIMD)
-constexpr int tap_bwd_k_waves(int prec) { return tap_x3(prec) ? 2 : 4; }
+constexpr int tap_bwd_k_waves(int prec) { return tap_split(prec) ? 2 : 4; }
 // dwords per (kind, parity, column) of a window: rows 0 .. Sp + NRX + 7, two rows per dword
 __host__ __device__ __forceinline__ int win_dwords(int Sp) { return (Sp + NRX + 8) / 2; }
 
@@ -59,8 +59,8 @@ __global__ __launch_bounds__(64 * (NKW + 1), tap_bwd_k_waves(PREC)) void attn_ta
     const float* __restrict__ table_t, float* __restrict__ dkey_a, float* __restrict__ dkey_b,
     float* __restrict__ dkey_y, float* __restrict__ dkey_x, int n_wg_ph TAP_DROP_PARAMS) {
   typedef LdsKp<PREC> L;
-  constexpr bool X3 = tap_x3(PREC);
-  constexpr int NP = X3 ? 2 : 1;
+  constexpr bool X3 = tap_split(PREC);
+  constexpr int NP = tap_np<PREC>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
   const int n_ph = d.n_prob * d.heads;
@@ -175,35 +175,28 @@ __global__ __launch_bounds__(64 * (NKW + 1), tap_bwd_k_waves(PREC)) void attn_ta
     // slab `sl` (0 .. S nslab - 1, column-major) of the packed rows starts sl * 1024 bytes in; a step stages SPB slabs
     auto slab_index = [&](int j2, int st2, int u) { return min(j2 * nslab + min(SPB * st2 + u, nslab - 1), d.S * nslab - 1); };
     int e = 0;
-    u32x4 gv[SPB * NP], hv[SPB * NP];     // split mode: [SPB + u] the lo planes' rows
-    [[maybe_unused]] const size_t g_lo = (size_t)n_ph * Mp * 32;
+    u32x4 gv[NP][SPB], hv[NP][SPB];       // the rows in flight, per image
+    const size_t g_lo = (size_t)n_ph * Mp * 32;     // the lo planes of G and H
+    auto rows_load = [&](int j2, int st2) {
 #pragma unroll
-    for (int u = 0; u < SPB; ++u) {
-      gv[u] = gload16(Gp + (size_t)slab_index(0, 0, u) * 1024);
-      hv[u] = gload16(Hq + (size_t)slab_index(0, 0, u) * 1024);
-    }
-    if constexpr (X3) {
+      for (int pl = 0; pl < NP; ++pl)
 #pragma unroll
-      for (int u = 0; u < SPB; ++u) {
-        gv[SPB * (NP - 1) + u] = gload16(Gp + g_lo + (size_t)slab_index(0, 0, u) * 1024);
-        hv[SPB * (NP - 1) + u] = gload16(Hq + g_lo + (size_t)slab_index(0, 0, u) * 1024);
-      }
-    }
+        for (int u = 0; u < SPB; ++u) {
+          gv[pl][u] = gload16(Gp + pl * g_lo + (size_t)slab_index(j2, st2, u) * 1024);
+          hv[pl][u] = gload16(Hq + pl * g_lo + (size_t)slab_index(j2, st2, u) * 1024);
+        }
+    };
+    rows_load(0, 0);
     for (int j = 0; j < d.S; ++j) {
       for (int st = 0; st < nstep; ++st, ++e) {
         char* bb = smem + (e & 1) * L::BUF;
 #pragma unroll
-        for (int u = 0; u < SPB; ++u) {
-          *reinterpret_cast<u32x4*>(bb + u * L::SLAB + L::OFF_G + lane * 16) = gv[u];
-          *reinterpret_cast<u32x4*>(bb + u * L::SLAB + L::OFF_H + lane * 16) = hv[u];
-        }
-        if constexpr (X3) {
+        for (int pl = 0; pl < NP; ++pl)
 #pragma unroll
           for (int u = 0; u < SPB; ++u) {
-            *reinterpret_cast<u32x4*>(bb + u * L::SLAB + L::OFF_LO + L::OFF_G + lane * 16) = gv[SPB * (NP - 1) + u];
-            *reinterpret_cast<u32x4*>(bb + u * L::SLAB + L::OFF_LO + L::OFF_H + lane * 16) = hv[SPB * (NP - 1) + u];
+            *reinterpret_cast<u32x4*>(bb + u * L::SLAB + pl * L::OFF_LO + L::OFF_G + lane * 16) = gv[pl][u];
+            *reinterpret_cast<u32x4*>(bb + u * L::SLAB + pl * L::OFF_LO + L::OFF_H + lane * 16) = hv[pl][u];
           }
-        }
         if constexpr (!SLOW) {
           item_store(j + 1, slice_item(st, 0), f0);
           item_store(j + 1, slice_item(st, 1), f1);
@@ -216,18 +209,7 @@ __global__ __launch_bounds__(64 * (NKW + 1), tap_bwd_k_waves(PREC)) void attn_ta
         }
         // the next step's rows and the next window slice: in flight across the barrier
         const int jn = st + 1 < nstep ? j : min(j + 1, d.S - 1), stn = st + 1 < nstep ? st + 1 : 0;
-#pragma unroll
-        for (int u = 0; u < SPB; ++u) {
-          gv[u] = gload16(Gp + (size_t)slab_index(jn, stn, u) * 1024);
-          hv[u] = gload16(Hq + (size_t)slab_index(jn, stn, u) * 1024);
-        }
-        if constexpr (X3) {
-#pragma unroll
-          for (int u = 0; u < SPB; ++u) {
-            gv[SPB * (NP - 1) + u] = gload16(Gp + g_lo + (size_t)slab_index(jn, stn, u) * 1024);
-            hv[SPB * (NP - 1) + u] = gload16(Hq + g_lo + (size_t)slab_index(jn, stn, u) * 1024);
-          }
-        }
+        rows_load(jn, stn);
         if constexpr (!SLOW) {
           const int jf = st + 1 < nstep ? j + 1 : j + 2;
           item_load(jf, slice_item(stn, 0), f0);
@@ -248,8 +230,8 @@ __global__ __launch_bounds__(64 * (NKW + 1), tap_bwd_k_waves(PREC)) void attn_ta
   const StepBox sb = box[tl];
   const int da = sb.amin - a0w;                       // rows between the window's origin and this tile's chunk origin
 
-  bf16x8 bk[2 * NP];   // (split mode: [2 + kb] the lo parts)
-  //                      B operand of S / dP for key sub-tile kb: lanes 0..31 the tap slots, lanes 32..63 the cells (per column)
+  // B operand of S / dP for key sub-tile kb: lanes 0..31 the tap slots, lanes 32..63 the cells (per column)
+  TapOp<NP> bk[2];
   // Z[slot 4 g + e][key] of the logit path (G^T dS) and of the value path (H^T P: H carries ln2, undone at the end),
   // Z[cell (c = g, r = e)][key]
   f32x4 zt[2], zv[2], zc[2];
@@ -258,16 +240,10 @@ __global__ __launch_bounds__(64 * (NKW + 1), tap_bwd_k_waves(PREC)) void attn_ta
   for (int kb = 0; kb < 2; ++kb) {
     const TapRec r0 = recs[(size_t)tl * 32 + 16 * kb + li];
     if (g == 0) stash[16 * kb + li] = r0;
-    if constexpr (X3) {
-      u32x4 th0, th1, tl0, tl1;
-      tap_weights_x3(r0.ys, r0.xs, th0, th1, tl0, tl1);
-      bk[kb] = __builtin_bit_cast(bf16x8, g == 0 ? th0 : th1);
-      bk[2 * (NP - 1) + kb] = __builtin_bit_cast(bf16x8, g == 0 ? tl0 : tl1);
-    } else {
-      u32x4 t0, t1;
-      tap_weights<PREC>(r0.ys, r0.xs, t0, t1);
-      bk[kb] = __builtin_bit_cast(bf16x8, g == 0 ? t0 : t1);
-    }
+    TapOp<NP> t[2];
+    tap_weights<PREC>(r0.ys, r0.xs, t);
+#pragma unroll
+    for (int pl = 0; pl < NP; ++pl) bk[kb].p[pl] = g == 0 ? t[0].p[pl] : t[1].p[pl];
     zt[kb] = f32x4{0.f, 0.f, 0.f, 0.f};
     zv[kb] = f32x4{0.f, 0.f, 0.f, 0.f};
     zc[kb] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -293,40 +269,39 @@ __global__ __launch_bounds__(64 * (NKW + 1), tap_bwd_k_waves(PREC)) void attn_ta
   // 2 (g - 2) and + 1) and the transposed reads of the Z operands (hi and lo parts)
   const char* win_b = nullptr;
   int wq0 = 0, wq1 = 0, wth = 0, wtl = 0;
+  const int win_lo = 2 * NCW * NRWD * 4;      // the window's lo parts behind its hi parts
   // one 32-row slab of column j against this wave's 32 keys.  FIT: the tile's taps fit one chunk inside the window (bias
   // and its position gradient through the matrix cores); else the per-pair gather from the table in global memory
   auto slab = [&](auto fit_tag, const char* base, int i0) {
     constexpr bool FIT = decltype(fit_tag)::value;
     // (rows past the grid carry the offset -big in G: their weights are 0 without a test here)
-    bf16x8 qa[2], ha[2];
+    TapOp<NP> qa[2], ha[2];
 #pragma unroll
     for (int rb = 0; rb < 2; ++rb) {
-      u32x4 v = {0u, 0u, 0u, 0u}, hv = {0u, 0u, 0u, 0u};
+      qa[rb] = ha[rb] = TapOp<NP>{};
       if (g < 2) {
-        v = *reinterpret_cast<const u32x4*>(base + a_row + rb * 512);
-        hv = *reinterpret_cast<const u32x4*>(base + L::OFF_H - L::OFF_G + a_row + rb * 512);
+        qa[rb] = tap_ld<NP>(base + a_row + rb * 512, L::OFF_LO);
+        ha[rb] = tap_ld<NP>(base + L::OFF_H - L::OFF_G + a_row + rb * 512, L::OFF_LO);
       } else if (FIT) {
         // the chunk's cells for BEV row i0 + 16 rb + li: columns 2 (g - 2), + 1; rows i .. i + 3 of the window (addresses
-        // prepared per column: wq0 / wq1; a slab is 16 dwords further, the second row block 8 more)
-        const uint32_t* w0 = reinterpret_cast<const uint32_t*>(win_b + wq0 + 2 * i0) + 8 * rb;
-        const uint32_t* w1 = reinterpret_cast<const uint32_t*>(win_b + wq1 + 2 * i0) + 8 * rb;
-        v[0] = w0[0]; v[1] = w0[1];
-        v[2] = w1[0]; v[3] = w1[1];
+        // prepared per column: wq0 / wq1; a slab is 16 dwords further, the second row block 8 more); the lo image is the
+        // window's lo parts
+#pragma unroll
+        for (int pl = 0; pl < NP; ++pl) {
+          const uint32_t* w0 = reinterpret_cast<const uint32_t*>(win_b + pl * win_lo + wq0 + 2 * i0) + 8 * rb;
+          const uint32_t* w1 = reinterpret_cast<const uint32_t*>(win_b + pl * win_lo + wq1 + 2 * i0) + 8 * rb;
+          qa[rb].p[pl] = __builtin_bit_cast(bf16x8, u32x4{w0[0], w0[1], w1[0], w1[1]});
+        }
       }
-      qa[rb] = __builtin_bit_cast(bf16x8, v);
-      ha[rb] = __builtin_bit_cast(bf16x8, hv);
     }
-    const bf16x8 gt = lds_tr8(base + L::OFF_G + t_off, 512);
-    const bf16x8 ht = lds_tr8(base + L::OFF_H + t_off, 512);
-    bf16x8 thi = gt, tlo = gt;
+    const TapOp<NP> gt = tap_ld_tr<NP>(base + L::OFF_G + t_off, 512, L::OFF_LO);
+    const TapOp<NP> ht = tap_ld_tr<NP>(base + L::OFF_H + t_off, 512, L::OFF_LO);
+    bf16x8 thi = gt.p[0], tlo = gt.p[0];
     if constexpr (FIT) {
       const uint32_t* w0 = reinterpret_cast<const uint32_t*>(win_b + wth + 2 * i0);
       const uint32_t* w1 = reinterpret_cast<const uint32_t*>(win_b + wtl + 2 * i0);
-      u32x4 a, b;
-      a[0] = w0[0]; a[1] = w0[1]; a[2] = w0[8]; a[3] = w0[9];
-      b[0] = w1[0]; b[1] = w1[1]; b[2] = w1[8]; b[3] = w1[9];
-      thi = __builtin_bit_cast(bf16x8, a);
-      tlo = __builtin_bit_cast(bf16x8, b);
+      thi = __builtin_bit_cast(bf16x8, u32x4{w0[0], w0[1], w0[8], w0[9]});
+      tlo = __builtin_bit_cast(bf16x8, u32x4{w1[0], w1[1], w1[8], w1[9]});
     }
 #if BEVR_DROP
     // the 8 queries of this lane's accumulator rows: i0 + 4 g + r (row block 0) and + 16 (row block 1): the row hash and
@@ -344,10 +319,10 @@ __global__ __launch_bounds__(64 * (NKW + 1), tap_bwd_k_waves(PREC)) void attn_ta
 #pragma unroll
     for (int kb = 0; kb < 2; ++kb) {
       const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
-      f32x4 s0 = mfma16<PREC>(qa[0], bk[kb], z4);       // S[query 4 g + e of row block 0][key]
-      f32x4 s1 = mfma16<PREC>(qa[1], bk[kb], z4);
-      const f32x4 q0 = mfma16<PREC>(ha[0], bk[kb], z4);  // dP
-      const f32x4 q1 = mfma16<PREC>(ha[1], bk[kb], z4);
+      const f32x4 s0 = tap_mm<PREC, true>(qa[0], bk[kb], z4);       // S[query 4 g + e of row block 0][key]
+      const f32x4 s1 = tap_mm<PREC, true>(qa[1], bk[kb], z4);
+      const f32x4 q0 = tap_mm<PREC>(ha[0], bk[kb], z4);             // dP
+      const f32x4 q1 = tap_mm<PREC>(ha[1], bk[kb], z4);
       float p[8], ds[8];
       if constexpr (!FIT) {
         const TapRec rk = stash[16 * kb + li];
@@ -399,104 +374,21 @@ __global__ __launch_bounds__(64 * (NKW + 1), tap_bwd_k_waves(PREC)) void attn_ta
 #endif
         }
       }
-      u32x4 dsw, pw;
+      u32x4 dsw[NP], pw[NP];      // (pair by pair: packed one after the other the two cost the gather launch scratch)
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        dsw[k] = TapHalf<PREC>::pack2(ds[2 * k], ds[2 * k + 1]);
-        pw[k] = TapHalf<PREC>::pack2(p[2 * k], p[2 * k + 1]);
+        tap_pack2<PREC>(ds[2 * k], ds[2 * k + 1], k, dsw);
+        tap_pack2<PREC>(p[2 * k], p[2 * k + 1], k, pw);
       }
-      const bf16x8 ds8 = __builtin_bit_cast(bf16x8, dsw), p8 = __builtin_bit_cast(bf16x8, pw);
-      zt[kb] = mfma16<PREC>(gt, ds8, zt[kb]);
-      zv[kb] = mfma16<PREC>(ht, p8, zv[kb]);
+      const TapOp<NP> ds8 = tap_op(dsw), p8 = tap_op(pw);
+      zt[kb] = tap_mm<PREC>(gt, ds8, zt[kb]);
+      zv[kb] = tap_mm<PREC>(ht, p8, zv[kb]);
       if constexpr (FIT) {
-        zc[kb] = mfma16<PREC>(tlo, ds8, zc[kb]);
-        zc[kb] = mfma16<PREC>(thi, ds8, zc[kb]);
+        // the window's hi + lo parts against dS, small terms first (split mode: the lo image of dS against the hi part too)
+        zc[kb] = mfma16<PREC>(tlo, ds8.p[0], zc[kb]);
+        if constexpr (X3) zc[kb] = mfma16<PREC>(thi, ds8.p[1], zc[kb]);
+        zc[kb] = mfma16<PREC>(thi, ds8.p[0], zc[kb]);
       }
-    }
-  };
-
-  // split mode: the same with every operand as (hi, lo); P and dS are split after the exponential
-  [[maybe_unused]] auto slab3 = [&](auto fit_tag, const char* base, int i0) {
-    constexpr bool FIT = decltype(fit_tag)::value;
-    bf16x8 qa[2][2], ha[2][2], gt[2], ht[2];     // [.][plane]
-#pragma unroll
-    for (int pl = 0; pl < 2; ++pl) {
-#pragma unroll
-      for (int rb = 0; rb < 2; ++rb) {
-        u32x4 v = {0u, 0u, 0u, 0u}, hv = {0u, 0u, 0u, 0u};
-        if (g < 2) {
-          v = *reinterpret_cast<const u32x4*>(base + pl * L::OFF_LO + a_row + rb * 512);
-          hv = *reinterpret_cast<const u32x4*>(base + pl * L::OFF_LO + L::OFF_H - L::OFF_G + a_row + rb * 512);
-        } else if (FIT) {
-          const int kind = pl * 2 * NCW * NRWD * 4;      // the window's lo parts
-          const uint32_t* w0 = reinterpret_cast<const uint32_t*>(win_b + kind + wq0 + 2 * i0) + 8 * rb;
-          const uint32_t* w1 = reinterpret_cast<const uint32_t*>(win_b + kind + wq1 + 2 * i0) + 8 * rb;
-          v[0] = w0[0]; v[1] = w0[1];
-          v[2] = w1[0]; v[3] = w1[1];
-        }
-        qa[rb][pl] = __builtin_bit_cast(bf16x8, v);
-        ha[rb][pl] = __builtin_bit_cast(bf16x8, hv);
-      }
-      gt[pl] = lds_tr8(base + pl * L::OFF_LO + L::OFF_G + t_off, 512);
-      ht[pl] = lds_tr8(base + pl * L::OFF_LO + L::OFF_H + t_off, 512);
-    }
-    bf16x8 thi = gt[0], tlo = gt[0];
-    if constexpr (FIT) {
-      const uint32_t* w0 = reinterpret_cast<const uint32_t*>(win_b + wth + 2 * i0);
-      const uint32_t* w1 = reinterpret_cast<const uint32_t*>(win_b + wtl + 2 * i0);
-      u32x4 a, b;
-      a[0] = w0[0]; a[1] = w0[1]; a[2] = w0[8]; a[3] = w0[9];
-      b[0] = w1[0]; b[1] = w1[1]; b[2] = w1[8]; b[3] = w1[9];
-      thi = __builtin_bit_cast(bf16x8, a);
-      tlo = __builtin_bit_cast(bf16x8, b);
-    }
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb) {
-      const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
-      const bf16x8 kh = bk[kb], kl = bk[2 * (NP - 1) + kb];
-      const f32x4 s0 = mfma16s4(qa[0][0], qa[0][1], kh, kl, z4);
-      const f32x4 s1 = mfma16s4(qa[1][0], qa[1][1], kh, kl, z4);
-      const f32x4 q0 = mfma16s(ha[0][0], ha[0][1], kh, kl, z4);
-      const f32x4 q1 = mfma16s(ha[1][0], ha[1][1], kh, kl, z4);
-      float p[8], ds[8];
-      if constexpr (!FIT) {
-        const TapRec rk = stash[16 * kb + li];
-        const float a = rk.a, tx = jrx + rk.b;
-        const float af = floorf(a), xf = floorf(tx);
-        const float fy = a - af, fx = tx - xf;
-        const bool dead = rk.ys < -50.0f;
-        const int xc = max(0, min((int)xf + d.x_off, d.Wp - 2));
-        const int yb = (int)af + d.y_off + i0 + 4 * g;
-        float pa = 0.f, pb = 0.f;
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {
-          const int y = max(0, min(yb + (r & 3) + 16 * (r >> 2), HpT - 2));
-          const float* c0p = tbl + (size_t)xc * HpT + y;
-          const float t00 = c0p[0], t01 = c0p[1], t10 = c0p[HpT], t11 = c0p[HpT + 1];
-          const float u0 = t00 + fy * (t01 - t00), u1 = t10 + fy * (t11 - t10);
-          const float sv = (r < 4 ? s0[r & 3] : s1[r & 3]) + (dead ? 0.f : u0 + fx * (u1 - u0));
-          p[r] = fast_exp2(sv);
-          ds[r] = p[r] * (r < 4 ? q0[r & 3] : q1[r & 3]);
-          pa += ds[r] * ((1.0f - fx) * (t01 - t00) + fx * (t11 - t10));
-          pb += ds[r] * (u1 - u0);
-        }
-        acc_a[kb] += dead ? 0.f : pa;
-        acc_b[kb] += dead ? 0.f : pb;
-      } else {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          p[r] = fast_exp2(s0[r]);
-          ds[r] = p[r] * q0[r];
-          p[4 + r] = fast_exp2(s1[r]);
-          ds[4 + r] = p[4 + r] * q1[r];
-        }
-      }
-      bf16x8 dh, dl, ph, pl;
-      split8v(ds, dh, dl);
-      split8v(p, ph, pl);
-      zt[kb] = mfma16s(gt[0], gt[1], dh, dl, zt[kb]);
-      zv[kb] = mfma16s(ht[0], ht[1], ph, pl, zv[kb]);
-      if constexpr (FIT) zc[kb] = mfma16s(thi, tlo, dh, dl, zc[kb]);
     }
   };
 
@@ -520,22 +412,12 @@ __global__ __launch_bounds__(64 * (NKW + 1), tap_bwd_k_waves(PREC)) void attn_ta
 #pragma unroll
     for (int kb = 0; kb < 2; ++kb) {
       if (g >= 2) {
-        u32x4 cw = {0u, 0u, 0u, 0u};
-        if constexpr (X3) {
-          u32x4 cl = {0u, 0u, 0u, 0u};
-          if (!SLOW && mine) {
-            float tcol, trow;
-            chunk_coords(kb, tcol, trow);
-            tap_cell_half_x3(tcol, trow, g - 2, cw, cl);
-          }
-          bk[2 * (NP - 1) + kb] = __builtin_bit_cast(bf16x8, cl);
-        } else
+        bk[kb] = TapOp<NP>{};
         if (!SLOW && mine) {
           float tcol, trow;
           chunk_coords(kb, tcol, trow);
-          cw = __builtin_bit_cast(u32x4, cell_weights<PREC>(tcol, trow, g - 2).v);
+          bk[kb] = tap_cell_half<PREC>(tcol, trow, g - 2);
         }
-        bk[kb] = __builtin_bit_cast(bf16x8, cw);
       }
       zc[kb] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
@@ -546,17 +428,14 @@ __global__ __launch_bounds__(64 * (NKW + 1), tap_bwd_k_waves(PREC)) void attn_ta
       wq1 = wq0 + NRWD * 4;
       const int it = 4 * g + cell_r + da, pt = it & 1;           // transposed reads: rows 4 g + cell_r .. + 3 and + 16 ..
       wth = ((pt * NCW + dx + cell_c) * NRWD + ((it - pt) >> 1)) * 4;
-      wtl = wth + 2 * NCW * NRWD * 4;
+      wtl = wth + win_lo;
     }
     for (int st = 0; st < nstep; ++st, ++e) {
       __syncthreads();
       if (!mine) continue;
 #pragma unroll
       for (int u = 0; u < SPB; ++u)
-        if (SPB * st + u < nslab) {
-          if constexpr (X3) slab3(std::integral_constant<bool, !SLOW>{}, smem + (e & 1) * L::BUF + u * L::SLAB, 32 * (SPB * st + u));
-          else slab(std::integral_constant<bool, !SLOW>{}, smem + (e & 1) * L::BUF + u * L::SLAB, 32 * (SPB * st + u));
-        }
+        if (SPB * st + u < nslab) slab(std::integral_constant<bool, !SLOW>{}, smem + (e & 1) * L::BUF + u * L::SLAB, 32 * (SPB * st + u));
     }
     // ---- the column's bias-position gradients out of Z: this lane holds chunk column c = g, rows 0..3 of its key ----
     if (!SLOW && mine) {
@@ -640,10 +519,6 @@ int bevr_tap_bwd_k_x3(const bevr_attn_desc& d, const void* G, const void* H, con
   return launch<BEVR_PREC_BF16X3>(d, G, H, tap_ws, table_t, dkey_a, dkey_b, dkey_y, dkey_x, st);
 }
 #else
-#if !BEVR_DROP
-int bevr_tap_bwd_k_x3(const bevr_attn_desc& d, const void* G, const void* H, const void* tap_ws, const float* table_t,
-                      float* dkey_a, float* dkey_b, float* dkey_y, float* dkey_x, hipStream_t st);     // attn_tap_bwd_k_x3.hip
-#endif
 #if BEVR_DROP
 extern "C" int bevr_attn_tap_bwd_k_dropout(const bevr_attn_desc* d, const void* G, const void* H, const void* tap_ws,
                                            const float* table_t, float* dkey_a, float* dkey_b, float* dkey_y,

@@ -16,14 +16,13 @@
 namespace {
 
 // (split mode: every operand twice -- the fat NB = 4 instantiation gets the registers of 2 waves per SIMD)
-constexpr int tap_bwd_q_waves(int prec, int nb) { return tap_x3(prec) && nb == 4 ? 2 : 4; }
+constexpr int tap_bwd_q_waves(int prec, int nb) { return tap_split(prec) && nb == 4 ? 2 : 4; }
 template <int PREC, int NB>
 __global__ __launch_bounds__(512, tap_bwd_q_waves(PREC, NB)) void attn_tap_bwd_q_kernel(
     bevr_attn_desc d, const char* __restrict__ G, const char* __restrict__ H, const char* __restrict__ tap_ws, const char* __restrict__ table_pair,
     float* __restrict__ dG, float* __restrict__ dtable TAP_DROP_PARAMS) {
   typedef LdsTp<PREC> L;
-  constexpr bool X3 = tap_x3(PREC);
-  constexpr int NP = X3 ? 2 : 1;
+  constexpr int NP = tap_np<PREC>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
   const int n_ph = d.n_prob * d.heads;
@@ -52,37 +51,23 @@ __global__ __launch_bounds__(512, tap_bwd_q_waves(PREC, NB)) void attn_tap_bwd_q
   }
 
   const int blk0 = wave * NB;
-  bf16x8 bop[NB * NP];     // lanes 0..31 G[q][8 kg ..], lanes 32..63 the chunk's table side (split mode: [NB + nb] the lo parts)
-  bf16x8 hop[NB * NP];     // lanes 0..31 H[q][8 kg ..], lanes 32..63 zero
+  TapOp<NP> bop[NB];     // lanes 0..31 G[q][8 kg ..], lanes 32..63 the chunk's table side
+  TapOp<NP> hop[NB];     // lanes 0..31 H[q][8 kg ..], lanes 32..63 zero
   f32x4 ytap[NB], ycell[NB];
   size_t mqv[NB];
+  const size_t g_lo = (size_t)n_ph * Mp * TAP_SLOTS * 2;     // the lo planes of G and H
 #pragma unroll
   for (int nb = 0; nb < NB; ++nb) {
     const int blk = min(blk0 + nb, nblk - 1);
     const size_t mq = (size_t)ph * Mp + (size_t)j * d.Sp + blk * QB + li;
     mqv[nb] = mq;
-    u32x4 g = {0u, 0u, 0u, 0u}, hh = {0u, 0u, 0u, 0u};
+    bop[nb] = hop[nb] = TapOp<NP>{};
     if (kg < 2) {
-      g = *reinterpret_cast<const u32x4*>(G + (mq * TAP_SLOTS + 8 * kg) * 2);
-      hh = *reinterpret_cast<const u32x4*>(H + (mq * TAP_SLOTS + 8 * kg) * 2);
+      bop[nb] = tap_ld<NP>(G + (mq * TAP_SLOTS + 8 * kg) * 2, g_lo);
+      hop[nb] = tap_ld<NP>(H + (mq * TAP_SLOTS + 8 * kg) * 2, g_lo);
     }
-    bop[nb] = __builtin_bit_cast(bf16x8, g);
-    hop[nb] = __builtin_bit_cast(bf16x8, hh);
     ytap[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
     ycell[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
-  }
-  if constexpr (X3) {   // the lo planes of G and H
-    const size_t g_lo = (size_t)n_ph * Mp * TAP_SLOTS * 2;
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) {
-      u32x4 g = {0u, 0u, 0u, 0u}, hh = {0u, 0u, 0u, 0u};
-      if (kg < 2) {
-        g = *reinterpret_cast<const u32x4*>(G + g_lo + (mqv[nb] * TAP_SLOTS + 8 * kg) * 2);
-        hh = *reinterpret_cast<const u32x4*>(H + g_lo + (mqv[nb] * TAP_SLOTS + 8 * kg) * 2);
-      }
-      bop[NB * (NP - 1) + nb] = __builtin_bit_cast(bf16x8, g);
-      hop[NB * (NP - 1) + nb] = __builtin_bit_cast(bf16x8, hh);
-    }
   }
 #if BEVR_DROP
   // dropout: dS = P (keep ? D dP : 0 - delta).  The MFMA gives x = D dP - delta (D dP = w . H + H[TAP_ONE], -delta in slots
@@ -93,7 +78,7 @@ __global__ __launch_bounds__(512, tap_bwd_q_waves(PREC, NB)) void attn_tap_bwd_q
   for (int nb = 0; nb < NB; ++nb) {
     hrow[nb] = bevr_drop_row(drop_seed, (uint32_t)ph, (uint32_t)(j * d.Sp + min(blk0 + nb, nblk - 1) * QB + li));
     const uint32_t c2 = *reinterpret_cast<const uint32_t*>(H + (mqv[nb] * TAP_SLOTS + TAP_CHI) * 2);
-    ndel[nb] = Half<PREC>::lo(c2) + Half<PREC>::hi(c2);
+    ndel[nb] = TapHalf<PREC>::lo(c2) + TapHalf<PREC>::hi(c2);
   }
 #endif
   const int a_off = (kg < 2 ? L::OFF_TAPS : L::OFF_CELLS) + li * 32 + (kg & 1) * 16;     // + tile * 1024 + sub * 512
@@ -134,74 +119,34 @@ __global__ __launch_bounds__(512, tap_bwd_q_waves(PREC, NB)) void attn_tap_bwd_q
     for (int nb = 0; nb < NB; ++nb) ycell[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
   };
 
-#if BEVR_DROP
-  auto tile = [&](const char* base, int t, uint32_t kh) {
-#else
-  [[maybe_unused]] auto tile = [&](const char* base, int t) {
-#endif
-    const bf16x8 a0 = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(base + a_off + t * 1024));
-    const bf16x8 a1 = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(base + a_off + t * 1024 + 512));
-    const bf16x8 wt = lds_tr8(base + L::OFF_TAPS + t_off + t * 1024, 512);
-    const bf16x8 wct = lds_tr8(base + L::OFF_CELLS + t_off + t * 1024, 512);
+  // one 32-key tile against the wave's row blocks (kh: the tile's key hash, dropout builds)
+  auto tile = [&](const char* base, int t, [[maybe_unused]] uint32_t kh) {
+    const TapOp<NP> a0 = tap_ld<NP>(base + a_off + t * 1024, L::OFF_LO);
+    const TapOp<NP> a1 = tap_ld<NP>(base + a_off + t * 1024 + 512, L::OFF_LO);
+    const TapOp<NP> wt = tap_ld_tr<NP>(base + L::OFF_TAPS + t_off + t * 1024, 512, L::OFF_LO);
+    const TapOp<NP> wct = tap_ld_tr<NP>(base + L::OFF_CELLS + t_off + t * 1024, 512, L::OFF_LO);
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
       if (NB > 1 && blk0 + nb >= nblk) continue;
       const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
-      const f32x4 s0 = mfma16<PREC>(a0, bop[nb], z4);
-      const f32x4 s1 = mfma16<PREC>(a1, bop[nb], z4);
-      const f32x4 p0 = mfma16<PREC>(a0, hop[nb], z4);
-      const f32x4 p1 = mfma16<PREC>(a1, hop[nb], z4);
-      u32x4 dsw;
-#if BEVR_DROP
+      const f32x4 s0 = tap_mm<PREC, true>(a0, bop[nb], z4);
+      const f32x4 s1 = tap_mm<PREC, true>(a1, bop[nb], z4);
+      const f32x4 p0 = tap_mm<PREC>(a0, hop[nb], z4);
+      const f32x4 p1 = tap_mm<PREC>(a1, hop[nb], z4);
       float ds[8];
+#if BEVR_DROP
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         ds[k] = fast_exp2(s0[k]) * (tap_drop_keep8(hrow[nb], kh, k, drop_thr) ? p0[k] : ndel[nb]);
         ds[4 + k] = fast_exp2(s1[k]) * (tap_drop_keep8(hrow[nb], kh, 4 + k, drop_thr) ? p1[k] : ndel[nb]);
       }
-#pragma unroll
-      for (int k = 0; k < 4; ++k) dsw[k] = TapHalf<PREC>::pack2(ds[2 * k], ds[2 * k + 1]);
 #else
-      dsw[0] = TapHalf<PREC>::pack2(fast_exp2(s0[0]) * p0[0], fast_exp2(s0[1]) * p0[1]);
-      dsw[1] = TapHalf<PREC>::pack2(fast_exp2(s0[2]) * p0[2], fast_exp2(s0[3]) * p0[3]);
-      dsw[2] = TapHalf<PREC>::pack2(fast_exp2(s1[0]) * p1[0], fast_exp2(s1[1]) * p1[1]);
-      dsw[3] = TapHalf<PREC>::pack2(fast_exp2(s1[2]) * p1[2], fast_exp2(s1[3]) * p1[3]);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) ds[k] = fast_exp2(k < 4 ? s0[k & 3] : s1[k & 3]) * (k < 4 ? p0[k & 3] : p1[k & 3]);
 #endif
-      const bf16x8 ds8 = __builtin_bit_cast(bf16x8, dsw);
-      ytap[nb] = mfma16<PREC>(wt, ds8, ytap[nb]);
-      ycell[nb] = mfma16<PREC>(wct, ds8, ycell[nb]);
-    }
-  };
-
-  // split mode: the same with every operand as (hi, lo); dS is split after the product
-  [[maybe_unused]] auto tile3 = [&](const char* base, int t) {
-    bf16x8 a0[2], a1[2], wt[2], wct[2];
-#pragma unroll
-    for (int pl = 0; pl < 2; ++pl) {
-      a0[pl] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(base + pl * L::OFF_LO + a_off + t * 1024));
-      a1[pl] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(base + pl * L::OFF_LO + a_off + t * 1024 + 512));
-      wt[pl] = lds_tr8(base + pl * L::OFF_LO + L::OFF_TAPS + t_off + t * 1024, 512);
-      wct[pl] = lds_tr8(base + pl * L::OFF_LO + L::OFF_CELLS + t_off + t * 1024, 512);
-    }
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) {
-      if (NB > 1 && blk0 + nb >= nblk) continue;
-      const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
-      const bf16x8 bh = bop[nb], bl = bop[NB * (NP - 1) + nb], hh = hop[nb], hl = hop[NB * (NP - 1) + nb];
-      const f32x4 s0 = mfma16s4(a0[0], a0[1], bh, bl, z4);
-      const f32x4 s1 = mfma16s4(a1[0], a1[1], bh, bl, z4);
-      const f32x4 p0 = mfma16s(a0[0], a0[1], hh, hl, z4);
-      const f32x4 p1 = mfma16s(a1[0], a1[1], hh, hl, z4);
-      float ds[8];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        ds[k] = fast_exp2(s0[k]) * p0[k];
-        ds[4 + k] = fast_exp2(s1[k]) * p1[k];
-      }
-      bf16x8 dh, dl;
-      split8v(ds, dh, dl);
-      ytap[nb] = mfma16s(wt[0], wt[1], dh, dl, ytap[nb]);
-      ycell[nb] = mfma16s(wct[0], wct[1], dh, dl, ycell[nb]);
+      const TapOp<NP> ds8 = tap_pack8<PREC>(ds);
+      ytap[nb] = tap_mm<PREC>(wt, ds8, ytap[nb]);
+      ycell[nb] = tap_mm<PREC>(wct, ds8, ycell[nb]);
     }
   };
 
@@ -223,20 +168,13 @@ __global__ __launch_bounds__(512, tap_bwd_q_waves(PREC, NB)) void attn_tap_bwd_q
         if (kg >= 2) {
           const char* img = ring + (al & (L::RING - 1)) * img_bytes + i_off;
 #pragma unroll
-          for (int nb = 0; nb < NB; ++nb)
-            bop[nb] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(img + min(blk0 + nb, nblk - 1) * 512));
-          if constexpr (X3) {
-#pragma unroll
-            for (int nb = 0; nb < NB; ++nb)
-              bop[NB * (NP - 1) + nb] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(img + rows_img * 32 + min(blk0 + nb, nblk - 1) * 512));
-          }
+          for (int nb = 0; nb < NB; ++nb) bop[nb] = tap_ld<NP>(img + min(blk0 + nb, nblk - 1) * 512, rows_img * 32);
         }
       }
 #if BEVR_DROP
       tile(base, t, tap_drop_key0(key0 + (uint32_t)__builtin_amdgcn_readfirstlane((int)ct[3]) + 32u * t, kg));
 #else
-      if constexpr (X3) tile3(base, t);
-      else tile(base, t);
+      tile(base, t, 0u);
 #endif
     }
   }
@@ -256,7 +194,7 @@ int launch(const bevr_attn_desc& d, const void* G, const void* H, const void* ta
   const int n_ph = d.n_prob * d.heads;
   const int grid = ((n_ph + 7) / 8) * 8 * d.S;
   const int nblk = (d.S + QB - 1) / QB;
-  const size_t lds = 2 * L::BUF + (size_t)L::RING * nblk * QB * 32 * (tap_x3(PREC) ? 2 : 1);
+  const size_t lds = 2 * L::BUF + (size_t)L::RING * nblk * QB * 32 * tap_np<PREC>;
   if (lds > 160 * 1024 || nblk > 28) return BEVR_E_SHAPE;
   const int nb = nblk <= 7 ? 1 : nblk <= 14 ? 2 : 4;
   const int n_cw = (nblk + nb - 1) / nb;
@@ -280,10 +218,6 @@ int bevr_tap_bwd_q_x3(const bevr_attn_desc& d, const void* G, const void* H, con
   return launch<BEVR_PREC_BF16X3>(d, G, H, tap_ws, table_pair, dG, dtable, st);
 }
 #else
-#if !BEVR_DROP
-int bevr_tap_bwd_q_x3(const bevr_attn_desc& d, const void* G, const void* H, const void* tap_ws, const float* table_pair,
-                      float* dG, float* dtable, hipStream_t st);     // attn_tap_bwd_q_x3.hip
-#endif
 #if BEVR_DROP
 extern "C" int bevr_attn_tap_bwd_q_dropout(const bevr_attn_desc* d, const void* G, const void* H, const void* tap_ws,
                                            const float* table_pair, float* dG, float* dtable, unsigned key0,

@@ -20,6 +20,12 @@
 // and recomputed by the EXACT instantiation (online maximum), which overwrites R and mref of the flagged columns.
 #include "attn_tap.h"
 
+#if BEVR_DROP
+#define BEVR_TAP_FWD_DROP_ARGS , lsum TAP_DROP_ARGS
+#else
+#define BEVR_TAP_FWD_DROP_ARGS
+#endif
+
 namespace {
 
 // NB: 16-row blocks per row-block wave (at most 7 row-block waves + the producer: fewer, fatter waves beat one wave per
@@ -32,7 +38,7 @@ namespace {
 #define TAP_FWD_WAVES(NB_) ((NB_) == 4 ? 4 : 6)
 #endif
 // (split mode: every operand twice -- 4 waves per SIMD, the fat NB = 4 instantiation 2)
-constexpr int tap_fwd_waves(int prec, int nb) { return tap_x3(prec) ? (nb == 4 ? 2 : 4) : TAP_FWD_WAVES(nb); }
+constexpr int tap_fwd_waves(int prec, int nb) { return tap_split(prec) ? (nb == 4 ? 2 : 4) : TAP_FWD_WAVES(nb); }
 template <int PREC, int NB, bool EXACT>
 __global__ __launch_bounds__(512, tap_fwd_waves(PREC, NB)) void attn_tap_fwd_kernel(
     bevr_attn_desc d, const char* __restrict__ G, const char* __restrict__ tap_ws,
@@ -42,8 +48,7 @@ __global__ __launch_bounds__(512, tap_fwd_waves(PREC, NB)) void attn_tap_fwd_ker
 #endif
     ) {
   typedef LdsTp<PREC> L;
-  constexpr bool X3 = tap_x3(PREC);
-  constexpr int NP = X3 ? 2 : 1;
+  constexpr int NP = tap_np<PREC>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
   const int n_ph = d.n_prob * d.heads;
@@ -76,31 +81,21 @@ __global__ __launch_bounds__(512, tap_fwd_waves(PREC, NB)) void attn_tap_fwd_ker
 
   // ---- row-block waves ------------------------------------------------------------------------------------
   const int blk0 = wave * NB;
-  // B operand: lanes 0..31 G[q][8 kg ..] (constant), lanes 32..63 the chunk's table side (per origin); split mode: [NB + nb]
-  // the lo parts
-  bf16x8 bop[NB * NP];
+  // B operand: lanes 0..31 G[q][8 kg ..] (constant), lanes 32..63 the chunk's table side (per origin)
+  TapOp<NP> bop[NB];
   f32x4 r[NB];        // R[slot 4 kg + e][q]
   float sh[NB];       // EXACT: the running maximum relative to mref
   size_t mqv[NB];
+  const size_t g_lo = (size_t)n_ph * Mp * TAP_SLOTS * 2;     // G's lo plane
 #pragma unroll
   for (int nb = 0; nb < NB; ++nb) {
     const int blk = min(blk0 + nb, nblk - 1);
     const size_t mq = (size_t)ph * Mp + (size_t)j * d.Sp + blk * QB + li;
     mqv[nb] = mq;
-    u32x4 g = {0u, 0u, 0u, 0u};
-    if (kg < 2) g = *reinterpret_cast<const u32x4*>(G + (mq * TAP_SLOTS + 8 * kg) * 2);
-    bop[nb] = __builtin_bit_cast(bf16x8, g);
+    bop[nb] = TapOp<NP>{};
+    if (kg < 2) bop[nb] = tap_ld<NP>(G + (mq * TAP_SLOTS + 8 * kg) * 2, g_lo);
     r[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
     sh[nb] = -3.0e38f;
-  }
-  if constexpr (X3) {   // G's lo plane
-    const size_t g_lo = (size_t)n_ph * Mp * TAP_SLOTS * 2;
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) {
-      u32x4 gl = {0u, 0u, 0u, 0u};
-      if (kg < 2) gl = *reinterpret_cast<const u32x4*>(G + g_lo + (mqv[nb] * TAP_SLOTS + 8 * kg) * 2);
-      bop[NB * (NP - 1) + nb] = __builtin_bit_cast(bf16x8, gl);
-    }
   }
 #if BEVR_DROP
   uint32_t hrow[NB];  // the row part of the keep hash, out of the key loop
@@ -116,20 +111,18 @@ __global__ __launch_bounds__(512, tap_fwd_waves(PREC, NB)) void attn_tap_fwd_ker
   const int t_off = L::OFF_TAPS + (4 * kg + (li >> 2)) * 32 + (lane & 3) * 8;             // + tile * 1024, second block + 512
   const int i_off = li * 32 + (kg & 1) * 16;                                             // in a table image, + block * 512
   // the B operand exists once per tile slot of an emission (their chunk origins may differ); lanes 0..31 of both hold G
-  bf16x8 bop1[NB * NP];
+  TapOp<NP> bop1[NB];
 #pragma unroll
-  for (int nb = 0; nb < NB * NP; ++nb) bop1[nb] = bop[nb];
+  for (int nb = 0; nb < NB; ++nb) bop1[nb] = bop[nb];
   int have0 = 0, have1 = 0;      // allocation numbers of the table images in bop / bop1 (0: the zeroed image)
 
   // one 32-key tile against one row block: S^T (two 16-key sub-tiles) -> weights -> R += w^T P
-#if BEVR_DROP
-  auto tile = [&](const bf16x8& a0, const bf16x8& a1, const bf16x8& wt, const bf16x8& b, int nb, uint32_t kh) {
-#else
-  [[maybe_unused]] auto tile = [&](const bf16x8& a0, const bf16x8& a1, const bf16x8& wt, const bf16x8& b, int nb) {
-#endif
+  // (kh: the tile's key hash, dropout builds)
+  auto tile = [&](const TapOp<NP>& a0, const TapOp<NP>& a1, const TapOp<NP>& wt, const TapOp<NP>& b, int nb,
+                  [[maybe_unused]] uint32_t kh) {
     const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
-    f32x4 s0 = mfma16<PREC>(a0, b, z4);
-    f32x4 s1 = mfma16<PREC>(a1, b, z4);
+    f32x4 s0 = tap_mm<PREC, true>(a0, b, z4);
+    f32x4 s1 = tap_mm<PREC, true>(a1, b, z4);
     if constexpr (EXACT) {
       float tm = fmaxf(fmaxf(fmaxf(s0[0], s0[1]), fmaxf(s0[2], s0[3])), fmaxf(fmaxf(s1[0], s1[1]), fmaxf(s1[2], s1[3])));
       tm = fmaxf(tm, __shfl_xor(tm, 16));
@@ -144,14 +137,10 @@ __global__ __launch_bounds__(512, tap_fwd_waves(PREC, NB)) void attn_tap_fwd_ker
       s0 -= mn;
       s1 -= mn;
     }
-    u32x4 pw;
-#if BEVR_DROP
     float p[8];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      p[k] = fast_exp2(s0[k]);
-      p[4 + k] = fast_exp2(s1[k]);
-    }
+    for (int k = 0; k < 8; ++k) p[k] = fast_exp2(k < 4 ? s0[k & 3] : s1[k & 3]);
+#if BEVR_DROP
     ls[nb] += ((p[0] + p[1]) + (p[2] + p[3])) + ((p[4] + p[5]) + (p[6] + p[7]));
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
@@ -160,42 +149,15 @@ __global__ __launch_bounds__(512, tap_fwd_waves(PREC, NB)) void attn_tap_fwd_ker
       // v_perm, one more instruction per pair)
       asm("" : "+v"(p[k]));
     }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) pw[k] = TapHalf<PREC>::pack2(p[2 * k], p[2 * k + 1]);
-#else
-    pw[0] = TapHalf<PREC>::pack2(fast_exp2(s0[0]), fast_exp2(s0[1]));
-    pw[1] = TapHalf<PREC>::pack2(fast_exp2(s0[2]), fast_exp2(s0[3]));
-    pw[2] = TapHalf<PREC>::pack2(fast_exp2(s1[0]), fast_exp2(s1[1]));
-    pw[3] = TapHalf<PREC>::pack2(fast_exp2(s1[2]), fast_exp2(s1[3]));
 #endif
-    r[nb] = mfma16<PREC>(wt, __builtin_bit_cast(bf16x8, pw), r[nb]);
+    r[nb] = tap_mm<PREC>(wt, tap_pack8<PREC>(p), r[nb]);
   };
-
-  // split mode: the same with every operand as (hi, lo)
-  [[maybe_unused]] auto tile3 = [&](const bf16x8 (&a0)[2], const bf16x8 (&a1)[2], const bf16x8 (&wt)[2], const bf16x8& bh,
-                                    const bf16x8& bl, int nb) {
-    const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
-    f32x4 s0 = mfma16s4(a0[0], a0[1], bh, bl, z4);
-    f32x4 s1 = mfma16s4(a1[0], a1[1], bh, bl, z4);
-    if constexpr (EXACT) {
-      float tm = fmaxf(fmaxf(fmaxf(s0[0], s0[1]), fmaxf(s0[2], s0[3])), fmaxf(fmaxf(s1[0], s1[1]), fmaxf(s1[2], s1[3])));
-      tm = fmaxf(tm, __shfl_xor(tm, 16));
-      tm = fmaxf(tm, __shfl_xor(tm, 32));
-      const float mn = fmaxf(sh[nb], tm);
-      r[nb] *= fast_exp2(sh[nb] - mn);
-      sh[nb] = mn;
-      s0 -= mn;
-      s1 -= mn;
-    }
-    float p[8];
+  // a chunk's table side out of ring image `al` (lanes 32..63)
+  auto ring_load = [&](TapOp<NP> (&b)[NB], int al) {
+    if (kg < 2) return;
+    const char* img = ring + (al & (L::RING - 1)) * img_bytes + i_off;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      p[k] = fast_exp2(s0[k]);
-      p[4 + k] = fast_exp2(s1[k]);
-    }
-    bf16x8 ph8, pl8;
-    split8v(p, ph8, pl8);
-    r[nb] = mfma16s(wt[0], wt[1], ph8, pl8, r[nb]);
+    for (int nb = 0; nb < NB; ++nb) b[nb] = tap_ld<NP>(img + min(blk0 + nb, nblk - 1) * 512, rows_img * 32);
   };
 
   for (int e = 0;; ++e) {
@@ -207,71 +169,29 @@ __global__ __launch_bounds__(512, tap_fwd_waves(PREC, NB)) void attn_tap_fwd_ker
     const int al0 = __builtin_amdgcn_readfirstlane((int)ct[1]), al1 = __builtin_amdgcn_readfirstlane((int)ct[2]);
     if (al0 != have0) {   // uniform, rare: another chunk origin
       have0 = al0;
-      if (kg >= 2) {
-        const char* img = ring + (al0 & (L::RING - 1)) * img_bytes + i_off;
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb)
-          bop[nb] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(img + min(blk0 + nb, nblk - 1) * 512));
-        if constexpr (X3) {
-#pragma unroll
-          for (int nb = 0; nb < NB; ++nb)
-            bop[NB + nb] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(img + rows_img * 32 + min(blk0 + nb, nblk - 1) * 512));
-        }
-      }
+      ring_load(bop, al0);
     }
     if (al1 != have1) {
       have1 = al1;
-      if (kg >= 2) {
-        const char* img = ring + (al1 & (L::RING - 1)) * img_bytes + i_off;
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb)
-          bop1[nb] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(img + min(blk0 + nb, nblk - 1) * 512));
-        if constexpr (X3) {
-#pragma unroll
-          for (int nb = 0; nb < NB; ++nb)
-            bop1[NB + nb] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(img + rows_img * 32 + min(blk0 + nb, nblk - 1) * 512));
-        }
-      }
+      ring_load(bop1, al1);
     }
     // both tile slots, unconditionally: a slot without live keys holds masked keys only (weight 0)
-    if constexpr (X3) {
-      bf16x8 a[4][2], wt[2][2];
+    TapOp<NP> a[4], wt[2];     // A of sub-tile k = 2 tile + sub, w^T of tile 0 / 1
 #pragma unroll
-      for (int pl = 0; pl < 2; ++pl) {
+    for (int k = 0; k < 4; ++k) a[k] = tap_ld<NP>(base + a_off + 512 * k, L::OFF_LO);
 #pragma unroll
-        for (int k = 0; k < 4; ++k)
-          a[k][pl] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(base + pl * L::OFF_LO + a_off + 512 * k));
-        wt[0][pl] = lds_tr8(base + pl * L::OFF_LO + t_off, 512);
-        wt[1][pl] = lds_tr8(base + pl * L::OFF_LO + t_off + 1024, 512);
-      }
-#pragma unroll
-      for (int nb = 0; nb < NB; ++nb) {
-        if (NB > 1 && blk0 + nb >= nblk) continue;
-        tile3(a[0], a[1], wt[0], bop[nb], bop[NB * (NP - 1) + nb], nb);
-        tile3(a[2], a[3], wt[1], bop1[nb], bop1[NB * (NP - 1) + nb], nb);
-      }
-      continue;
-    }
-    const bf16x8 a00 = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(base + a_off));
-    const bf16x8 a01 = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(base + a_off + 512));
-    const bf16x8 a10 = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(base + a_off + 1024));
-    const bf16x8 a11 = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(base + a_off + 1536));
-    const bf16x8 wt0 = lds_tr8(base + t_off, 512);
-    const bf16x8 wt1 = lds_tr8(base + t_off + 1024, 512);
+    for (int t = 0; t < 2; ++t) wt[t] = tap_ld_tr<NP>(base + t_off + 1024 * t, 512, L::OFF_LO);
 #if BEVR_DROP
     const uint32_t kh0 = tap_drop_key0(key0 + (uint32_t)__builtin_amdgcn_readfirstlane((int)ct[3]), kg);
     const uint32_t kh1 = kh0 + 32u * 0xC2B2AE3Du;
+#else
+    const uint32_t kh0 = 0u, kh1 = 0u;
 #endif
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
       if (NB > 1 && blk0 + nb >= nblk) continue;
-#if BEVR_DROP
-      tile(a00, a01, wt0, bop[nb], nb, kh0);
-      tile(a10, a11, wt1, bop1[nb], nb, kh1);
-#else
-      tile(a00, a01, wt0, bop[nb], nb);
-      tile(a10, a11, wt1, bop1[nb], nb);
-#endif
+      tile(a[0], a[1], wt[0], bop[nb], nb, kh0);
+      tile(a[2], a[3], wt[1], bop1[nb], nb, kh1);
     }
   }
 
@@ -315,17 +235,12 @@ int launch(const bevr_attn_desc& d, const void* G, const void* tap_ws, const flo
   const int n_ph = d.n_prob * d.heads;
   const int grid = ((n_ph + 7) / 8) * 8 * d.S;
   const int nblk = (d.S + QB - 1) / QB;
-  const size_t lds = 2 * L::BUF + (size_t)L::RING * nblk * QB * 32 * (tap_x3(PREC) ? 2 : 1);
+  const size_t lds = 2 * L::BUF + (size_t)L::RING * nblk * QB * 32 * tap_np<PREC>;
   if (lds > 160 * 1024) return BEVR_E_SHAPE;
   const int nb = nblk <= 7 ? 1 : nblk <= 14 ? 2 : 4;      // row blocks per wave: at most 7 row-block waves + the producer
   if (nblk > 28) return BEVR_E_SHAPE;
   const int n_cw = (nblk + nb - 1) / nb;
   const dim3 block(64 * (n_cw + 1));
-#if BEVR_DROP
-#define BEVR_TAP_FWD_DROP_ARGS , lsum TAP_DROP_ARGS
-#else
-#define BEVR_TAP_FWD_DROP_ARGS
-#endif
 #define BEVR_TAP_LAUNCH(NB_, EX_)                                                                                     \
   hipLaunchKernelGGL((attn_tap_fwd_kernel<PREC, NB_, EX_>), dim3(grid), block, lds, st, d, (const char*)G,          \
                      (const char*)tap_ws, (const char*)table_pair, mref, R, flags BEVR_TAP_FWD_DROP_ARGS)
@@ -349,10 +264,6 @@ int bevr_tap_fwd_x3(const bevr_attn_desc& d, const void* G, const void* tap_ws, 
   return launch<BEVR_PREC_BF16X3>(d, G, tap_ws, table_pair, mref, R, flags, st);
 }
 #else
-#if !BEVR_DROP
-int bevr_tap_fwd_x3(const bevr_attn_desc& d, const void* G, const void* tap_ws, const float* table_pair, float* mref,
-                    float* R, int* flags, hipStream_t st);     // attn_tap_fwd_x3.hip
-#endif
 #if BEVR_DROP
 extern "C" int bevr_attn_tap_fwd_dropout(const bevr_attn_desc* d, const void* G, const void* tap_ws,
                                          const float* table_pair, float* mref, float* R, float* lsum, int* flags,

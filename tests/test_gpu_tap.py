@@ -33,6 +33,12 @@ KERNEL_CASES = {
     "unsorted_wide": dict(P=1, h=2, S=18, N=200, Wt=2 * 18 * 5 - 1, spread=(12.0, 30.0), sort=False, seed=2),
     "three_row_blocks": dict(P=1, h=1, S=40, N=1000, Wt=2 * 40 * 5 - 1, seed=3),
     "fp16": dict(P=1, h=2, S=24, N=400, Wt=2 * 24 * 3 - 1, seed=5, prec=_lib.PREC_F16, gscale=2.0, headroom=8.0),
+    # More than one 16-row block per wave (the cases above: S <= 40, one block): the smallest sizes that select the NB = 2
+    # (8 row blocks, the last wave with a partial share) and NB = 4 (15 row blocks) instantiations of the forward and the
+    # query-side backward.  320 key slots, the last 7 of them masked padding; keys as in `unsorted_wide`: tiles emitted in
+    # several masked passes, and the key side's second (per-pair gather) launch has work
+    "two_blocks_per_wave": dict(P=1, h=1, S=120, N=313, Wt=2 * 120 * 2 - 1, spread=(12.0, 30.0), sort=False, seed=8),
+    "four_blocks_per_wave": dict(P=1, h=1, S=232, N=313, Wt=2 * 232 * 2 - 1, spread=(12.0, 30.0), sort=False, seed=9),
 }
 
 

@@ -28,11 +28,13 @@ REGION_DROP = ("bevr_attn_fwd_dropout", "bevr_attn_bwd_q_dropout", "bevr_attn_bw
 TAP_PLAIN = ("bevr_attn_tap_fwd", "bevr_attn_tap_bwd_q", "bevr_attn_tap_bwd_k")
 
 
-@pytest.mark.parametrize("name", ["sorted", "ragged", "unsorted_wide", "three_row_blocks", "fp16"])
+@pytest.mark.parametrize("name", ["sorted", "ragged", "unsorted_wide", "three_row_blocks", "fp16", "two_blocks_per_wave",
+                                  "four_blocks_per_wave"])
 def test_tap_dropout_entry_points_match_their_float64_definition(name):
     """The cases and limits of tests/test_gpu_tap.py::test_tap_entry_points_match_their_float64_definition (lim_f, lim_g =
     1e-3, 4e-3 in fp16 and 4e-3, 3e-2 in bf16; LSE at 10 lim_f), p = 0.3, the segment's keys hashed from key0 = 1234.
-    `unsorted_wide`: every 32-key tile is emitted in several masked passes -- a key has one keep decision in all of them."""
+    `unsorted_wide`: every 32-key tile is emitted in several masked passes -- a key has one keep decision in all of them.
+    `two_blocks_per_wave`, `four_blocks_per_wave`: the NB = 2 and NB = 4 instantiations (S = 120, S = 232)."""
     import tap_drop_check
     r = tap_drop_check.check_case(name, key0=1234, p=0.3, **KERNEL_CASES[name])
     f16 = KERNEL_CASES[name].get("prec") == _lib.PREC_F16
