@@ -20,23 +20,9 @@
 //    slab does not fit the ring (keys of the block far apart in table space).
 #include "attn_kstage.h"
 
-#ifdef BEVR_PROF
-__device__ unsigned long long bevr_prof_k[16];
-extern "C" int bevr_debug_prof_k(unsigned long long* out, int reset) {
-  if (reset) { unsigned long long z[16] = {0}; return (int)hipMemcpyToSymbol(HIP_SYMBOL(bevr_prof_k), z, sizeof(z)); }
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(bevr_prof_k), 16 * 8);
-}
-__device__ __forceinline__ unsigned long long prof_now(float dep) {
-  unsigned long long t;
-  asm volatile("s_nop 0\n s_waitcnt lgkmcnt(0)\n s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(t) : "v"(dep) : "memory");
-  return t;
-}
-#define PROF_TD(var, dep) const unsigned long long var = prof_now(dep)
-#define PROF_ADD(i, v) pacc[i] += (v)
-#else
-#define PROF_TD(var, dep)
-#define PROF_ADD(i, v)
-#endif
+#include "bevr_prof.h"
+
+BEVR_PROF_DEFINE(bwd_k, 16)   // window kernel, waves 0 and 11, 8 slots each: phases of an iteration, the whole, the count
 
 namespace {
 
@@ -45,36 +31,15 @@ constexpr int KEYS_WG = 384;    // keys per workgroup, both kernels: the unit of
 // bounding box of a key block in table coordinates (padded keys excluded)
 struct KBox { int amin, amax; float bmin, bmax; };
 
-__device__ __forceinline__ int wred_min_i(int v) {
-#pragma unroll
-  for (int s = 32; s > 0; s >>= 1) v = min(v, __shfl_xor(v, s));
-  return v;
-}
-__device__ __forceinline__ int wred_max_i(int v) {
-#pragma unroll
-  for (int s = 32; s > 0; s >>= 1) v = max(v, __shfl_xor(v, s));
-  return v;
-}
-__device__ __forceinline__ float wred_min_f(float v) {
-#pragma unroll
-  for (int s = 32; s > 0; s >>= 1) v = fminf(v, __shfl_xor(v, s));
-  return v;
-}
-__device__ __forceinline__ float wred_max_f(float v) {
-#pragma unroll
-  for (int s = 32; s > 0; s >>= 1) v = fmaxf(v, __shfl_xor(v, s));
-  return v;
-}
-
 // Workgroup-wide box from per-lane partial boxes (empty: lo > hi).  red: n_wave KBox slots in LDS.  Ends with a
 // barrier; the result is uniform.
 __device__ __forceinline__ KBox wg_key_box(int a_lo, int a_hi, float b_lo, float b_hi, KBox* red, int n_wave, int wave,
                                            int lane) {
   KBox w;
-  w.amin = wred_min_i(a_lo);
-  w.amax = wred_max_i(a_hi);
-  w.bmin = wred_min_f(b_lo);
-  w.bmax = wred_max_f(b_hi);
+  w.amin = lanes_min<64>(a_lo);
+  w.amax = lanes_max<64>(a_hi);
+  w.bmin = lanes_min<64>(b_lo);
+  w.bmax = lanes_max<64>(b_hi);
   if (lane == 0) red[wave] = w;
   __syncthreads();
   KBox r = red[0];
@@ -112,16 +77,12 @@ __device__ __forceinline__ Slab make_slab(const KBox& kb, const bevr_attn_desc& 
   return sl;
 }
 
-// clamp a key's table coordinates exactly as make_keyc does and split off the integer row
+// a key's clamped table coordinates (key_clamp, as make_keyc) with the integer row split off
 __device__ __forceinline__ void key_split(float a, float b, const bevr_attn_desc& d, int& A, float& fy, float& bc) {
-  const float aL = -(float)(d.Sp + 1), aU = (float)(d.Ht + 1);
-  const float half = (float)((d.Wt) / 2);
-  const float bL = -(half + 2.0f), bU = (float)(d.Wt + 1);
-  a = fminf(fmaxf(a, aL), aU);
-  bc = fminf(fmaxf(b, bL), bU);
-  const float af = floorf(a);
-  A = (int)af;
-  fy = a - af;
+  const KeyClamp c = key_clamp(a, b, d);
+  bc = c.b;
+  A = (int)c.af;
+  fy = c.a - c.af;
 }
 
 // =========================================================================================================
@@ -274,11 +235,9 @@ __global__ __launch_bounds__(TW, 3) void attn_bwd_k_win_kernel(
   const size_t trow0 = (size_t)(box.amin + d.y_off);
   __syncthreads();
 
-#ifdef BEVR_PROF
-  unsigned long long pacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#endif
+  PROF_ACC(8);
   for (int it = 0; it < n_it; ++it) {
-    PROF_TD(t0, 0.f);
+    PROF_T_LGKM(t0, 0.f);
     const int buf = it & 1;
     const char* base = smem + buf * L::BUF;
     const int t_first = first_tile(it);
@@ -344,7 +303,7 @@ __global__ __launch_bounds__(TW, 3) void attn_bwd_k_win_kernel(
         }
       }
     }
-    PROF_TD(t1, 0.f);
+    PROF_T_LGKM(t1, 0.f);
     PROF_ADD(0, t1 - t0);
 
 #pragma unroll
@@ -388,7 +347,7 @@ __global__ __launch_bounds__(TW, 3) void attn_bwd_k_win_kernel(
         kmask |= (keep ? 1u : 0u) << r;
       }
 #endif
-      PROF_TD(t2, s[0] + dp[15]);
+      PROF_T_LGKM(t2, s[0] + dp[15]);
       PROF_ADD(1, t2 - t1);
 
       const int ioff = (rb * 32 + 4 * hi) * 4;
@@ -435,7 +394,7 @@ __global__ __launch_bounds__(TW, 3) void attn_bwd_k_win_kernel(
 #pragma unroll
       for (int r = 0; r < 16; ++r) s[r] = ((kmask >> r) & 1u) ? s[r] * ksc : 0.f;
 #endif
-      PROF_TD(t3, sa + sb + s[15]);
+      PROF_T_LGKM(t3, sa + sb + s[15]);
       PROF_ADD(2, t3 - t2);
       {
         Frag<PREC> dotf;
@@ -447,13 +406,13 @@ __global__ __launch_bounds__(TW, 3) void attn_bwd_k_win_kernel(
         load_perm(qtf, base + 2 * L::TILE_Q + lq * L::TSTRIDE + sub * 32 * EB, hi);
         dk[w] = mma_acc_b(qtf, dp, dk[w]);
       }
-      PROF_TD(t4, dk[w][0] + dv[w][0]);
+      PROF_T_LGKM(t4, dk[w][0] + dv[w][0]);
       PROF_ADD(3, t4 - t3);
     }
 
     }   // sub-tiles
 
-    PROF_TD(t5, 0.f);
+    PROF_T_LGKM(t5, 0.f);
     if (pf_units > 0) {
 #pragma unroll
       for (int k = 0; k < PF; ++k) {
@@ -464,19 +423,15 @@ __global__ __launch_bounds__(TW, 3) void attn_bwd_k_win_kernel(
       }
     }
     if (it + 1 < n_it) qs.store(tid, smem + (buf ^ 1) * L::BUF);
-    PROF_TD(t6, 0.f);
+    PROF_T_LGKM(t6, 0.f);
     __syncthreads();
-    PROF_TD(t7, 0.f);
+    PROF_T_LGKM(t7, 0.f);
     PROF_ADD(4, t6 - t5);
     PROF_ADD(5, t7 - t6);
     PROF_ADD(6, t7 - t0);
     PROF_ADD(7, 1);
   }
-#ifdef BEVR_PROF
-  if (lane == 0 && (wave == 0 || wave == 11)) {
-    for (int i = 0; i < 8; ++i) atomicAdd(&bevr_prof_k[(wave ? 8 : 0) + i], pacc[i]);
-  }
-#endif
+  PROF_FLUSH(bwd_k, wave ? 8 : 0, lane == 0 && (wave == 0 || wave == 11));
 
   // ---- epilogue -------------------------------------------------------------------------------------
 #pragma unroll

@@ -24,25 +24,9 @@
 #include <type_traits>
 #include "attn_tile.h"
 
-#ifdef BEVR_PROF
-__device__ unsigned long long bevr_prof[16];
-extern "C" int bevr_debug_prof(unsigned long long* out, int reset) {
-  if (reset) { unsigned long long z[16] = {0}; return (int)hipMemcpyToSymbol(HIP_SYMBOL(bevr_prof), z, sizeof(z)); }
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(bevr_prof), 16 * 8);
-}
-__device__ __forceinline__ unsigned long long prof_now(float dep) {
-  unsigned long long t;
-  asm volatile("s_nop 0\n s_waitcnt vmcnt(0) lgkmcnt(0)\n s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(t) : "v"(dep) : "memory");
-  return t;
-}
-#define PROF_T(var) const unsigned long long var = prof_now(0.f)
-#define PROF_TD(var, dep) const unsigned long long var = prof_now(dep)
-#define PROF_ADD(i, v) pacc[i] += (v)
-#else
-#define PROF_T(var)
-#define PROF_TD(var, dep)
-#define PROF_ADD(i, v)
-#endif
+#include "bevr_prof.h"
+
+BEVR_PROF_DEFINE(bwd_q, 16)   // waves 0 and 7, 8 slots each: phases of a step, the region moves, the step count
 
 namespace {
 
@@ -71,44 +55,6 @@ template <int PREC> struct LdsQ {
 };
 
 constexpr int QROWS = 31;   // query rows per tile: lane 31 of each 32-lane half carries no query (see the kernel header)
-
-// round-to-nearest-even float -> int (v_rndne_f32 + v_cvt_i32_f32), as plain C so that the compiler sees the read.
-// Round 1 used inline asm (v_cvt_rpi_i32_f32, one instruction).  Inline asm is opaque to the hazard recognizer: fed
-// directly by a v_dot2c_f32_bf16 result (two instructions earlier in the stream) it read a stale register and the
-// bf16-mode table gradient came out 65 % wrong while the same arithmetic through v_fma_f32 was right
-// (tools/micro/dot2_test.hip shows the instruction itself is exact).
-__device__ __forceinline__ int cvt_rpi(float x) { return (int)__builtin_rintf(x); }
-
-// the value of the lane below (lane - 1) across the whole wave; lane 0 receives 0 (v_mov_b32_dpp wave_shr:1)
-__device__ __forceinline__ float lane_below(float x) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x138, 0xf, 0xf, true));
-}
-
-// Fixed-point accumulation cell: 64-bit in both precision modes.
-//   unit = ln2 * bound * 2^-30, bound >= max |P (dP - delta)| over all pairs (handed in by the caller as grad_scale);
-//   one contribution converts to a 32-bit integer (v_cvt_rpi, round to nearest: truncation would bias the sum of
-//   many small same-sign contributions) and is sign-extended into the 64-bit cell, so a cell can take 2^32
-//   contributions of the largest possible size before it wraps -- more than a launch has pairs per cell.
-//   32-bit cells (round 1, bf16 mode: ds_add_u32 is 4.4 clk, ds_add_u64 6.3) cannot hold both ends: a cell of the
-//   pinned-key box receives ~10^5 contributions per region, so a unit that is safe against wrap-around is
-//   ~bound * 2^-14, far above a typical contribution (P ~ 1/N): at S = 200 the table gradient came out 67 % wrong
-//   against the f32 mode (tests/test_gpu_fullsize.py).  Native LDS float atomics are no way out on gfx950 either:
-//   ds_add_f32 / ds_pk_add_bf16 retire ~3 clk per active LANE (193 clk per wave instruction; tools/micro/lds_bench.hip).
-struct AccCell {
-  typedef unsigned long long type;
-  static __device__ __forceinline__ type from_int(int v) {
-    return ((unsigned long long)(unsigned)(v >> 31) << 32) | (unsigned)v;
-  }
-  static __device__ __forceinline__ type from(float x) { return from_int(cvt_rpi(x)); }
-  // whole 64-bit value at once: converting the halves separately rounds the low word of a small NEGATIVE sum
-  // (hi = -1, lo = 2^32 - k) to a multiple of 256 units before the halves cancel -- up to 128 units of error per
-  // flushed cell, which over the thousands of flushes a table entry receives was 1.3 % of the S = 200 table gradient
-  static __device__ __forceinline__ float to_float(type v) {
-    const int lo = (int)(unsigned)v, hi = (int)(unsigned)(v >> 32);
-    if (hi == (lo >> 31)) return (float)lo;   // fits 32 bits (nearly always): one conversion instead of the emulated 64-bit one
-    return (float)(long long)v;
-  }
-};
 
 template <int PREC>
 __global__ __launch_bounds__(TQ, is16(PREC) ? 4 : 2) void attn_bwd_q_kernel(
@@ -337,14 +283,12 @@ __global__ __launch_bounds__(TQ, is16(PREC) ? 4 : 2) void attn_bwd_q_kernel(
     dc0 = 1 << 20; dc1 = -1; dr0 = 1 << 20; dr1 = -1;
   };
 
-#ifdef BEVR_PROF
-  unsigned long long pacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#endif
+  PROF_ACC(8);
   // boxes of the two 32-key halves of a step: uniform (scalar loads), fetched one step ahead
   StepBox sb_cur[2] = {kbox[0], kbox[1]};
   StepBox sb_nxt[2] = {kbox[2 * min(1, n_step - 1)], kbox[2 * min(1, n_step - 1) + 1]};
   for (int step = 0; step < n_step; ++step) {
-    PROF_T(t0);
+    PROF_T(t0, 0.f);
     // single staging buffer: the registers hold this step's tiles (loaded during the previous step); every wave
     // finished reading the previous tiles at the barrier that ended the previous step
     const char* base = smem;
@@ -358,7 +302,7 @@ __global__ __launch_bounds__(TQ, is16(PREC) ? 4 : 2) void attn_bwd_q_kernel(
     sb_nxt[1] = kbox[2 * min(step + 2, n_step - 1) + 1];
     // if the whole step's box fits, both halves share one region test (fewer moves); else the halves go separately
     const WinInfo wi_step = make_wininfo(box_union(sb0, sb1), jrx_lo, jrx_hi, CAP);
-    PROF_T(t1);
+    PROF_T(t1, 0.f);
     PROF_ADD(3, t1 - t0);   // staging store + barrier + box bookkeeping
     const KeyW* kc0 = reinterpret_cast<const KeyW*>(base + 2 * L::R_BYTES + L::T_BYTES);
 
@@ -389,7 +333,7 @@ __global__ __launch_bounds__(TQ, is16(PREC) ? 4 : 2) void attn_bwd_q_kernel(
           BEVR_ASSERT(wi.ok);
         }
         BEVR_ASSERT_WG_UNIFORM(wi.xlo * 131 + wi.amin * 7 + wi.ncols + gsel * 977);
-        PROF_T(tp);
+        PROF_T(tp, 0.f);
         // ---- this pass's table window ------------------------------------------------------------------
         if (!region_contains(rg, wi, CAP)) {
           // every wave must be done with the taps and adds of the previous half / pass of this step
@@ -422,7 +366,7 @@ __global__ __launch_bounds__(TQ, is16(PREC) ? 4 : 2) void attn_bwd_q_kernel(
           __syncthreads();
           PROF_ADD(5, 1);
         }
-        PROF_T(tq);
+        PROF_T(tq, 0.f);
         PROF_ADD(0, tq - tp);   // region handling (moves: flush + refill + barriers)
         {   // the pass's cells become dirty (region coordinates)
           dc0 = min(dc0, wi.xlo - rg.ax0);
@@ -485,7 +429,7 @@ __global__ __launch_bounds__(TQ, is16(PREC) ? 4 : 2) void attn_bwd_q_kernel(
             dp[r] = bevr_drop_keep(hrow, (uint32_t)(step * KT + kh * 32 + crow(r, hi)), drop_thr) ? fmaf(ksc, dp[r] - nd2, nd2) : nd2;
         }
 #endif
-        PROF_TD(t2, s[0] + dp[15]);
+        PROF_T(t2, s[0] + dp[15]);
         PROF_ADD(1, t2 - tq);
 
         {
@@ -567,14 +511,14 @@ __global__ __launch_bounds__(TQ, is16(PREC) ? 4 : 2) void attn_bwd_q_kernel(
             e0 = e1; e1 = e2; ta = na; tb = nb;
           }
         }
-        PROF_TD(t3, s[15]);
+        PROF_T(t3, s[15]);
         PROF_ADD(2, t3 - t2);
         {
           Frag<PREC> ktf;
           load_perm(ktf, base + 2 * L::R_BYTES + lq * L::T_STRIDE + kh * 32 * EB, hi);
           dq = mma_acc_b(ktf, s, dq);
         }
-        PROF_TD(t3b, dq[0]);
+        PROF_T(t3b, dq[0]);
         PROF_ADD(6, t3b - t3);
       }
 
@@ -646,17 +590,13 @@ __global__ __launch_bounds__(TQ, is16(PREC) ? 4 : 2) void attn_bwd_q_kernel(
       }
     }
 
-    PROF_T(t4);
+    PROF_T(t4, 0.f);
     __syncthreads();   // every wave is done with the staged tiles (and with the region, should the next step move it)
-    PROF_T(t5);
+    PROF_T(t5, 0.f);
     PROF_ADD(4, t5 - t4);
     PROF_ADD(7, 1);
   }
-#ifdef BEVR_PROF
-  if (lane == 0 && (wave == 0 || wave == NWAVE - 1)) {
-    for (int i = 0; i < 8; ++i) atomicAdd(&bevr_prof[(wave ? 8 : 0) + i], pacc[i]);
-  }
-#endif
+  PROF_FLUSH(bwd_q, wave ? 8 : 0, lane == 0 && (wave == 0 || wave == NWAVE - 1));
   flush_and_clear(rg);
 
   // ---- store dQ (ln2 of dS = ln2 P (dP - delta) and the 2^-e of the cell scale applied here) -----------------------------------------------

@@ -46,24 +46,9 @@
 #define BEVR_GATHER_ROWS 0
 #endif
 
-#if defined(BEVR_GPROF) && !BEVR_GATHER_ROWS
-__device__ unsigned long long bevr_prof_gather[32];
-extern "C" int bevr_debug_prof_gather(unsigned long long* out, int reset) {
-  if (reset) { unsigned long long z[32] = {0}; return (int)hipMemcpyToSymbol(HIP_SYMBOL(bevr_prof_gather), z, sizeof(z)); }
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(bevr_prof_gather), 32 * 8);
-}
-__device__ __forceinline__ unsigned long long gprof_now() {
-  unsigned long long t;
-  asm volatile("s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(t) : : "memory");
-  return t;
-}
-#define GPROF(var) const unsigned long long var = gprof_now()
-#define GPROF_ADD(i, v) gacc[i] += (v)
-#define BEVR_GPROF_ON 1
-#else
-#define GPROF(var)
-#define GPROF_ADD(i, v)
-#endif
+#include "bevr_prof.h"
+
+BEVR_PROF_DEFINE(gather, 32)   // 8 slots each: the producer wave (at 0), row-block waves 0 (at 8) and 3 (at 16)
 
 namespace {
 
@@ -331,15 +316,13 @@ __global__ __launch_bounds__(512, 4) void BEVR_GATHER_KERNEL(
       stage(cur, 0, more ? &nxt : nullptr);
       wait_vm0();
     }
-#ifdef BEVR_GPROF_ON
-    unsigned long long gacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#endif
+    PROF_ACC(8);
     // iteration e: the row-block waves work on emission e; the producer stages emission e + 1 (`nxt`), fills its share of
     // window e + 1 and describes emission e + 2
     for (int e = 0;; ++e) {
-      GPROF(p0);
+      PROF_T_FREE(p0);
       barrier_lds();      // emission e and window e are complete; buffer / window (e + 1) & 1 are free
-      GPROF(p1);
+      PROF_T_FREE(p1);
       if (!more) {
         if (lane == 0) *reinterpret_cast<u32x4*>(smem + ((e + 1) & 1) * L::BUF + L::OFF_CT) = u32x4{4u, 0u, 0u, 0u};
         barrier_lds();
@@ -351,21 +334,19 @@ __global__ __launch_bounds__(512, 4) void BEVR_GATHER_KERNEL(
         for (int c = wave; c < cur.nfill; c += n_wave)
           fill_one(wn, c, __builtin_amdgcn_readlane(cur.fd_xc, c), __builtin_amdgcn_readlane(cur.fd_r0, c));
       }
-      GPROF(p2);
+      PROF_T_FREE(p2);
       more = advance(nxt);
       stage(cur, e + 1, more ? &nxt : nullptr);
-      GPROF(p3);
+      PROF_T_FREE(p3);
       wait_vm0();         // the K / V rows and the window columns have landed
-      GPROF(p4);
-      GPROF_ADD(4, p1 - p0);
-      GPROF_ADD(6, p2 - p1);
-      GPROF_ADD(1, p3 - p2);
-      GPROF_ADD(3, p4 - p3);
-      GPROF_ADD(5, 1);
+      PROF_T_FREE(p4);
+      PROF_ADD(4, p1 - p0);
+      PROF_ADD(6, p2 - p1);
+      PROF_ADD(1, p3 - p2);
+      PROF_ADD(3, p4 - p3);
+      PROF_ADD(5, 1);
     }
-#ifdef BEVR_GPROF_ON
-    if (lane == 0) for (int i = 0; i < 8; ++i) atomicAdd(&bevr_prof_gather[i], gacc[i]);
-#endif
+    PROF_FLUSH(gather, 0, lane == 0);
     return;
   }
 
@@ -407,25 +388,21 @@ __global__ __launch_bounds__(512, 4) void BEVR_GATHER_KERNEL(
     wait_vm0();
   }
   bool first = true;      // EXACT only
-#ifdef BEVR_GPROF_ON
-  unsigned long long gacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long cprev = gprof_now();
-#endif
+  PROF_ACC(8);
+  PROF_T_FREE(cprev);
   // the sweep over the emissions, instantiated for the distance (dwords) from the first block's window rows to the
   // second's: QB, or 0 for the wave whose second block lies past the column (it leaves that block out)
   auto sweep = [&](auto off1_c) {
   constexpr int OFF1 = decltype(off1_c)::value;
   constexpr int NBX = (NB == 2 && OFF1 == 0) ? 1 : NB;      // that wave works on its one block only
   for (int e = 0;; ++e) {
-    GPROF(c0);
+    PROF_T_FREE(c0);
     barrier_lds();
-    GPROF(c1);
-    GPROF_ADD(0, c1 - c0);
-    GPROF_ADD(4, c0 - cprev);
-    GPROF_ADD(5, 1);
-#ifdef BEVR_GPROF_ON
-    cprev = c1;
-#endif
+    PROF_T_FREE(c1);
+    PROF_ADD(0, c1 - c0);
+    PROF_ADD(4, c0 - cprev);
+    PROF_ADD(5, 1);
+    PROF_SET(cprev, c1);
     const char* bb = smem + (e & 1) * L::BUF;
     const u32x4 ct = *reinterpret_cast<const u32x4*>(bb + L::OFF_CT);
     if (__builtin_amdgcn_readfirstlane((int)ct[0]) & 4) break;
@@ -524,11 +501,11 @@ __global__ __launch_bounds__(512, 4) void BEVR_GATHER_KERNEL(
         lacc[nb] = mfma16<PREC>(ones, pb, lacc[nb]);
       }
     }
-    GPROF(c2);
-    GPROF_ADD(1, c2 - c1);
+    PROF_T_FREE(c2);
+    PROF_ADD(1, c2 - c1);
     wait_vm0();
-    GPROF(c3);
-    GPROF_ADD(2, c3 - c2);
+    PROF_T_FREE(c3);
+    PROF_ADD(2, c3 - c2);
   }
   };
   if constexpr (NB == 2) {
@@ -537,9 +514,7 @@ __global__ __launch_bounds__(512, 4) void BEVR_GATHER_KERNEL(
   } else {
     sweep(IntC<0>{});
   }
-#ifdef BEVR_GPROF_ON
-  if (lane == 0 && (wave == 0 || wave == 3)) for (int i = 0; i < 8; ++i) atomicAdd(&bevr_prof_gather[8 + (wave ? 8 : 0) + i], gacc[i]);
-#endif
+  PROF_FLUSH(gather, wave ? 16 : 8, lane == 0 && (wave == 0 || wave == 3));
 
   // ---- epilogue: O[q][16 half + 4 kg ..], the two LSE planes; flag the column if a row's mass is not a healthy number ----
   bool bad = false;

@@ -8,27 +8,6 @@
 
 namespace {
 
-__device__ __forceinline__ int wave_min_i(int v) {
-#pragma unroll
-  for (int s = 16; s > 0; s >>= 1) v = min(v, __shfl_xor(v, s));
-  return v;
-}
-__device__ __forceinline__ int wave_max_i(int v) {
-#pragma unroll
-  for (int s = 16; s > 0; s >>= 1) v = max(v, __shfl_xor(v, s));
-  return v;
-}
-__device__ __forceinline__ float wave_min_f(float v) {
-#pragma unroll
-  for (int s = 16; s > 0; s >>= 1) v = fminf(v, __shfl_xor(v, s));
-  return v;
-}
-__device__ __forceinline__ float wave_max_f(float v) {
-#pragma unroll
-  for (int s = 16; s > 0; s >>= 1) v = fmaxf(v, __shfl_xor(v, s));
-  return v;
-}
-
 __global__ __launch_bounds__(256) void attn_keyprep_kernel(bevr_attn_desc d, const float* __restrict__ key_a,
                                                            const float* __restrict__ key_b, KeyW* __restrict__ kw_out,
                                                            StepBox* __restrict__ box_out, StepBox* __restrict__ gbox_out,
@@ -40,16 +19,11 @@ __global__ __launch_bounds__(256) void attn_keyprep_kernel(bevr_attn_desc d, con
   const int pg = gw / n_step, step = gw % n_step;
   const size_t idx = (size_t)pg * d.Np + (size_t)step * KT + lane;
   const bool live = step * KT + lane < d.N;
-  float a = key_a[idx], b = key_b[idx];
-  const float aL = -(float)(d.Sp + 1), aU = (float)(d.Ht + 1);
-  const float half = (float)(d.Wt / 2);
-  const float bL = -(half + 2.0f), bU = (float)(d.Wt + 1);
-  a = fminf(fmaxf(a, aL), aU);
-  b = fminf(fmaxf(b, bL), bU);
-  const float af = floorf(a);
+  const KeyClamp kc = key_clamp(key_a[idx], key_b[idx], d);
+  const float a = kc.a, b = kc.b, af = kc.af;
   const int A = (int)af;
-  const int amin = wave_min_i(live ? A : 0x7fffffff), amax = wave_max_i(live ? A : (int)0x80000000);
-  const float bmin = wave_min_f(live ? b : 3.0e38f), bmax = wave_max_f(live ? b : -3.0e38f);
+  const int amin = lanes_min<32>(live ? A : 0x7fffffff), amax = lanes_max<32>(live ? A : (int)0x80000000);
+  const float bmin = lanes_min<32>(live ? b : 3.0e38f), bmax = lanes_max<32>(live ? b : -3.0e38f);
   KeyW k;
   k.aoff = ((A + d.y_off) + d.x_off * d.Hp) * 8;
   k.fy = a - af;
@@ -77,10 +51,10 @@ __global__ __launch_bounds__(256) void attn_keyprep_kernel(bevr_attn_desc d, con
   for (int g = 0; g < N_GROUP; ++g) {
     const bool in = live && groupable && gid == g;
     StepBox sb;
-    sb.amin = wave_min_i(in ? A : 0x7fffffff);
-    sb.amax = wave_max_i(in ? A : (int)0x80000000);
-    sb.bmin = wave_min_f(in ? b : 3.0e38f);
-    sb.bmax = wave_max_f(in ? b : -3.0e38f);
+    sb.amin = lanes_min<32>(in ? A : 0x7fffffff);
+    sb.amax = lanes_max<32>(in ? A : (int)0x80000000);
+    sb.bmin = lanes_min<32>(in ? b : 3.0e38f);
+    sb.bmax = lanes_max<32>(in ? b : -3.0e38f);
     if (g == 0 && !groupable) { sb.amin = GROUPS_NONE; sb.amax = (int)0x80000000; }   // no groups: global path
     if ((lane & 31) == 0) gb_half[g] = sb;
   }

@@ -38,25 +38,11 @@
 #include "attn_tile.h"
 #include "attn_tap.h"
 
-#ifdef BEVR_SPROF
-// phase stamps (make SPROF=1 OUTDIR=../lib_sprof; tools/prof_phases_slab.py): clocks summed over the emissions of wave 0
-// (a worker), wave 6 (the last worker) and the producer of every workgroup
-__device__ unsigned long long bevr_prof_slab[48];
-extern "C" int bevr_debug_prof_slab(unsigned long long* out, int reset) {
-  if (reset) { unsigned long long z[48] = {0}; return (int)hipMemcpyToSymbol(HIP_SYMBOL(bevr_prof_slab), z, sizeof(z)); }
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(bevr_prof_slab), 48 * 8);
-}
-__device__ __forceinline__ unsigned long long sprof_now() {
-  unsigned long long t;
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(t) : : "memory");
-  return t;
-}
-#define SPROF(var) const unsigned long long var = sprof_now()
-#define SPROF_ADD(i, v) pacc[i] += (v)
-#else
-#define SPROF(var)
-#define SPROF_ADD(i, v)
-#endif
+#include "bevr_prof.h"
+
+// clocks summed over the emissions of wave 0 (a worker, at 0), wave 6 (the last worker, at 16) and the producer (at 32) of
+// every workgroup, 16 slots each
+BEVR_PROF_DEFINE(slab, 48)
 
 namespace {
 
@@ -150,18 +136,11 @@ __global__ __launch_bounds__(256) void slab_keys_kernel(bevr_attn_desc d, const 
   if (t >= total) return;
   const int pg = (int)(t / d.N);
   const int n = order[t];
-  float a = key_a[(size_t)pg * d.Np + n], b = key_b[(size_t)pg * d.Np + n];
-  // the clamps of attn_keyprep.hip: every tap of a clamped key lies inside the zero-padded table
-  const float aL = -(float)(d.Sp + 1), aU = (float)(d.Ht + 1);
-  const float half = (float)(d.Wt / 2);
-  const float bL = -(half + 2.0f), bU = (float)(d.Wt + 1);
-  a = fminf(fmaxf(a, aL), aU);
-  b = fminf(fmaxf(b, bL), bU);
-  const float af = floorf(a);
+  const KeyClamp c = key_clamp(key_a[(size_t)pg * d.Np + n], key_b[(size_t)pg * d.Np + n], d);
   SlabKey k;
-  k.A = (int)af;
-  k.fy = a - af;
-  k.b = b;
+  k.A = (int)c.af;
+  k.fy = c.a - c.af;
+  k.b = c.b;
   k.pad = 0;
   out[t] = k;
 }
@@ -208,24 +187,6 @@ __global__ __launch_bounds__(256) void slab_ranges_kernel(bevr_attn_desc d, cons
   }
 }
 
-// the value of the lane below (lane - 1) across the whole wave; lane 0 receives 0 (v_mov_b32_dpp wave_shr:1)
-__device__ __forceinline__ float slab_lane_below(float x) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x138, 0xf, 0xf, true));
-}
-__device__ __forceinline__ unsigned long long slab_from_int(int v) {
-  return ((unsigned long long)(unsigned)(v >> 31) << 32) | (unsigned)v;
-}
-__device__ __forceinline__ float slab_to_float(unsigned long long v) {
-  const int lo = (int)(unsigned)v, hi = (int)(unsigned)(v >> 32);
-  if (hi == (lo >> 31)) return (float)lo;
-  return (float)(long long)v;
-}
-__device__ __forceinline__ int half_max_i(int v) {
-#pragma unroll
-  for (int s = 16; s > 0; s >>= 1) v = max(v, __shfl_xor(v, s));
-  return v;
-}
-
 // LDS-only barrier is not enough here: the producer's global loads are consumed by its own LDS stores before the barrier
 #define SLAB_BARRIER() __syncthreads()
 
@@ -260,9 +221,7 @@ __global__ __launch_bounds__(STHREADS, 1) void attn_slab_bwd_q_kernel(
   const float kp16 = PREC == BEVR_PREC_F16 ? grad_scale[2] : 0.f, c2_16 = PREC == BEVR_PREC_F16 ? grad_scale[3] : 1.f;
   const float cfix = PREC == BEVR_PREC_F16 ? grad_scale[0] * grad_scale[4] : 1.f;
   const float dq_scale = PREC == BEVR_PREC_F16 ? grad_scale[4] * BEVR_LN2 : ginv;
-#ifdef BEVR_SPROF
-  unsigned long long pacc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#endif
+  PROF_ACC(16);
 
   for (;;) {
     // ---- next work item -------------------------------------------------------------------------------------------
@@ -283,7 +242,7 @@ __global__ __launch_bounds__(STHREADS, 1) void attn_slab_bwd_q_kernel(
     const int j0 = chunk * SLAB_CH, j1 = min(d.S, j0 + SLAB_CH);
     const char* tbl = table_pair + (size_t)hd * d.Wp * d.Hp * 8;
     float* dtb = dtable + (size_t)hd * d.Wp * Hq;
-    SPROF(ti0);
+    PROF_T_DRAIN(ti0);
 
     // ---- the slab: values in, cells cleared -----------------------------------------------------------------------
     for (int u = tid; u < (sw + 1) * RP; u += STHREADS) {
@@ -301,9 +260,9 @@ __global__ __launch_bounds__(STHREADS, 1) void attn_slab_bwd_q_kernel(
       cells[u] = 0ull;
     }
     SLAB_BARRIER();
-    SPROF(ti1);
-    SPROF_ADD(12, ti1 - ti0);     // slab in
-    SPROF_ADD(15, 1);             // items
+    PROF_T_DRAIN(ti1);
+    PROF_ADD(12, ti1 - ti0);     // slab in
+    PROF_ADD(15, 1);             // items
 
     if (producer) {
       // =========================================== PRODUCER ========================================================
@@ -357,13 +316,13 @@ __global__ __launch_bounds__(STHREADS, 1) void attn_slab_bwd_q_kernel(
         const bool last = !(lc < j1 - j0) || lc != c;
         const bool first = c != prev_c;
         prev_c = c;
-        SPROF(tp0);
+        PROF_T_DRAIN(tp0);
         const SlabKey sk_e = sk;
         u32x4 kv_e[8];
 #pragma unroll
         for (int q = 0; q < 8; ++q) kv_e[q] = kv[q];
-        SPROF(tp1);
-        SPROF_ADD(0, tp1 - tp0);      // producer: wait for this emission's loads
+        PROF_T_DRAIN(tp1);
+        PROF_ADD(0, tp1 - tp0);      // producer: wait for this emission's loads
         issue();              // the next emission's loads fly while this one is written and processed
         // ---- constants of (column j, key) ----
         {
@@ -404,12 +363,12 @@ __global__ __launch_bounds__(STHREADS, 1) void attn_slab_bwd_q_kernel(
           *reinterpret_cast<u32x4*>(bb + L::OFF_V + (cid >> 2) * SKROW + (cid & 3) * 16) = kv_e[4 + q];
         }
         ++e;
-        SPROF(tp2);
-        SPROF_ADD(1, tp2 - tp1);      // producer: constants, stores, next loads issued
+        PROF_T_DRAIN(tp2);
+        PROF_ADD(1, tp2 - tp1);      // producer: constants, stores, next loads issued
         SLAB_BARRIER();
-        SPROF(tp3);
-        SPROF_ADD(2, tp3 - tp2);      // producer: waiting for the workers
-        SPROF_ADD(3, 1);
+        PROF_T_DRAIN(tp3);
+        PROF_ADD(2, tp3 - tp2);      // producer: waiting for the workers
+        PROF_ADD(3, 1);
       }
       if (lane == 0) *reinterpret_cast<u32x4*>(stage + (e & 1) * L::BUF + L::OFF_CT) = u32x4{(unsigned)SF_DONE, 0u, 0u, 0u};
       SLAB_BARRIER();
@@ -510,7 +469,7 @@ __global__ __launch_bounds__(STHREADS, 1) void attn_slab_bwd_q_kernel(
         }
         if (jn >= 0) issue_column(jn);
         __builtin_amdgcn_sched_barrier(0);
-        SPROF(tq0);
+        PROF_T_DRAIN(tq0);
         // byte offset of the key's first tap VALUE for this lane's row; the gradient cell sits at twice that (8-byte
         // cells behind the 4-byte values)
         auto offset = [&](const SlabCK& e) -> int {
@@ -579,7 +538,7 @@ __global__ __launch_bounds__(STHREADS, 1) void attn_slab_bwd_q_kernel(
               float ds = fast_exp2(sv) * dp[h][row];
               if constexpr (PREC == BEVR_PREC_F16) ds *= c2_16;
               s[h][row] = ds;
-              const float gb_ = slab_lane_below(ds);
+              const float gb_ = lane_below(ds);
               if constexpr (PREC == BEVR_PREC_BF16) {
                 const unsigned pr = pack_bf16x2(ds, gb_);
                 asm("v_dot2_f32_bf16 %0, %2, %3, 0\n\t"
@@ -605,8 +564,8 @@ __global__ __launch_bounds__(STHREADS, 1) void attn_slab_bwd_q_kernel(
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
               unsigned long long* gp = reinterpret_cast<unsigned long long*>(lds + cells_off + 2 * o0[c]);
-              atomicAdd(gp, slab_from_int(iA[c]));
-              atomicAdd(gp + RP, slab_from_int(iB[c]));
+              atomicAdd(gp, AccCell::from_int(iA[c]));
+              atomicAdd(gp + RP, AccCell::from_int(iB[c]));
               e0[c] = e1[c]; e1[c] = e2[c]; ta[c] = na[c]; tb[c] = nb[c]; o0[c] = o1[c];
             }
           }
@@ -614,16 +573,16 @@ __global__ __launch_bounds__(STHREADS, 1) void attn_slab_bwd_q_kernel(
           dq_product(h);
           __builtin_amdgcn_sched_barrier(0);
         }
-        SPROF(tq1);
-        SPROF_ADD(4, tq1 - tq0);      // worker: the key-row loops and dQ products
+        PROF_T_DRAIN(tq1);
+        PROF_ADD(4, tq1 - tq0);      // worker: the key-row loops and dQ products
       };
 
       int e = 0;
       for (;;) {
-        SPROF(tw0);
+        PROF_T_DRAIN(tw0);
         SLAB_BARRIER();
-        SPROF(tw1);
-        SPROF_ADD(0, tw1 - tw0);      // worker: barrier wait
+        PROF_T_DRAIN(tw1);
+        PROF_ADD(0, tw1 - tw0);      // worker: barrier wait
         const char* bb = stage + (e & 1) * L::BUF;
         const u32x4 ct = *reinterpret_cast<const u32x4*>(bb + L::OFF_CT);
         const unsigned flags = (unsigned)__builtin_amdgcn_readfirstlane((int)ct[0]);
@@ -643,34 +602,29 @@ __global__ __launch_bounds__(STHREADS, 1) void attn_slab_bwd_q_kernel(
           }
           if (flags & SF_LAST) flush_dq();
         }
-        SPROF(tw2);
-        SPROF_ADD(1, tw2 - tw1);      // worker: the emission
-        SPROF_ADD(2, (flags >> 8) & 1u);
-        SPROF_ADD(3, 1);
+        PROF_T_DRAIN(tw2);
+        PROF_ADD(1, tw2 - tw1);      // worker: the emission
+        PROF_ADD(2, (flags >> 8) & 1u);
+        PROF_ADD(3, 1);
         ++e;
       }
     }
 
     // ---- flush the slab: every cell once ----------------------------------------------------------------------------
     SLAB_BARRIER();
-    SPROF(tf0);
+    PROF_T_DRAIN(tf0);
     for (int u = tid; u < (sw + 1) * RP; u += STHREADS) {
       const int c = u / RP, w = u - c * RP;
       const unsigned long long v = w < R ? cells[RP + u] : 0ull;
       if (v != 0ull) {
         const int xc = x0 + c + d.x_off, yr = w - SLAB_ROW0 + d.y_off;
-        if (xc >= 0 && xc < d.Wp && yr >= 0 && yr < Hq) atomicAdd(dtb + (size_t)xc * Hq + yr, slab_to_float(v) * ginv);
+        if (xc >= 0 && xc < d.Wp && yr >= 0 && yr < Hq) atomicAdd(dtb + (size_t)xc * Hq + yr, AccCell::to_float(v) * ginv);
       }
     }
-    SPROF(tf1);
-    SPROF_ADD(13, tf1 - tf0);     // slab out
+    PROF_T_DRAIN(tf1);
+    PROF_ADD(13, tf1 - tf0);     // slab out
   }
-#ifdef BEVR_SPROF
-  if (lane == 0 && (wave == 0 || wave == SNWORK - 1 || producer)) {
-    const int base = producer ? 32 : (wave ? 16 : 0);
-    for (int i = 0; i < 16; ++i) atomicAdd(&bevr_prof_slab[base + i], pacc[i]);
-  }
-#endif
+  PROF_FLUSH(slab, producer ? 32 : (wave ? 16 : 0), lane == 0 && (wave == 0 || wave == SNWORK - 1 || producer));
 }
 
 template <int PREC>

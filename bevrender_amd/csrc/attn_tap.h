@@ -198,13 +198,6 @@ template <int PREC> __device__ __forceinline__ TapOpP<PREC> tap_cell_half(float 
   return tap_pack8<PREC>(w);
 }
 
-// reductions inside a 32-lane half
-__device__ __forceinline__ int half_min_i(int v) {
-#pragma unroll
-  for (int s = 16; s > 0; s >>= 1) v = min(v, __shfl_xor(v, s));
-  return v;
-}
-
 // Attention dropout (bevr_common.h: bevr_drop_keep).  The dropout variants are separate translation units
 // (attn_tap_*_drop.hip: #define BEVR_DROP 1 and #include the kernel's source), as the region kernels': the kernels
 // without dropout stay what they were.  key0: index of the segment's first key in the caller's key order for the whole
@@ -324,9 +317,9 @@ __device__ __forceinline__ void tap_producer(const bevr_attn_desc& d, char* smem
       } else {
         // one chunk's worth of the remaining keys: rows from the lowest remaining key, columns from the lowest key
         // among those (that key is always selected: progress)
-        a0 = half_min_i(rem ? A : 0x7fffffff);
+        a0 = lanes_min<32>(rem ? A : 0x7fffffff);
         const bool rowok = rem && A < a0 + CELL_R - 1;
-        x0 = half_min_i(rowok ? X : 0x7fffffff);
+        x0 = lanes_min<32>(rowok ? X : 0x7fffffff);
         sel = rowok && X < x0 + CELL_C - 1;
       }
       whole = false;

@@ -4,27 +4,6 @@
 
 namespace {
 
-__device__ __forceinline__ int hmin_i(int v) {
-#pragma unroll
-  for (int s = 16; s > 0; s >>= 1) v = min(v, __shfl_xor(v, s));
-  return v;
-}
-__device__ __forceinline__ int hmax_i(int v) {
-#pragma unroll
-  for (int s = 16; s > 0; s >>= 1) v = max(v, __shfl_xor(v, s));
-  return v;
-}
-__device__ __forceinline__ float hmin_f(float v) {
-#pragma unroll
-  for (int s = 16; s > 0; s >>= 1) v = fminf(v, __shfl_xor(v, s));
-  return v;
-}
-__device__ __forceinline__ float hmax_f(float v) {
-#pragma unroll
-  for (int s = 16; s > 0; s >>= 1) v = fmaxf(v, __shfl_xor(v, s));
-  return v;
-}
-
 __global__ __launch_bounds__(256) void attn_tap_prep_kernel(bevr_attn_desc d, const float* __restrict__ key_a,
                                                             const float* __restrict__ key_b, const float* __restrict__ key_y,
                                                             const float* __restrict__ key_x, TapRec* __restrict__ rec_out,
@@ -36,16 +15,11 @@ __global__ __launch_bounds__(256) void attn_tap_prep_kernel(bevr_attn_desc d, co
   const int prob = gw / n_step, step = gw % n_step;
   const size_t idx = (size_t)prob * d.Np + (size_t)step * KT + lane;
   const bool live = step * KT + lane < d.N;
-  float a = key_a[idx], b = key_b[idx];
-  // the same clamps as attn_keyprep.hip: every tap of a clamped key lies inside the zero-padded table
-  const float aL = -(float)(d.Sp + 1), aU = (float)(d.Ht + 1);
-  const float half = (float)(d.Wt / 2);
-  const float bL = -(half + 2.0f), bU = (float)(d.Wt + 1);
-  a = fminf(fmaxf(a, aL), aU);
-  b = fminf(fmaxf(b, bL), bU);
-  const int A = (int)floorf(a);
-  const int amin = hmin_i(live ? A : 0x7fffffff), amax = hmax_i(live ? A : (int)0x80000000);
-  const float bmin = hmin_f(live ? b : 3.0e38f), bmax = hmax_f(live ? b : -3.0e38f);
+  const KeyClamp kc = key_clamp(key_a[idx], key_b[idx], d);
+  const float a = kc.a, b = kc.b;
+  const int A = (int)kc.af;
+  const int amin = lanes_min<32>(live ? A : 0x7fffffff), amax = lanes_max<32>(live ? A : (int)0x80000000);
+  const float bmin = lanes_min<32>(live ? b : 3.0e38f), bmax = lanes_max<32>(live ? b : -3.0e38f);
   TapRec r;
   r.a = live ? a : (amax >= amin ? (float)amin : 0.f);
   r.b = live ? b : (amax >= amin ? bmin : 0.f);

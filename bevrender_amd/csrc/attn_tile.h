@@ -179,6 +179,46 @@ __device__ __forceinline__ f32x2 region_entry(const char* tbl, const bevr_attn_d
   return v;
 }
 
+// ---------------------------------------------------------------------------------------------------
+// The table gradient of the query-side backward kernels (attn_bwd_q.hip, attn_slab_bwd_q.hip): fixed-point LDS cells.
+// round-to-nearest-even float -> int (v_rndne_f32 + v_cvt_i32_f32), as plain C so that the compiler sees the read.
+// Round 1 used inline asm (v_cvt_rpi_i32_f32, one instruction).  Inline asm is opaque to the hazard recognizer: fed
+// directly by a v_dot2c_f32_bf16 result (two instructions earlier in the stream) it read a stale register and the
+// bf16-mode table gradient came out 65 % wrong while the same arithmetic through v_fma_f32 was right
+// (tools/micro/dot2_test.hip shows the instruction itself is exact).
+__device__ __forceinline__ int cvt_rpi(float x) { return (int)__builtin_rintf(x); }
+
+// the value of the lane below (lane - 1) across the whole wave; lane 0 receives 0 (v_mov_b32_dpp wave_shr:1)
+__device__ __forceinline__ float lane_below(float x) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x138, 0xf, 0xf, true));
+}
+
+// Fixed-point accumulation cell: 64-bit in both precision modes.
+//   unit = ln2 * bound * 2^-30, bound >= max |P (dP - delta)| over all pairs (handed in by the caller as grad_scale);
+//   one contribution converts to a 32-bit integer (v_cvt_rpi, round to nearest: truncation would bias the sum of
+//   many small same-sign contributions) and is sign-extended into the 64-bit cell, so a cell can take 2^32
+//   contributions of the largest possible size before it wraps -- more than a launch has pairs per cell.
+//   32-bit cells (round 1, bf16 mode: ds_add_u32 is 4.4 clk, ds_add_u64 6.3) cannot hold both ends: a cell of the
+//   pinned-key box receives ~10^5 contributions per region, so a unit that is safe against wrap-around is
+//   ~bound * 2^-14, far above a typical contribution (P ~ 1/N): at S = 200 the table gradient came out 67 % wrong
+//   against the f32 mode (tests/test_gpu_fullsize.py).  Native LDS float atomics are no way out on gfx950 either:
+//   ds_add_f32 / ds_pk_add_bf16 retire ~3 clk per active LANE (193 clk per wave instruction; tools/micro/lds_bench.hip).
+struct AccCell {
+  typedef unsigned long long type;
+  static __device__ __forceinline__ type from_int(int v) {
+    return ((unsigned long long)(unsigned)(v >> 31) << 32) | (unsigned)v;
+  }
+  static __device__ __forceinline__ type from(float x) { return from_int(cvt_rpi(x)); }
+  // whole 64-bit value at once: converting the halves separately rounds the low word of a small NEGATIVE sum
+  // (hi = -1, lo = 2^32 - k) to a multiple of 256 units before the halves cancel -- up to 128 units of error per
+  // flushed cell, which over the thousands of flushes a table entry receives was 1.3 % of the S = 200 table gradient
+  static __device__ __forceinline__ float to_float(type v) {
+    const int lo = (int)(unsigned)v, hi = (int)(unsigned)(v >> 32);
+    if (hi == (lo >> 31)) return (float)lo;   // fits 32 bits (nearly always): one conversion instead of the emulated 64-bit one
+    return (float)(long long)v;
+  }
+};
+
 // Workgroup-uniformity contract of the query-stationary kernels: every __syncthreads() they execute conditionally
 // (region moves, mid-step moves) sits under predicates computed ONLY from kernel arguments, blockIdx and the
 // scalar-loaded StepBox records -- never from threadIdx, the wave's column or a key's data.  -DBEVR_DEBUG builds

@@ -256,25 +256,58 @@ __device__ __forceinline__ void load_perm(Frag<BEVR_PREC_F32>& f, const void* ro
   }
 }
 
+// Minimum / maximum over the W lanes that differ in the low log2(W) lane bits (W = 32: one half of the wave, 64: the
+// whole wave), by xor-shuffle; every lane ends up with the result.
+template <int W> __device__ __forceinline__ int lanes_min(int v) {
+#pragma unroll
+  for (int s = W / 2; s > 0; s >>= 1) v = min(v, __shfl_xor(v, s));
+  return v;
+}
+template <int W> __device__ __forceinline__ int lanes_max(int v) {
+#pragma unroll
+  for (int s = W / 2; s > 0; s >>= 1) v = max(v, __shfl_xor(v, s));
+  return v;
+}
+template <int W> __device__ __forceinline__ float lanes_min(float v) {
+#pragma unroll
+  for (int s = W / 2; s > 0; s >>= 1) v = fminf(v, __shfl_xor(v, s));
+  return v;
+}
+template <int W> __device__ __forceinline__ float lanes_max(float v) {
+#pragma unroll
+  for (int s = W / 2; s > 0; s >>= 1) v = fmaxf(v, __shfl_xor(v, s));
+  return v;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Bias-tap addressing shared by the attention kernels (global-memory gather path).
 // key constants, packed per key by the kernels' prologue: Aoff (byte offset of row floor(a)+y_off
 // in column x_off), fy, clamped b, 1 - fy.
 struct KeyC { int aoff; float fy; float b; float wy0; };
 
-__device__ __forceinline__ KeyC make_keyc(float a, float b, const bevr_attn_desc& d) {
+// A key's table coordinates clamped into the padded table -- every tap of a clamped key lies inside its zero padding --
+// and the integer row.  Every kernel that places a key in the table goes through this one function: the forward and the
+// backward kernels touch the same table cells of a key because they clamp alike.
+struct KeyClamp { float a, b, af; };   // the clamped pair and floor(a)
+__device__ __forceinline__ KeyClamp key_clamp(float a, float b, const bevr_attn_desc& d) {
   float aL = -(float)(d.Sp + 1), aU = (float)(d.Ht + 1);
   float half = (float)((d.Wt) / 2);  // ceil((Wt-1)/2)
   float bL = -(half + 2.0f), bU = (float)(d.Wt + 1);
+  KeyClamp c;
   // NaN-safe clamps (fminf/fmaxf return the non-NaN operand)
-  a = fminf(fmaxf(a, aL), aU);
-  b = fminf(fmaxf(b, bL), bU);
-  float af = floorf(a);
+  c.a = fminf(fmaxf(a, aL), aU);
+  c.b = fminf(fmaxf(b, bL), bU);
+  c.af = floorf(c.a);
+  return c;
+}
+
+__device__ __forceinline__ KeyC make_keyc(float a, float b, const bevr_attn_desc& d) {
+  const KeyClamp c = key_clamp(a, b, d);
   KeyC k;
-  k.aoff = (((int)af + d.y_off) + d.x_off * d.Hp) * 8;
-  k.fy = a - af;
+  k.aoff = (((int)c.af + d.y_off) + d.x_off * d.Hp) * 8;
+  k.fy = c.a - c.af;
   k.wy0 = 1.0f - k.fy;
-  k.b = b;
+  k.b = c.b;
   return k;
 }
 

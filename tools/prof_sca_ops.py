@@ -5,8 +5,8 @@ import os, sys, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from torch.profiler import profile, ProfilerActivity
-os.environ["ITERS"] = "1"
-exec(open(os.path.join(ROOT, "tools", "prof_sca.py")).read())      # warm-up (allocator, first-use compiles)
+from prof_sca import run
+sca, q, feat = run(iters=1)      # warm-up (allocator, first-use compiles)
 torch.cuda.synchronize()
 with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA], record_shapes=True) as prof:
     out, _ = sca(q, feat, torch.tensor(0), None, False)
