@@ -47,7 +47,9 @@ template <int PREC> struct LdsQ {
   static constexpr int WCOLS = CAP + 2;           // + two "kill" columns of -1e30: where masked keys point their taps
   static constexpr int WIN = WCOLS * WIN_PITCH * ENT;
   static constexpr int CELLS = CAP * WIN_PITCH;   // accumulation window: one 64-bit cell per table entry (+ kill columns)
-  static constexpr int PCK = NWAVE * 32 * (is16(PREC) ? 16 : 32);   // per wave: one 32-key half at a time
+  // (column, key) records, f32 modes only, per wave: one 32-key half at a time (16-bit modes keep them in registers: one
+  // unused record, an array cannot be empty)
+  static constexpr int PCK = is16(PREC) ? 16 : NWAVE * 32 * 32;
   // bf16 mode: the tile's dO fragments live in LDS (fragment order, re-read every step) instead of 8 registers
   static constexpr int QDO = is16(PREC) ? NCOL * 2 * 64 * 16 : 16;
   static constexpr int ACCB = 8;   // bytes per accumulation cell (see AccCell)
@@ -78,7 +80,7 @@ __global__ __launch_bounds__(TQ, is16(PREC) ? 4 : 2) void attn_bwd_q_kernel(
   typedef typename Acc::type acc_t;
   __shared__ __attribute__((aligned(16))) acc_t accw[L::WCOLS * WIN_PITCH];
   typedef ColKeyT<PREC> CK;
-  __shared__ __attribute__((aligned(16))) CK pck_all[NWAVE * 32];
+  __shared__ __attribute__((aligned(16))) CK pck_all[L::PCK / sizeof(CK)];
   __shared__ __attribute__((aligned(16))) char qdo[L::QDO];
 
   const int n_rb = (d.S + QROWS - 1) / QROWS;
@@ -96,7 +98,7 @@ __global__ __launch_bounds__(TQ, is16(PREC) ? 4 : 2) void attn_bwd_q_kernel(
 
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lq = lane & 31, hi = lane >> 5;
   const int col = wave;
-  CK* pck = pck_all + wave * 32;
+  CK* pck = pck_all + (is16(PREC) ? 0 : wave * 32);
   const int Mp = d.S * d.Sp;
   const int i0 = rb * QROWS;
 
@@ -374,22 +376,6 @@ __global__ __launch_bounds__(TQ, is16(PREC) ? 4 : 2) void attn_bwd_q_kernel(
           dr0 = min(dr0, wi.amin - rg.ay0);
           dr1 = max(dr1, wi.amin - rg.ay0 + wi.nrows);
         }
-        {
-          // this wave's (column, key) constants for the 32 keys of this half: lane & 31 = key (both lane halves write
-          // the same values); read back by this wave only -- a wave's LDS operations execute in order
-          const KeyW kw = kc[lq];
-          const float tx = jrx + (kw.b - (float)rg.ax0);
-          const float xf = floorf(tx);
-          CK e;
-          // masked key (padding, or not of this pass's group): taps in the kill column => P = 0, dS = 0
-          const bool dead = step * KT + kh * 32 + lq >= d.N || (gsel >= 0 && (kw.arow8 & 7) != gsel);
-          const float fx = tx - xf, fy = kw.fy;
-          if (dead) e.set(1.f, 0.f, 0.f, 0.f);
-          else e.set((1.0f - fx) * (1.0f - fy), (1.0f - fx) * fy, fx * (1.0f - fy), fx * fy);
-          e.cell = dead ? CAP * WIN_PITCH : (int)xf * WIN_PITCH + (kw.arow8 >> 3) + (sbh.amin - rg.ay0);   // arow8: relative to the half's first row
-          BEVR_ASSERT(dead || (e.cell >= 0 && e.cell + 32 + WIN_PITCH < L::WCOLS * WIN_PITCH));
-          pck[lq] = e;
-        }
         // operand fragments are loaded one MFMA chain at a time (K with Q, then V with dO; K^T only after the loop):
         // all three at once put the kernel 16 registers over its 128 and the Q fragment went to scratch
         f32x16 s, dp;
@@ -419,6 +405,26 @@ __global__ __launch_bounds__(TQ, is16(PREC) ? 4 : 2) void attn_bwd_q_kernel(
             dp = mma_frag(vkf, dof, dp);
           }
         }
+        // (column, key) constants of this half.  16-bit modes: lane l keeps those of key bcast_key(l) in registers, so
+        // that the DPP rows of a lane half hold its 16 key rows' constants in key-row order and the r-loop takes them by
+        // row_bcast (attn_tile.h): no LDS round trip.  f32 modes (four weights and a cell: five DPP moves per key row
+        // would cost more than the two reads): lane & 31 = key into this wave's LDS records (both lane halves write the
+        // same values), read back by this wave only -- a wave's LDS operations execute in order
+        CK e;
+        {
+          const int kq = is16(PREC) ? bcast_key(lane) : lq;
+          const KeyW kw = kc[kq];
+          const float tx = jrx + (kw.b - (float)rg.ax0);
+          const float xf = floorf(tx);
+          // masked key (padding, or not of this pass's group): taps in the kill column => P = 0, dS = 0
+          const bool dead = step * KT + kh * 32 + kq >= d.N || (gsel >= 0 && (kw.arow8 & 7) != gsel);
+          const float fx = tx - xf, fy = kw.fy;
+          if (dead) e.set(1.f, 0.f, 0.f, 0.f);
+          else e.set((1.0f - fx) * (1.0f - fy), (1.0f - fx) * fy, fx * (1.0f - fy), fx * fy);
+          e.cell = dead ? CAP * WIN_PITCH : (int)xf * WIN_PITCH + (kw.arow8 >> 3) + (sbh.amin - rg.ay0);   // arow8: relative to the half's first row
+          BEVR_ASSERT(dead || (e.cell >= 0 && e.cell + 32 + WIN_PITCH < L::WCOLS * WIN_PITCH));
+          if constexpr (!is16(PREC)) pck[lq] = e;
+        }
 #if BEVR_DROP
         {
           // dropout: O = sum_n D_n P_n V_n, D = keep / (1 - p)  =>  dS = P (D dP - delta); dp holds dP - delta
@@ -442,8 +448,19 @@ __global__ __launch_bounds__(TQ, is16(PREC) ? 4 : 2) void attn_bwd_q_kernel(
             a = *reinterpret_cast<const tap_t*>(p);
             b = *reinterpret_cast<const tap_t*>(p + WIN_PITCH * ENT);
           };
-          const CK* pk = pck;
-          CK e0 = pk[crow(0, hi)], e1 = pk[crow(1, hi)];
+          auto rec = [&](int r) -> CK {   // key row r's constants
+            if constexpr (is16(PREC)) {
+              CK c;
+              c.wA = row_bcast(e.wA, r);
+              c.wB = row_bcast(e.wB, r);
+              c.cell = row_bcast(e.cell, r);
+              c.pad = 0;
+              return c;
+            } else {
+              return pck[crow(r, hi)];
+            }
+          };
+          CK e0 = rec(0), e1 = rec(1);
           tap_t ta, tb;
           read_tap(e0.cell, ta, tb);
 #pragma unroll
@@ -451,7 +468,7 @@ __global__ __launch_bounds__(TQ, is16(PREC) ? 4 : 2) void attn_bwd_q_kernel(
             tap_t na = ta, nb = tb;
             CK e2 = e1;
             if (r + 1 < 16) read_tap(e1.cell, na, nb);
-            if (r + 2 < 16) e2 = pk[crow(r + 2, hi)];
+            if (r + 2 < 16) e2 = rec(r + 2);
             float sv;
             if constexpr (is16(PREC)) {
               sv = Half<PREC>::dot2(ta, e0.wA, s[r]);

@@ -63,7 +63,8 @@ constexpr float SLAB_EPS = 0.02f;  // slack of the key runs (in table columns): 
 // per key, in the problem's b-sorted order (bevr_attn_slab_prep)
 struct SlabKey { int A; float fy; float b; int pad; };
 
-// per-(column, key) constants of an emission, written by the producer (lane = key), read as a broadcast
+// per-(column, key) constants of an emission, written by the producer (lane = key); a worker lane reads ONE record per
+// half and the key-row loop takes its constants from those registers by DPP (process)
 struct SlabCK {
   unsigned wA, wB;   // tap weights of column X / X + 1 as packed 16-bit pairs (row y, row y + 1)
   int cell;          // window index of the key's first tap for window row offset 0: colbase + row
@@ -449,7 +450,12 @@ __global__ __launch_bounds__(STHREADS, 1) void attn_slab_bwd_q_kernel(
       // read Q and dO are issued, the rows of column jn are requested INTO the same registers.
       auto process = [&](const char* bb, int jn, auto clamp_tag) {
         constexpr bool CLAMP = decltype(clamp_tag)::value;
-        const SlabCK* pk0 = reinterpret_cast<const SlabCK*>(bb + L::OFF_CK);
+        // the constants of both halves' keys: lane l holds the record of key bcast_key(l) of each half (attn_tile.h: the
+        // key-row loops take theirs from these by DPP)
+        u32x4 ck[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+          ck[h] = *reinterpret_cast<const u32x4*>(bb + L::OFF_CK + (h * 32 + bcast_key(lane)) * (int)sizeof(SlabCK));
         f32x16 s[2], dp[2];
         {
           float a = nl, b = nd;
@@ -470,11 +476,16 @@ __global__ __launch_bounds__(STHREADS, 1) void attn_slab_bwd_q_kernel(
         if (jn >= 0) issue_column(jn);
         __builtin_amdgcn_sched_barrier(0);
         PROF_T_DRAIN(tq0);
-        // byte offset of the key's first tap VALUE for this lane's row; the gradient cell sits at twice that (8-byte
+        // byte offset of key row t's first tap VALUE for this lane's row; the gradient cell sits at twice that (8-byte
         // cells behind the 4-byte values)
-        auto offset = [&](const SlabCK& e) -> int {
-          if constexpr (CLAMP) return (e.cell - 4 * e.row) + 4 * max(0, min(e.row + (rowoff4 >> 2), R - 1));
-          else return e.cell + rowoff4;
+        auto offset = [&](const u32x4& k, int t) -> int {
+          const int cell = row_bcast((int)k[2], t);
+          if constexpr (CLAMP) {
+            const int row = row_bcast((int)k[3], t);
+            return (cell - 4 * row) + 4 * max(0, min(row + (rowoff4 >> 2), R - 1));
+          } else {
+            return cell + rowoff4;
+          }
         };
         auto read_tap = [&](int off, unsigned& a, unsigned& b) {
           a = *reinterpret_cast<const unsigned*>(lds + off);
@@ -503,38 +514,34 @@ __global__ __launch_bounds__(STHREADS, 1) void attn_slab_bwd_q_kernel(
         };
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-          const SlabCK* pk = pk0 + h * 32;
           // chain c walks the key rows c * 8 + 0 .. 7 of the accumulator tile
-          SlabCK e0[2], e1[2];
+          const u32x4 k = ck[h];
           int o0[2];
           unsigned ta[2], tb[2];
 #pragma unroll
           for (int c = 0; c < 2; ++c) {
-            e0[c] = pk[crow(8 * c, hi)];
-            e1[c] = pk[crow(8 * c + 1, hi)];
-            o0[c] = offset(e0[c]);
+            o0[c] = offset(k, 8 * c);
             read_tap(o0[c], ta[c], tb[c]);
           }
 #pragma unroll
           for (int r = 0; r < 8; ++r) {
-            unsigned na[2], nb[2];
-            SlabCK e2[2];
+            unsigned na[2], nb[2], wA[2], wB[2];
             int o1[2];
             // the LDS atomics are ordered memory operations for the compiler (it moves no load across them): the taps of
-            // the next key row and the constants of the one after, of BOTH chains, are requested before the adds of this
-            // step are issued
+            // the next key row, of BOTH chains, are requested before the adds of this step are issued
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
-              na[c] = ta[c]; nb[c] = tb[c]; e2[c] = e1[c]; o1[c] = o0[c];
-              if (r + 1 < 8) { o1[c] = offset(e1[c]); read_tap(o1[c], na[c], nb[c]); }
-              if (r + 2 < 8) e2[c] = pk[crow(8 * c + r + 2, hi)];
+              na[c] = ta[c]; nb[c] = tb[c]; o1[c] = o0[c];
+              if (r + 1 < 8) { o1[c] = offset(k, 8 * c + r + 1); read_tap(o1[c], na[c], nb[c]); }
+              wA[c] = row_bcast(k[0], 8 * c + r);
+              wB[c] = row_bcast(k[1], 8 * c + r);
             }
             int iA[2], iB[2];
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
               const int row = 8 * c + r;
-              float sv = Half<PREC>::dot2(ta[c], e0[c].wA, s[h][row]);
-              sv = Half<PREC>::dot2(tb[c], e0[c].wB, sv);
+              float sv = Half<PREC>::dot2(ta[c], wA[c], s[h][row]);
+              sv = Half<PREC>::dot2(tb[c], wB[c], sv);
               float ds = fast_exp2(sv) * dp[h][row];
               if constexpr (PREC == BEVR_PREC_F16) ds *= c2_16;
               s[h][row] = ds;
@@ -547,7 +554,7 @@ __global__ __launch_bounds__(STHREADS, 1) void attn_slab_bwd_q_kernel(
                     "v_cvt_rpi_i32_f32 %0, %0\n\t"
                     "v_cvt_rpi_i32_f32 %1, %1"
                     : "=&v"(iA[c]), "=&v"(iB[c])
-                    : "v"(pr), "v"(e0[c].wA), "v"(e0[c].wB));
+                    : "v"(pr), "v"(wA[c]), "v"(wB[c]));
               } else {
                 const unsigned pr = Half<PREC>::pack2(ds, gb_);
                 asm("v_dot2_f32_f16 %0, %2, %3, 0\n\t"
@@ -558,7 +565,7 @@ __global__ __launch_bounds__(STHREADS, 1) void attn_slab_bwd_q_kernel(
                     "v_cvt_rpi_i32_f32 %0, %0\n\t"
                     "v_cvt_rpi_i32_f32 %1, %1"
                     : "=&v"(iA[c]), "=&v"(iB[c])
-                    : "v"(pr), "v"(e0[c].wA), "v"(e0[c].wB), "v"(cfix));
+                    : "v"(pr), "v"(wA[c]), "v"(wB[c]), "v"(cfix));
               }
             }
 #pragma unroll
@@ -566,7 +573,7 @@ __global__ __launch_bounds__(STHREADS, 1) void attn_slab_bwd_q_kernel(
               unsigned long long* gp = reinterpret_cast<unsigned long long*>(lds + cells_off + 2 * o0[c]);
               atomicAdd(gp, AccCell::from_int(iA[c]));
               atomicAdd(gp + RP, AccCell::from_int(iB[c]));
-              e0[c] = e1[c]; e1[c] = e2[c]; ta[c] = na[c]; tb[c] = nb[c]; o0[c] = o1[c];
+              ta[c] = na[c]; tb[c] = nb[c]; o0[c] = o1[c];
             }
           }
           // the half's dQ product: issued here, it runs under the other half's loop (h = 0) or the barrier wait (h = 1)
@@ -636,21 +643,25 @@ int launch(const bevr_attn_desc& d, const void* Q, const void* Ks, const void* V
   int* cnt = reinterpret_cast<int*>(const_cast<char*>(base) + w.off_cnt);
   hipError_t e = hipMemsetAsync(cnt + 1, 0, 4, st);       // the item counter of this launch
   if (e != hipSuccess) return (int)e;
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return BEVR_E_SHAPE;
-    n_cu = prop.multiProcessorCount;
+  // the CU count and the dynamic-LDS attribute belong to a DEVICE, not to the process: both are cached per device
+  constexpr int MAX_DEV = 64;
+  static int n_cu_of[MAX_DEV] = {};
+  static bool attr_set[MAX_DEV][4] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEV) return BEVR_E_SHAPE;
+  if (n_cu_of[dev] == 0) {
+    int n = 0;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) return BEVR_E_SHAPE;
+    n_cu_of[dev] = n;
   }
+  const int n_cu = n_cu_of[dev];
   const int R = slab_rows(d.S);
   const size_t lds = slab_lds_bytes(d.S, w.sw);
-  static bool attr_set[4] = {false, false, false, false};
-  if (!attr_set[PREC]) {
+  if (!attr_set[dev][PREC]) {
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_slab_bwd_q_kernel<PREC>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) return (int)e;
-    attr_set[PREC] = true;
+    attr_set[dev][PREC] = true;
   }
   hipLaunchKernelGGL((attn_slab_bwd_q_kernel<PREC>), dim3(n_cu), dim3(STHREADS), lds, st, d, (const char*)Q,
                      (const char*)Ks, (const char*)Vs, reinterpret_cast<const SlabKey*>(base),

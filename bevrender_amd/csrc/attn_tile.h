@@ -193,6 +193,37 @@ __device__ __forceinline__ float lane_below(float x) {
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x138, 0xf, 0xf, true));
 }
 
+// Per-key constants of the key-row loops by DPP instead of broadcast LDS reads.  Key row t of a 32-key half belongs to key
+// crow(t, hi), the same for all 32 lanes of a half, and for one hi the 16 key rows are 16 distinct keys.  So lane l PRELOADS
+// the constants of key bcast_key(l): the two DPP rows (16 lanes each) of a half then hold that half's 16 records, in
+// key-row order, and row_bcast(v, t) -- lane t of the own DPP row, handed to the whole row -- is the constant of key row t:
+// one v_mov_b32_dpp row_newbcast:t (or a DPP operand of the consumer), no LDS instruction.
+// t must fold to a constant (fully unrolled loops).  EVERY lane of the wave must be enabled: a disabled source lane is
+// not read.
+constexpr unsigned crow_keys(int hi) {
+  unsigned m = 0;
+  for (int n = 0; n < 16; ++n) m |= 1u << crow(n, hi);
+  return m;
+}
+// 16 rows per hi and all 32 keys met: crow(n, 0) and crow(n, 1), n = 0..15, are 16 distinct keys each
+static_assert((crow_keys(0) | crow_keys(1)) == 0xffffffffu && (crow_keys(0) & crow_keys(1)) == 0u, "crow: 2 x 16 distinct keys");
+__device__ __forceinline__ int bcast_key(int lane) { return crow(lane & 15, lane >> 5); }
+template <int T> __device__ __forceinline__ unsigned row_bcast_c(unsigned v) {
+  return (unsigned)__builtin_amdgcn_mov_dpp((int)v, 0x150 + T, 0xf, 0xf, true);
+}
+__device__ __forceinline__ unsigned row_bcast(unsigned v, int t) {
+  switch (t & 15) {
+#define BEVR_BC_(T_) case T_: return row_bcast_c<T_>(v);
+    BEVR_BC_(0) BEVR_BC_(1) BEVR_BC_(2) BEVR_BC_(3) BEVR_BC_(4) BEVR_BC_(5) BEVR_BC_(6) BEVR_BC_(7)
+    BEVR_BC_(8) BEVR_BC_(9) BEVR_BC_(10) BEVR_BC_(11) BEVR_BC_(12) BEVR_BC_(13) BEVR_BC_(14) default: return row_bcast_c<15>(v);
+#undef BEVR_BC_
+  }
+}
+__device__ __forceinline__ int row_bcast(int v, int t) { return (int)row_bcast((unsigned)v, t); }
+__device__ __forceinline__ float row_bcast(float v, int t) {
+  return __builtin_bit_cast(float, row_bcast(__builtin_bit_cast(unsigned, v), t));
+}
+
 // Fixed-point accumulation cell: 64-bit in both precision modes.
 //   unit = ln2 * bound * 2^-30, bound >= max |P (dP - delta)| over all pairs (handed in by the caller as grad_scale);
 //   one contribution converts to a 32-bit integer (v_cvt_rpi, round to nearest: truncation would bias the sum of
