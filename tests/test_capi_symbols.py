@@ -30,6 +30,62 @@ def test_library_exports_every_declared_symbol():
     assert L.bevr_abi_version() == _lib.ABI_VERSION == 6
 
 
+def declared_prototypes():
+    """{name: (return kind, [argument kinds])} of every prototype in the header.
+
+    Grammar: `int|size_t|const char* name(args);`.  An argument is a descriptor pointer ("desc"), any other pointer
+    ("ptr"), or a scalar "int", "longlong", "float", "u32" (`unsigned` / `uint32_t`), "size_t"."""
+    src = open(os.path.join(ROOT, "include", "bevrender_hip.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    src = re.sub(r"//[^\n]*", "", src)
+    scalars = {"int": "int", "int32_t": "int", "long long": "longlong", "float": "float", "unsigned": "u32",
+               "unsigned int": "u32", "uint32_t": "u32", "size_t": "size_t"}
+    protos = {}
+    for ret, name, args in re.findall(r"\b(int|size_t|const\s+char\s*\*)\s*(bevr_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", src):
+        kinds = []
+        args = " ".join(args.split())
+        for arg in ([] if args in ("", "void") else args.split(",")):
+            arg = arg.strip()
+            if "*" in arg:
+                kinds.append("desc" if re.search(r"\bbevr_attn_desc\b", arg) else "ptr")
+                continue
+            m = re.fullmatch(r"(?:const )?(.+?) ([A-Za-z_][A-Za-z0-9_]*)", arg)
+            assert m and m.group(1) in scalars, (name, arg)
+            kinds.append(scalars[m.group(1)])
+        assert name not in protos, name
+        protos[name] = ("cstr" if "char" in ret else ret, kinds)
+    return protos
+
+
+def binding_kind(t):
+    if t is ctypes.POINTER(_lib.AttnDesc):
+        return "desc"
+    if t is ctypes.c_void_p or (isinstance(t, type) and issubclass(t, ctypes._Pointer)):
+        return "ptr"
+    # ctypes aliases types of equal size (c_uint32 is c_uint, c_size_t is c_ulong, ...): compare by identity in an order
+    # that keeps the C ABI's distinctions (width, signedness, float) and nothing else
+    for kind, ct in (("int", ctypes.c_int), ("longlong", ctypes.c_longlong), ("float", ctypes.c_float),
+                     ("u32", ctypes.c_uint32), ("size_t", ctypes.c_size_t), ("cstr", ctypes.c_char_p)):
+        if t is ct:
+            return kind
+    return repr(t)
+
+
+def test_header_and_binding_agree_on_every_prototype():
+    """Argument by argument and return type by return type: a swapped int / long long or a missing argument in a
+    hand-written argtypes list would load and run."""
+    protos = declared_prototypes()
+    assert sorted(protos) == declared_symbols() == sorted(_lib.SYMBOLS)
+    L = _lib.lib()
+    bad = {}
+    for name, (ret, kinds) in sorted(protos.items()):
+        fn = getattr(L, name)
+        have = (binding_kind(fn.restype), [binding_kind(t) for t in (fn.argtypes or [])])
+        if have != (ret, kinds):
+            bad[name] = {"header": (ret, kinds), "binding": have}
+    assert not bad, bad
+
+
 def test_argument_contract_is_checked_without_a_gpu():
     """Bad descriptors / NULL pointers are rejected before anything is launched."""
     L = _lib.lib()

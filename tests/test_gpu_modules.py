@@ -38,7 +38,9 @@ def load_params(mod, z):
     assert not missing and not unexpected
 
 
-def check(mod, z, out, inputs, prec):
+def check(mod, z, out, inputs, prec, skip=()):
+    """skip: names of inputs that carry no gradient in this run (detached: the training step's history); their golden
+    grad_in.* is not compared -- they must have received none -- and every other limit is unchanged."""
     f32 = prec == _lib.PREC_F32
     np.testing.assert_allclose(out.detach().cpu().numpy(), z["out"], rtol=3e-4 if f32 else 3e-2,
                                atol=3e-5 if f32 else 2e-2)
@@ -54,6 +56,9 @@ def check(mod, z, out, inputs, prec):
             assert g is not None, k
             g = g.cpu().numpy()
         elif k.startswith("grad_in."):
+            if k[len("grad_in."):] in skip:
+                assert inputs[k[len("grad_in."):]].grad is None, k
+                continue
             g = inputs[k[len("grad_in."):]].grad.cpu().numpy()
         else:
             continue
@@ -94,6 +99,116 @@ def test_sca_module_matches_reference(name, prec):
     ref = torch.tensor(z["reference_points"]).to(DEV)
     out, _ = m(x, query, ref, None, False)
     check(m, z, out, {"query": query, "x": x}, prec)
+
+
+def _tsa(name, prec, history_grad=True):
+    from bevrender_amd.model.TSA_deform_attn import TSADeformableAttention
+    z = load(name)
+    B, C, h, g, S, k, s, sor, xnone = [int(v) for v in z["cfg"]]
+    m = TSADeformableAttention(bev_feat_shape=S, dim_embed=C, n_heads=h, n_groups=g, stride=s, kernel_size=k,
+                               scale_offset_range=bool(sor), batch_size=B, n_views=1, precision=prec).to(DEV)
+    load_params(m, z)
+    query = torch.tensor(z["query"]).to(DEV).requires_grad_(True)
+    prev = None if xnone else torch.tensor(z["prev_bev"]).to(DEV).requires_grad_(history_grad)
+    return m, z, query, prev
+
+
+def _sca(name, prec, x_grad=True):
+    from bevrender_amd.model.SCA_deform_attn import SCADeformableAttention
+    z = load(name)
+    B, C, h, g, S, D, Hi, Wi, sor = [int(v) for v in z["cfg"]]
+    m = SCADeformableAttention(bev_feat_shape=S, bev_depth_dim=D, dim_embed=C, n_heads=h, n_groups=g, stride=1,
+                               kernel_size=3, scale_offset_range=bool(sor), batch_size=B, n_views=1,
+                               precision=prec).to(DEV)
+    load_params(m, z)
+    query = torch.tensor(z["query"]).to(DEV).requires_grad_(True)
+    x = torch.tensor(z["x"]).to(DEV).requires_grad_(x_grad)
+    ref = torch.tensor(z["reference_points"]).to(DEV)
+    return m, z, query, x, ref
+
+
+TSA_WITH_HISTORY = [n for n in TSA if not int(load(n)["cfg"][8])]
+
+
+@pytest.mark.parametrize("prec", [_lib.PREC_F32, _lib.PREC_BF16])
+@pytest.mark.parametrize("name", TSA_WITH_HISTORY)
+def test_tsa_module_with_a_history_that_carries_no_gradient(name, prec):
+    """The training step's pattern (model/bevrender.py: the history frames run under no_grad, so the one frame with
+    gradients gets a prev_bev that does not require grad): every parameter's and the query's gradient against the SAME
+    golden values and limits -- they do not depend on whether the history asked for a gradient."""
+    m, z, query, prev = _tsa(name, prec, history_grad=False)
+    out, _ = m(prev, query, {"k": 1}, False)
+    check(m, z, out, {"query": query, "prev_bev": prev}, prec, skip=("prev_bev",))
+
+
+@pytest.mark.parametrize("prec", [_lib.PREC_F32, _lib.PREC_BF16])
+@pytest.mark.parametrize("name", SCA)
+def test_sca_module_with_image_features_that_carry_no_gradient(name, prec):
+    """A frozen backbone: x detached; the parameters' and the query's gradients against the same goldens and limits."""
+    m, z, query, x, ref = _sca(name, prec, x_grad=False)
+    out, _ = m(x, query, ref, None, False)
+    check(m, z, out, {"query": query, "x": x}, prec, skip=("x",))
+
+
+def _enclayer(prec):
+    from bevrender_amd.model.bev_cmr_proj import BEV2CameraProjector
+    from bevrender_amd.model.encoder import EncoderLayer
+    z = load("enclayer.npz")
+    B, C, S, D, h, X, Y, Z = [int(v) for v in z["cfg"]]
+    proj = BEV2CameraProjector(imu_to_rgb={0: list(z["imu_to_rgb"])}, K={0: [k.copy() for k in z["K"]]},
+                               vehicle_type_code=0, img_width=128, img_height=128, ori_img_width=128,
+                               ori_img_height=128, device=DEV)
+    layer = EncoderLayer(bev_bound={"X": X, "Y": Y, "Z": Z}, bev2cmr_projector=proj, n_views=1, bev_feat_shape=S,
+                         bev_depth_dim=D, z_shift=-1.0, dim_embed=C, expansion=4, stage_idx=0, n_groups=1, n_heads=h,
+                         stride=1, kernel_size=3, batch_size=B, scale_offset_range=True, drop_path_rate=0.0,
+                         precision=prec).to(DEV)
+    load_params(layer, z)
+    return layer, z, B
+
+
+@pytest.mark.parametrize("skip", [("prev_bev",), ("prev_bev", "img_feat")], ids=["history", "history+features"])
+def test_encoder_layer_with_inputs_that_carry_no_gradient(skip):
+    """tests/golden/enclayer.npz as test_encoder_layer_matches_reference runs it, with the history (and the image
+    features) detached: the remaining gradients against the same goldens and limits."""
+    prec = _lib.PREC_F32
+    layer, z, B = _enclayer(prec)
+    layer.train()
+    ins = {n: torch.tensor(z[n]).to(DEV).requires_grad_(n not in skip) for n in ("bev_query", "prev_bev", "img_feat")}
+    out, _ = layer(ins["bev_query"], ins["img_feat"], ins["prev_bev"], torch.zeros(B, 2, 3, device=DEV), torch.tensor(0), {},
+                   False)
+    check(layer, z, out, ins, prec, skip=skip)
+
+
+def _check_forward(out, z, prec):
+    """check's forward tolerance, on an output that has no graph"""
+    assert not out.requires_grad
+    f32 = prec == _lib.PREC_F32
+    e = np.abs(out.cpu().numpy() - z["out"]).max() / np.abs(z["out"]).max()
+    print(f"[modules eval / no_grad prec={prec}] out rel err {e:.3e}")
+    np.testing.assert_allclose(out.cpu().numpy(), z["out"], rtol=3e-4 if f32 else 3e-2, atol=3e-5 if f32 else 2e-2)
+
+
+@pytest.mark.parametrize("family,prec", [("tsa", _lib.PREC_F32), ("tsa", _lib.PREC_BF16), ("sca", _lib.PREC_F32),
+                                         ("sca", _lib.PREC_BF16), ("enclayer", _lib.PREC_F32)])
+def test_module_forward_in_eval_mode_under_no_grad(family, prec):
+    """How the history frames run (model/bevrender.py: eval mode, torch.no_grad()): the ops take their forward-only
+    branches (no transposed K, NULL outputs of the projection / packing kernels).  The goldens were made without dropout
+    or drop-path, so the eval forward equals the golden `out` within check's forward tolerance
+    (enclayer.npz in f32 only, as test_encoder_layer_matches_reference compares it)."""
+    if family == "tsa":
+        m, z, query, prev = _tsa(TSA_WITH_HISTORY[0], prec)
+        with torch.no_grad():
+            out, _ = m.eval()(prev, query, {}, False)
+    elif family == "sca":
+        m, z, query, x, ref = _sca(SCA[0], prec)
+        with torch.no_grad():
+            out, _ = m.eval()(x, query, ref, None, False)
+    else:
+        layer, z, B = _enclayer(prec)
+        ins = [torch.tensor(z[n]).to(DEV).requires_grad_(True) for n in ("bev_query", "img_feat", "prev_bev")]
+        with torch.no_grad():
+            out, _ = layer.eval()(*ins, torch.zeros(B, 2, 3, device=DEV), torch.tensor(0), {}, False)
+    _check_forward(out, z, prec)
 
 
 def test_sca_multi_view_is_the_composition_of_single_views():
