@@ -35,6 +35,17 @@
 // (ROW0 = 10, PADR = 8: the learned offsets move a key ~3 rows past the table's ends).  A 32-key half with a key outside
 // that range takes the CLAMPED body: the row index is clamped into the window, whose first and last rows lie outside the
 // real table (zero values, gradient discarded), exactly as the zero padding of the global table.
+//
+// BEVR_SLAB_ROWS = 1 (attn_slab_bwd_q_rows.hip, a translation unit of its own so that the kernels above stay what they
+// are): S <= 448.  The window keeps its FULL height -- every table row the whole column can reach, R from the same
+// formula -- at one of two taller row pitches (a template parameter: the pitch stays a compile-time multiple of 64), and
+// a launch covers a BAND of at most SNRB row blocks: worker wave w owns row block row0 / 31 + w.  Nothing else changes: a
+// pair's window row is A + ROW0 + i whichever band i lies in, so the indexing and the clamping argument are the ones
+// above (a window cut to the band's rows would clamp a key with A = -15 seen from row 217 onto the wrong, non-zero, row).
+// The entry points are bevr_attn_slab_rows_ws_bytes / _slab_rows_prep / bevr_attn_slab_bwd_q_rows.
+#ifndef BEVR_SLAB_ROWS
+#define BEVR_SLAB_ROWS 0
+#endif
 #include "attn_tile.h"
 #include "attn_tap.h"
 
@@ -53,7 +64,7 @@ constexpr int SLAB_RP = 448;       // row PITCH of a slab column in entries: 7 x
                                    // ds_read2st64_b32 and the two gradient adds share an address register (S <= 211)
 constexpr int SLAB_CH = 25;        // BEV columns per work item
 constexpr int SQROWS = 31;         // query rows per row block (lane 31 of a half: the 32nd table row, attn_bwd_q.hip)
-constexpr int SNRB = 7;            // row blocks per column (S <= 217)
+constexpr int SNRB = 7;            // row blocks per column (S <= 217) -- BEVR_SLAB_ROWS: per launch (a band of the column)
 constexpr int SNWORK = SNRB;       // worker waves: one per row block, BOTH 32-key halves of an emission each
 constexpr int STHREADS = (SNWORK + 1) * 64;   // 8 waves = 2 per SIMD: 256 registers per wave (see the kernel)
 constexpr int SEK = 64;            // keys per emission
@@ -84,14 +95,24 @@ __host__ __device__ inline int slab_n_rb(int S) { return (S + SQROWS - 1) / SQRO
 __host__ __device__ inline int slab_rows(int S) { return SLAB_ROW0 + S + SLAB_PADR + SQROWS * slab_n_rb(S) + 2; }
 // columns in LDS: column 0 is the KILL column (values -big, masked keys point there; its right neighbour is a real column,
 // read with weight 0), columns 1 .. sw + 1 the slab's sw owned columns and the right tap column of the last one
-__host__ __device__ inline size_t slab_lds_bytes(int S, int sw) {
-  return (size_t)(sw + 2) * SLAB_RP * 12 + 2 * SlabLds::BUF + 64;
+__host__ __device__ inline size_t slab_lds_bytes(int S, int sw, int rp = SLAB_RP) {
+  return (size_t)(sw + 2) * rp * 12 + 2 * SlabLds::BUF + 64;
 }
-__host__ __device__ inline int slab_width(int S) {
+__host__ __device__ inline int slab_width(int S, int rp = SLAB_RP) {
   int sw = SLAB_W_MAX;
-  while (sw > 1 && slab_lds_bytes(S, sw) > 160 * 1024) --sw;
+  while (sw > 1 && slab_lds_bytes(S, sw, rp) > 160 * 1024) --sw;
   return sw;
 }
+#if BEVR_SLAB_ROWS
+// the two tall pitches (13 x 64, 15 x 64): 832 holds the 826 rows of S = 403 at sw = 12 (162 432 B of LDS), 960 the 933
+// rows of S = 448 at sw = 10 (160 896 B)
+constexpr int SLAB_RP_A = 832, SLAB_RP_B = 960;
+constexpr int SLAB_ROWS_MAX_S = 448;
+constexpr int SLAB_BAND_ROWS = SNRB * SQROWS;      // 217
+__host__ __device__ inline int slab_pitch(int S) { return slab_rows(S) <= SLAB_RP_A ? SLAB_RP_A : SLAB_RP_B; }
+#else
+__host__ __device__ inline int slab_pitch(int S) { return SLAB_RP; }
+#endif
 // first table column any slab has to cover and the number of slabs: X = floor(j rx + b), b clamped as the key prep does
 __host__ __device__ inline int slab_xmin(const bevr_attn_desc& d) { return -(d.Wt / 2 + 2) - 1; }
 __host__ __device__ inline int slab_count(const bevr_attn_desc& d, int sw) {
@@ -108,7 +129,7 @@ struct SlabWs {
 };
 __host__ __device__ inline SlabWs slab_ws(const bevr_attn_desc& d) {
   SlabWs w;
-  w.sw = slab_width(d.S);
+  w.sw = slab_width(d.S, slab_pitch(d.S));
   w.n_slab = slab_count(d, w.sw);
   w.n_chunk = slab_chunks(d.S);
   const size_t pg = (size_t)d.n_prob * d.groups;
@@ -191,17 +212,30 @@ __global__ __launch_bounds__(256) void slab_ranges_kernel(bevr_attn_desc d, cons
 // LDS-only barrier is not enough here: the producer's global loads are consumed by its own LDS stores before the barrier
 #define SLAB_BARRIER() __syncthreads()
 
+// BEVR_SLAB_ROWS: RP the row pitch, row0 (a multiple of SQROWS) the first BEV row of the launch's band, n_rb_band <= SNRB its
+// row blocks: worker wave w owns row block row0 / SQROWS + w of the column
+#if BEVR_SLAB_ROWS
+template <int PREC, int RP>
+#else
 template <int PREC>
+#endif
 __global__ __launch_bounds__(STHREADS, 1) void attn_slab_bwd_q_kernel(
     bevr_attn_desc d, const char* __restrict__ Q, const char* __restrict__ Ks, const char* __restrict__ Vs,
     const SlabKey* __restrict__ skeys, const int* __restrict__ kbeg, const int* __restrict__ kend,
     const int4* __restrict__ items, int* __restrict__ cnt, const char* __restrict__ table_pair,
     const char* __restrict__ dO, const float* __restrict__ LSE, const float* __restrict__ delta,
-    const float* __restrict__ grad_scale, float* __restrict__ dQ, float* __restrict__ dtable, int n_slab, int sw, int R) {
+    const float* __restrict__ grad_scale, float* __restrict__ dQ, float* __restrict__ dtable, int n_slab, int sw, int R
+#if BEVR_SLAB_ROWS
+    , int row0, int n_rb_band
+#endif
+    ) {
   typedef SlabLds L;
   extern __shared__ __attribute__((aligned(256))) char lds[];
   // layout: vals (u32) | cells (u64) | staging x 2 | item slot
+#if !BEVR_SLAB_ROWS
   constexpr int RP = SLAB_RP;
+#endif
+  static_assert(RP % 64 == 0, "the two taps of a pair are one ds_read2st64_b32");
   const int ncell = (sw + 2) * RP;
   unsigned* vals = reinterpret_cast<unsigned*>(lds);
   unsigned long long* cells = reinterpret_cast<unsigned long long*>(lds + (size_t)ncell * 4);
@@ -210,8 +244,12 @@ __global__ __launch_bounds__(STHREADS, 1) void attn_slab_bwd_q_kernel(
 
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lq = lane & 31, hi = lane >> 5;
   const bool producer = wave == SNWORK;
-  const int rb = wave;                               // worker: row block
+  const int rb = wave;                               // worker: row block (BEVR_SLAB_ROWS: of the launch's band)
+#if BEVR_SLAB_ROWS
+  const int n_rb = n_rb_band;
+#else
   const int n_rb = slab_n_rb(d.S);
+#endif
   const int Mp = d.S * d.Sp;
   const int Hq = d.Hp + 1;
   const float rx = (float)(d.Wt - 1) / (2.0f * (float)(d.S - 1));
@@ -380,7 +418,11 @@ __global__ __launch_bounds__(STHREADS, 1) void attn_slab_bwd_q_kernel(
       // waves 4 .. 6 share a SIMD with waves 0 .. 2, and the issue arbitration favours the older wave: the phase stamps had
       // wave 6's key-row loop 26 % longer than wave 0's, and the barrier waits for the slowest
       if (wave >= 4) __builtin_amdgcn_s_setprio(1);
+#if BEVR_SLAB_ROWS
+      const int i0 = row0 + __builtin_amdgcn_readfirstlane(rb) * SQROWS;     // uniform: a scalar register
+#else
       const int i0 = rb * SQROWS;
+#endif
       const int qrow = i0 + lq;
       const bool live = lq < SQROWS && qrow < d.S;
       const int rowoff4 = (i0 + lq) * 4;
@@ -634,10 +676,16 @@ __global__ __launch_bounds__(STHREADS, 1) void attn_slab_bwd_q_kernel(
   PROF_FLUSH(slab, producer ? 32 : (wave ? 16 : 0), lane == 0 && (wave == 0 || wave == SNWORK - 1 || producer));
 }
 
-template <int PREC>
+#if BEVR_SLAB_ROWS
+#define SLAB_KERNEL(PREC, RP) attn_slab_bwd_q_kernel<PREC, RP>
+template <int PREC, int RP>
+#else
+#define SLAB_KERNEL(PREC, RP) attn_slab_bwd_q_kernel<PREC>
+template <int PREC, int RP = SLAB_RP>
+#endif
 int launch(const bevr_attn_desc& d, const void* Q, const void* Ks, const void* Vs, const void* ws, const float* table_pair,
            const void* dO, const float* LSE, const float* delta, const float* grad_scale, float* dQ, float* dtable,
-           hipStream_t st) {
+           int row0, int n_rb_band, hipStream_t st) {
   const SlabWs w = slab_ws(d);
   const char* base = static_cast<const char*>(ws);
   int* cnt = reinterpret_cast<int*>(const_cast<char*>(base) + w.off_cnt);
@@ -656,35 +704,59 @@ int launch(const bevr_attn_desc& d, const void* Q, const void* Ks, const void* V
   }
   const int n_cu = n_cu_of[dev];
   const int R = slab_rows(d.S);
-  const size_t lds = slab_lds_bytes(d.S, w.sw);
+  const size_t lds = slab_lds_bytes(d.S, w.sw, RP);
   if (!attr_set[dev][PREC]) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_slab_bwd_q_kernel<PREC>),
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&SLAB_KERNEL(PREC, RP)),
                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) return (int)e;
     attr_set[dev][PREC] = true;
   }
-  hipLaunchKernelGGL((attn_slab_bwd_q_kernel<PREC>), dim3(n_cu), dim3(STHREADS), lds, st, d, (const char*)Q,
+  hipLaunchKernelGGL((SLAB_KERNEL(PREC, RP)), dim3(n_cu), dim3(STHREADS), lds, st, d, (const char*)Q,
                      (const char*)Ks, (const char*)Vs, reinterpret_cast<const SlabKey*>(base),
                      reinterpret_cast<const int*>(base + w.off_beg), reinterpret_cast<const int*>(base + w.off_end),
                      reinterpret_cast<const int4*>(base + w.off_items), cnt, (const char*)table_pair, (const char*)dO,
-                     LSE, delta, grad_scale, dQ, dtable, w.n_slab, w.sw, R);
+                     LSE, delta, grad_scale, dQ, dtable, w.n_slab, w.sw, R
+#if BEVR_SLAB_ROWS
+                     , row0, n_rb_band
+#endif
+                     );
   return (int)hipGetLastError();
 }
 
+#if BEVR_SLAB_ROWS
+// any S up to 448: a small S runs on the 832 pitch like any other (its window is shorter than the pitch, as S < 200's is
+// at 448)
+bool slab_shape_ok(const bevr_attn_desc& d) {
+  return is16(d.precision) && d.S <= SLAB_ROWS_MAX_S && slab_rows(d.S) <= slab_pitch(d.S) && SLAB_CH <= 64 &&
+         slab_lds_bytes(d.S, slab_width(d.S, slab_pitch(d.S)), slab_pitch(d.S)) <= 160 * 1024;
+}
+// a band of row blocks: starts on a block, at most SNRB blocks, whole blocks unless it ends the column (no sum is formed
+// before its terms are bounded: 1 << 30 does not wrap)
+bool slab_band_ok(const bevr_attn_desc& d, int row0, int n_rows) {
+  if (row0 < 0 || row0 % SQROWS != 0 || n_rows < 1 || n_rows > SLAB_BAND_ROWS) return false;
+  if (row0 > d.S - n_rows) return false;
+  return n_rows % SQROWS == 0 || row0 == d.S - n_rows;
+}
+#define SLAB_WS_BYTES bevr_attn_slab_rows_ws_bytes
+#define SLAB_PREP bevr_attn_slab_rows_prep
+#else
 bool slab_shape_ok(const bevr_attn_desc& d) {
   return is16(d.precision) && slab_n_rb(d.S) <= SNRB && slab_rows(d.S) <= SLAB_RP && SLAB_CH <= 64 &&
          slab_lds_bytes(d.S, slab_width(d.S)) <= 160 * 1024;
 }
+#define SLAB_WS_BYTES bevr_attn_slab_ws_bytes
+#define SLAB_PREP bevr_attn_slab_prep
+#endif
 
 }  // namespace
 
-extern "C" size_t bevr_attn_slab_ws_bytes(const bevr_attn_desc* d) {
+extern "C" size_t SLAB_WS_BYTES(const bevr_attn_desc* d) {
   if (bevr_check_desc(d) || !slab_shape_ok(*d)) return 0;
   return slab_ws(*d).total;
 }
 
-extern "C" int bevr_attn_slab_prep(const bevr_attn_desc* d, const float* key_a, const float* key_b, const int* order,
-                                   void* slab_ws_, void* stream) {
+extern "C" int SLAB_PREP(const bevr_attn_desc* d, const float* key_a, const float* key_b, const int* order,
+                         void* slab_ws_, void* stream) {
   int rc = bevr_check_desc(d);
   if (rc) return rc;
   if (!key_a || !key_b || !order || !slab_ws_) return BEVR_E_NULL;
@@ -707,20 +779,40 @@ extern "C" int bevr_attn_slab_prep(const bevr_attn_desc* d, const float* key_a, 
   return (int)hipGetLastError();
 }
 
+#if BEVR_SLAB_ROWS
+extern "C" int bevr_attn_slab_bwd_q_rows(const bevr_attn_desc* d, const void* Q, const void* Ks, const void* Vs,
+                                         const void* slab_ws_, const float* table_pair, const void* dO, const float* LSE,
+                                         const float* delta, const float* grad_scale, float* dQ, float* dtable, int row0,
+                                         int n_rows, void* stream) {
+#else
 extern "C" int bevr_attn_slab_bwd_q(const bevr_attn_desc* d, const void* Q, const void* Ks, const void* Vs,
                                     const void* slab_ws_, const float* table_pair, const void* dO, const float* LSE,
                                     const float* delta, const float* grad_scale, float* dQ, float* dtable, void* stream) {
+#endif
   int rc = bevr_check_desc(d);
   if (rc) return rc;
   if (!Q || !Ks || !Vs || !slab_ws_ || !table_pair || !dO || !LSE || !delta || !grad_scale || !dQ || !dtable)
     return BEVR_E_NULL;
   if (!is16(d->precision)) return BEVR_E_PRECISION;
   if (!slab_shape_ok(*d)) return BEVR_E_SHAPE;
+#if BEVR_SLAB_ROWS
+  if (!slab_band_ok(*d, row0, n_rows)) return BEVR_E_SHAPE;
+#endif
   if (!bevr_aligned16(Q) || !bevr_aligned16(Ks) || !bevr_aligned16(Vs) || !bevr_aligned16(dO) || !bevr_aligned16(dQ) ||
       !bevr_aligned16(table_pair) || !bevr_aligned16(slab_ws_))
     return BEVR_E_ALIGN;
   hipStream_t st = (hipStream_t)stream;
+#if BEVR_SLAB_ROWS
+  const int nb = (n_rows + SQROWS - 1) / SQROWS;
+  const bool tall = slab_pitch(d->S) == SLAB_RP_B;
   if (d->precision == BEVR_PREC_BF16)
-    return launch<BEVR_PREC_BF16>(*d, Q, Ks, Vs, slab_ws_, table_pair, dO, LSE, delta, grad_scale, dQ, dtable, st);
-  return launch<BEVR_PREC_F16>(*d, Q, Ks, Vs, slab_ws_, table_pair, dO, LSE, delta, grad_scale, dQ, dtable, st);
+    return tall ? launch<BEVR_PREC_BF16, SLAB_RP_B>(*d, Q, Ks, Vs, slab_ws_, table_pair, dO, LSE, delta, grad_scale, dQ, dtable, row0, nb, st)
+                : launch<BEVR_PREC_BF16, SLAB_RP_A>(*d, Q, Ks, Vs, slab_ws_, table_pair, dO, LSE, delta, grad_scale, dQ, dtable, row0, nb, st);
+  return tall ? launch<BEVR_PREC_F16, SLAB_RP_B>(*d, Q, Ks, Vs, slab_ws_, table_pair, dO, LSE, delta, grad_scale, dQ, dtable, row0, nb, st)
+              : launch<BEVR_PREC_F16, SLAB_RP_A>(*d, Q, Ks, Vs, slab_ws_, table_pair, dO, LSE, delta, grad_scale, dQ, dtable, row0, nb, st);
+#else
+  if (d->precision == BEVR_PREC_BF16)
+    return launch<BEVR_PREC_BF16>(*d, Q, Ks, Vs, slab_ws_, table_pair, dO, LSE, delta, grad_scale, dQ, dtable, 0, 0, st);
+  return launch<BEVR_PREC_F16>(*d, Q, Ks, Vs, slab_ws_, table_pair, dO, LSE, delta, grad_scale, dQ, dtable, 0, 0, st);
+#endif
 }

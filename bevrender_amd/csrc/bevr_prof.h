@@ -3,8 +3,9 @@
 // A wave sums s_memtime differences (and event counts) of its phases in registers and adds them once, at its end, to a
 // per-kernel __device__ array that bevr_debug_prof_<tag>(out, reset) copies out or clears.  Without BEVR_PROF every
 // macro below expands to nothing, and so it does in the VARIANT translation units (BEVR_DROP, BEVR_TAP_X3,
-// BEVR_GATHER_ROWS: a kernel's source compiled a second time), which would define the array and its reader again.
-// Include it after those three have their defaults (bevr_common.h, attn_tap.h, attn_gather_fwd.hip).
+// BEVR_GATHER_ROWS, BEVR_SLAB_ROWS: a kernel's source compiled a second time), which would define the array and its reader
+// again.  Include it after those four have their defaults (bevr_common.h, attn_tap.h, attn_gather_fwd.hip,
+// attn_slab_bwd_q.hip).
 //
 //   BEVR_PROF_DEFINE(tag, n)      file scope: the n counters and their reader
 //   PROF_ACC(n)                   kernel body: the wave's accumulator
@@ -15,7 +16,7 @@
 #pragma once
 #include "bevr_common.h"
 
-#if defined(BEVR_PROF) && !(BEVR_DROP || BEVR_TAP_X3 || BEVR_GATHER_ROWS)
+#if defined(BEVR_PROF) && !(BEVR_DROP || BEVR_TAP_X3 || BEVR_GATHER_ROWS || BEVR_SLAB_ROWS)
 
 // PROF_T: memory counters drained, and `dep` (a value of the work just done) as an operand: the stamp cannot be hoisted
 // above that work.  The query-stationary region kernels.

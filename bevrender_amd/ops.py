@@ -536,6 +536,7 @@ class K:
     FWD, FWD_DROP = "bevr_attn_fwd", "bevr_attn_fwd_dropout"
     GATHER, GATHER_ROWS = "bevr_attn_gather_fwd", "bevr_attn_gather_fwd_rows"
     BWD_Q, BWD_Q_DROP, SLAB_BWD_Q = "bevr_attn_bwd_q", "bevr_attn_bwd_q_dropout", "bevr_attn_slab_bwd_q"
+    SLAB_BWD_Q_ROWS = "bevr_attn_slab_bwd_q_rows"
     BWD_K, BWD_K_DROP = "bevr_attn_bwd_k", "bevr_attn_bwd_k_dropout"
     CELL_FWD, CELL_BWD_Q, CELL_BWD_K = "bevr_attn_cell_fwd", "bevr_attn_cell_bwd_q", "bevr_attn_cell_bwd_k"
     TAP_FWD, TAP_FWD_DROP = "bevr_attn_tap_fwd", "bevr_attn_tap_fwd_dropout"
@@ -585,7 +586,7 @@ def attention_route(precision: int, groups: int, S: int, Wt: int, N: int, cell_s
     sample inside the tap grid?" (a reduction and a host sync at the caller): called at most once, and only for
     tap_source=True with dropout and a split that would otherwise be kept.  Raises attention_core's routing ValueErrors.
     Reads the A/B switches itself (BEVR_KNORM, BEVR_MERGE_TAP) or through gather_supported, slab_supported,
-    tap_supported and kv_source_supported."""
+    slab_rows_supported, tap_supported and kv_source_supported."""
     if dropout:
         if source == "tap_pix":
             raise ValueError("tap_pix has no attention dropout: pass every key's projected rows and no tap segment")
@@ -623,7 +624,10 @@ def attention_route(precision: int, groups: int, S: int, Wt: int, N: int, cell_s
             if gather_supported(precision, S):
                 gather = "whole" if len(gather_bands(S)) == 1 else "bands"
             fwd = {None: K.FWD, "whole": K.GATHER, "bands": K.GATHER_ROWS}[gather]
-            bwd_q = K.SLAB_BWD_Q if slab_supported(precision, S, Wt) else K.BWD_Q
+            if slab_rows_supported(precision, S, Wt):       # off unless BEVR_SLAB_ROWS asks for it
+                bwd_q = K.SLAB_BWD_Q_ROWS
+            else:
+                bwd_q = K.SLAB_BWD_Q if slab_supported(precision, S, Wt) else K.BWD_Q
             segs.append(KeySegment("region", 0, n_region, fwd, bwd_q, K.BWD_K))
     if tap and dropout:
         segs.append(KeySegment("tap", split, N, K.TAP_FWD_DROP, K.TAP_BWD_Q_DROP, K.TAP_BWD_K_DROP))
@@ -671,6 +675,36 @@ def slab_supported(precision, S, Wt=None) -> bool:
     if mode == "0" or precision not in (_lib.PREC_BF16, _lib.PREC_F16) or S > 211:
         return False
     return mode == "2" or Wt is None or Wt - 1 >= 4 * (S - 1)
+
+
+SLAB_ROWS_MAX_S, SLAB_BAND_BLOCKS = 448, 7
+
+
+def slab_rows_supported(precision, S, Wt=None) -> bool:
+    """Does the query-side backward over scattered keys run on the slab kernel IN ROW BANDS (bevr_attn_slab_bwd_q_rows:
+    the slab kernel with a column tall enough for S <= 448, one launch per band of slab_bands)?  The switch BEVR_SLAB_ROWS
+    decides: unset or 0 -- never (the default: every call keeps the route it has; config 5 measured 20 % faster with
+    it, profiles/r12_slab_rows.txt, and the default changes together with the pinned route table); 1 -- the sides the one-band kernel does not reach, 212 <= S <= 448, in the 16-bit modes, under slab_supported's
+    other rules (BEVR_SLAB=0 turns every slab route off; SCA-wide tables only, unless BEVR_SLAB=2); 2 -- every S <= 448
+    and every table width, ahead of the one-band kernel (tests, A/B timing)."""
+    mode = os.environ.get("BEVR_SLAB_ROWS", "0")
+    if mode not in ("1", "2") or precision not in (_lib.PREC_BF16, _lib.PREC_F16) or S > SLAB_ROWS_MAX_S:
+        return False
+    if mode == "2":
+        return True
+    slab = os.environ.get("BEVR_SLAB", "1")
+    return S > 211 and slab != "0" and (slab == "2" or Wt is None or Wt - 1 >= 4 * (S - 1))
+
+
+def slab_bands(S, max_blocks=None):
+    """The row ranges (row0, n_rows) the row-band slab backward covers a BEV column of S rows with: as few bands as the
+    seven worker waves allow (max_blocks = SLAB_BAND_BLOCKS row blocks of 31 rows each), of equal size up to the row
+    block -- S = 400: (0, 217), (217, 183); S = 448: (0, 155), (155, 155), (310, 138); S <= 217: one band."""
+    max_blocks = SLAB_BAND_BLOCKS if max_blocks is None else max_blocks
+    nb = -(-S // 31)
+    n = -(-nb // max_blocks)
+    step = 31 * (-(-nb // n))
+    return [(r, min(step, S - r)) for r in range(0, S, step)]
 
 
 def backward_scales(bound: torch.Tensor, pmax_log2: torch.Tensor, f16: bool, drop_thr: int = 0) -> torch.Tensor:
@@ -734,7 +768,9 @@ def _bwd_q_tile(name, o):
             flops=_attn_flops(o.g, 3), tag=_call_tag(o.g))
 
 
-def _bwd_q_slab(name, o):
+def _slab_operands(o, ws_bytes, prep):
+    """What both slab routes hand their kernel: the K and V rows in the sorted order and the prepared workspace
+    (ws_bytes, prep: the entry points of the route's slab width)."""
     g, Ke, Ve = o.g, o.Ke, o.Ve
     # keys sorted by table column b per problem-group; K and V rows gathered into that order (softmax and its
     # gradients do not depend on the order of the keys; dK / dV come from the key-side kernel in the caller's)
@@ -743,11 +779,26 @@ def _bwd_q_slab(name, o):
     idx = order.view(g.n_prob, g.groups, 1, g.N).expand(-1, -1, hpg, -1).reshape(g.n_prob, g.heads, g.N, 1)
     idx = idx.expand(-1, -1, -1, HEAD_DIM)
     Ks, Vs = Ke[:, :, :g.N].gather(2, idx), Ve[:, :, :g.N].gather(2, idx)
-    sws = torch.empty(_lib.lib().bevr_attn_slab_ws_bytes(C.byref(o.desc)), device=Ke.device, dtype=torch.uint8)
-    _launch("bevr_attn_slab_prep", C.byref(o.desc), _ptr(o.ka), _ptr(o.kb), _ptr(order.to(torch.int32).contiguous()),
-            _ptr(sws), _stream())
+    sws = torch.empty(getattr(_lib.lib(), ws_bytes)(C.byref(o.desc)), device=Ke.device, dtype=torch.uint8)
+    _launch(prep, C.byref(o.desc), _ptr(o.ka), _ptr(o.kb), _ptr(order.to(torch.int32).contiguous()), _ptr(sws), _stream())
+    return Ks, Vs, sws
+
+
+def _bwd_q_slab(name, o):
+    g = o.g
+    Ks, Vs, sws = _slab_operands(o, "bevr_attn_slab_ws_bytes", "bevr_attn_slab_prep")
     _launch(name, C.byref(o.desc), _ptr(o.Qe), _ptr(Ks), _ptr(Vs), _ptr(sws), _ptr(o.pair), _ptr(o.dOe), _ptr(o.LSE),
             _ptr(o.delta), _ptr(o.gscale), _ptr(o.dQ), _ptr(o.dT), _stream(), flops=_attn_flops(g, 3), tag=_call_tag(g))
+
+
+def _bwd_q_slab_rows(name, o):
+    g = o.g
+    # one sort, one gather and one prep for all bands; a band's launch resets the work list's counter itself
+    Ks, Vs, sws = _slab_operands(o, "bevr_attn_slab_rows_ws_bytes", "bevr_attn_slab_rows_prep")
+    for row0, n_rows in slab_bands(g.S):      # (the timer's name is the slab route's, whichever entry point runs it)
+        _launch(name, C.byref(o.desc), _ptr(o.Qe), _ptr(Ks), _ptr(Vs), _ptr(sws), _ptr(o.pair), _ptr(o.dOe), _ptr(o.LSE),
+                _ptr(o.delta), _ptr(o.gscale), _ptr(o.dQ), _ptr(o.dT), row0, n_rows, _stream(),
+                flops=_attn_flops(g, 3) * n_rows / g.S, tag=_call_tag(g), timer=K.SLAB_BWD_Q)
 
 
 def _bwd_k(name, o, *keys):
@@ -781,6 +832,7 @@ def _tap_bwd_k(name, o):
 
 _RUN = {K.FWD: _fwd_tile, K.FWD_DROP: _fwd_tile, K.GATHER: _fwd_gather, K.GATHER_ROWS: _fwd_gather, K.CELL_FWD: _fwd_cell,
         K.BWD_Q: _bwd_q_tile, K.BWD_Q_DROP: _bwd_q_tile, K.CELL_BWD_Q: _bwd_q_tile, K.SLAB_BWD_Q: _bwd_q_slab,
+        K.SLAB_BWD_Q_ROWS: _bwd_q_slab_rows,
         K.BWD_K: _bwd_k_tile, K.BWD_K_DROP: _bwd_k_tile, K.CELL_BWD_K: _bwd_k_cell,
         K.TAP_FWD: _tap_fwd, K.TAP_FWD_DROP: _tap_fwd, K.TAP_BWD_Q: _tap_bwd_q, K.TAP_BWD_Q_DROP: _tap_bwd_q,
         K.TAP_BWD_K: _tap_bwd_k, K.TAP_BWD_K_DROP: _tap_bwd_k}

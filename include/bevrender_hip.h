@@ -60,7 +60,9 @@ extern "C" {
  *    bevr_attn_gather_fwd_rows (the gather forward over a row range of every BEV column: BEV sides above 224), and
  *    bevr_attn_gather_fwd accepts BEVR_PREC_F16 where it returned BEVR_E_PRECISION;
  *    bevr_attn_tap_fwd, bevr_attn_tap_bwd_q and bevr_attn_tap_bwd_k accept BEVR_PREC_BF16X3 where they returned
- *    BEVR_E_PRECISION (operand format: "TAP entry points in BEVR_PREC_BF16X3" below). */
+ *    BEVR_E_PRECISION (operand format: "TAP entry points in BEVR_PREC_BF16X3" below);
+ *    bevr_attn_slab_rows_ws_bytes / _slab_rows_prep / bevr_attn_slab_bwd_q_rows (the slab query-side backward over a band
+ *    of BEV rows of every column: BEV sides up to 448; the three bevr_attn_slab_* entry points keep their contract). */
 #define BEVR_ABI_VERSION 6
 
 enum {
@@ -401,8 +403,9 @@ int bevr_attn_gather_fwd_rows(const bevr_attn_desc* d, const void* Q, const void
  * keeps bevr_attn_bwd_q: bevrender_amd/ops.py:slab_supported).  Any key set is handled.
  *   order  [n_prob*groups][N] int32: per problem-group, a permutation of 0..N-1 that sorts key_b ascending
  *   Ks, Vs [n_prob][heads][N][32] E: the K / V rows IN THAT ORDER (row t of (prob, head) = key order[pg][t]), unpadded
- *   slab_ws: bevr_attn_slab_ws_bytes(d) bytes (0: unsupported shape), written by bevr_attn_slab_prep, opaque; one
- *           bevr_attn_slab_bwd_q launch per prep (the launch consumes the work list's counter)
+ *   slab_ws: bevr_attn_slab_ws_bytes(d) bytes (0: unsupported shape), written by bevr_attn_slab_prep, opaque; a launch
+ *           resets the work list's item counter on its stream before it starts, so launches that follow one another on
+ *           a stream may share a prep (the launches of one workspace must not overlap: they share that counter)
  *   Q, table_pair, dO, LSE, delta, grad_scale: as bevr_attn_bwd_q
  *   dQ [n_prob][heads][Mp][32] float ACCUMULATED with float atomics (caller zeroes; bevr_attn_bwd_q WRITES its dQ)
  *   dtable ACCUMULATED (as bevr_attn_bwd_q)
@@ -413,6 +416,26 @@ int bevr_attn_slab_prep(const bevr_attn_desc* d, const float* key_a, const float
 int bevr_attn_slab_bwd_q(const bevr_attn_desc* d, const void* Q, const void* Ks, const void* Vs, const void* slab_ws,
                          const float* table_pair, const void* dO, const float* LSE, const float* delta,
                          const float* grad_scale, float* dQ, float* dtable, void* stream);
+/* The same for any S <= 448, over the BEV rows [row0, row0 + n_rows) of every BEV column (csrc/attn_slab_bwd_q_rows.hip:
+ * the same kernel with a taller slab column and seven worker waves that take the row blocks row0 / 31 ... of a column).
+ * The slab keeps EVERY table row the whole column can reach, whichever band is computed -- a pair's table row depends on
+ * the key and the query row alone -- so the bands of a column are independent launches that add into the same dQ
+ * (disjoint rows) and dtable: all of them together are bevr_attn_slab_bwd_q's result.  The slab is narrower for it
+ * (12 table columns up to S = 403, 10 above), and every band fills the slabs and streams the sorted K / V rows again.
+ *   bevr_attn_slab_rows_ws_bytes / _slab_rows_prep: as bevr_attn_slab_ws_bytes / _slab_prep, for this kernel's slab width
+ *           (0 / BEVR_E_SHAPE for S > 448, 0 / BEVR_E_PRECISION for a mode that is not 16-bit); the two workspaces are
+ *           not interchangeable.  ONE prep serves all bands of a call (launched one after another on a stream: see
+ *           slab_ws above).
+ *   bevr_attn_slab_bwd_q_rows: operands and checks of bevr_attn_slab_bwd_q, in its order (NULL, precision, shape,
+ *           alignment); the shape check also asks for row0 >= 0, row0 % 31 == 0, 1 <= n_rows <= 217 (seven row blocks of
+ *           31), row0 + n_rows <= S, and n_rows % 31 == 0 unless row0 + n_rows == S; else BEVR_E_SHAPE.  dQ of rows
+ *           outside the range is not touched.  bevrender_amd/ops.py:slab_bands cuts a column into such bands. */
+size_t bevr_attn_slab_rows_ws_bytes(const bevr_attn_desc* d);
+int bevr_attn_slab_rows_prep(const bevr_attn_desc* d, const float* key_a, const float* key_b, const int32_t* order,
+                             void* slab_ws, void* stream);
+int bevr_attn_slab_bwd_q_rows(const bevr_attn_desc* d, const void* Q, const void* Ks, const void* Vs, const void* slab_ws,
+                              const float* table_pair, const void* dO, const float* LSE, const float* delta,
+                              const float* grad_scale, float* dQ, float* dtable, int row0, int n_rows, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Bilinear feature sampling, align_corners=True, zero padding (grid_sample semantics).
