@@ -40,10 +40,27 @@
 // row ORIGIN moves -- the table row of a tap for the band's first BEV row, the Q / mref / O / LSE rows and the rows a
 // window must hold.  Rows outside the band are not written; the band that ends at S writes the rows past the grid as the
 // whole-column kernel does.  BEV sides up to 448 run as bands of at most 224 rows (bevrender_amd/ops.py).
+//
+// BEVR_GATHER_X3 = 1 (attn_gather_fwd_x3.hip, a translation unit of its own again, with BEVR_GATHER_ROWS = 1: the split
+// mode takes a row range from the start): BEVR_PREC_BF16X3.  Every matrix operand is two bf16 IMAGES, hi = bf16(x) and
+// lo = bf16(x - hi), of the 16-bit mode's shape and addressing, the lo image a fixed distance behind the hi image
+// (LdsGn<2>), and a product is three MFMAs, lo hi + hi lo + hi hi (mfma16s, attn_tap.h):
+//   Q, K, V   arrive in the split ROW format (bevr_common.h: 128-byte rows, per 16-element half hi(e0..7) | hi(e8..15) |
+//             lo(e0..7) | lo(e8..15)); the producer's direct-to-LDS loads put each 16-byte chunk into the image that
+//             needs it -- K hi / lo with the swizzle of the 16-bit image, V as a hi and a lo image of each channel half
+//   table     table_pk2[2][heads][Wp][Hp]: plane 0 the pairs of hi parts, plane 1 the pairs of lo parts; a window holds
+//             both, the lo plane LdsGn::WIN_PLANE behind the hi plane: ONE address per key, two direct-to-LDS loads per column
+//   W         computed in f32 by the producer, a hi and a lo image in the layout of w_image_pos
+//   P         split in registers after exp2; the row sum is the ones-operand product of BOTH parts -- of the values PV
+//             contracts
+// One workgroup per CU (152 KB of LDS), two waves per SIMD: see DESIGN.md "Split-bf16 mode on the gather forward".
 #include "attn_tap.h"
 
 #ifndef BEVR_GATHER_ROWS
 #define BEVR_GATHER_ROWS 0
+#endif
+#ifndef BEVR_GATHER_X3
+#define BEVR_GATHER_X3 0
 #endif
 
 #include "bevr_prof.h"
@@ -61,23 +78,30 @@ constexpr int PITCH = 272;             // column stride in dwords, = 16 (mod 32)
                                        // of ds_read_b32, conflict-free for every key position
 constexpr int WIN_COLS = 28;
 constexpr int STRIP_KEYS = WIN_COLS / 2;
-struct LdsG {
+// NP: images per operand (1; split mode 2: the lo image of K, of each V half, of W and of the window K_IMG, V_IMG, W_IMG
+// and WIN_PLANE bytes behind the hi image)
+template <int NP> struct LdsGn {
+  static constexpr int K_IMG = GT * 64, V_IMG = GT * 32, W_IMG = (GT / 16) * 2 * 64 * 16;
   static constexpr int OFF_K = 0;                       // [64 keys][4 chunks of 16 B], chunk c of key n at position c ^ ((n >> 2) & 3)
-  static constexpr int OFF_VLO = GT * 64;               // [64 keys][16 channels] 16-bit: channels 0..15
-  static constexpr int OFF_VHI = OFF_VLO + GT * 32;     // channels 16..31
-  static constexpr int OFF_W = OFF_VHI + GT * 32;       // the W operand AS THE LANES HOLD IT: [16-key sub-tile][bias product][lane]
+  static constexpr int OFF_VLO = NP * K_IMG;            // [64 keys][16 channels] 16-bit: channels 0..15
+  static constexpr int OFF_VHI = OFF_VLO + NP * V_IMG;  // channels 16..31
+  static constexpr int OFF_W = OFF_VHI + NP * V_IMG;    // the W operand AS THE LANES HOLD IT: [16-key sub-tile][bias product][lane]
                                                         // 16 bytes; zero but for one dword per (key, column): w_image_pos
-  static constexpr int W_BYTES = (GT / 16) * 2 * 64 * 16;
+  static constexpr int W_BYTES = NP * W_IMG;
   static constexpr int OFF_OFF = OFF_W + W_BYTES;       // [64 keys] LDS byte address of tap (y, x) for BEV row 0
   static constexpr int OFF_CT = OFF_OFF + GT * 4;       // u32x4: flags (bit 2: done), live keys 0..31, 32..63, entries of the fill list
   static constexpr int OFF_FD = OFF_CT + 16;            // fill list of the NEXT emission's window: [WIN_COLS] (column, first row)
   static constexpr int BUF = OFF_FD + WIN_COLS * 8;
-  static constexpr int WIN = WIN_COLS * PITCH * 4;
+  static constexpr int WIN_PLANE = WIN_COLS * PITCH * 4;
+  static constexpr int WIN = NP * WIN_PLANE;
   static constexpr int OFF_WIN = 2 * BUF;
   static constexpr int TOTAL = OFF_WIN + 2 * WIN;
 };
+typedef LdsGn<BEVR_GATHER_X3 ? 2 : 1> LdsG;
 static_assert(LdsG::BUF % 16 == 0 && LdsG::WIN % 16 == 0, "16-byte aligned LDS blocks");
-static_assert(2 * LdsG::TOTAL <= 160 * 1024, "two workgroups per CU");
+// 16-bit modes: two workgroups per CU; split mode: one (both planes of two full windows: DESIGN.md)
+static_assert((BEVR_GATHER_X3 ? 1 : 2) * LdsG::TOTAL <= 160 * 1024, "workgroups per CU");
+static_assert(LdsG::WIN_PLANE + 2 * QB * 4 < 65536, "the lo plane of a tap is an immediate offset of its hi plane's read");
 // Slot order of a bias product (8 keys x 4 taps = 32 slots of the contraction): k-group kg holds the dwords ((y, y + 1)
 // pairs) of keys 4 (kg >> 1) + {0 .. 3} at table column x + (kg & 1).  The A operand of product m of a 16-key sub-tile is
 // then, for lane (key li, k-group kg), dword dd = the key's packed weights of that column if li == 8 m + 4 (kg >> 1) + dd,
@@ -112,19 +136,32 @@ __device__ __forceinline__ void glds16(const char* src, char* lds_base) {
   __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)lds_base, 16, 0, 0);
 }
 
-#if BEVR_GATHER_ROWS
+#if BEVR_GATHER_X3
+#define BEVR_GATHER_KERNEL attn_gather_fwd_x3_kernel
+#define BEVR_GATHER_ROW_PARAMS , const int row0, const int n_rows
+#define BEVR_GATHER_WAVES_PER_SIMD 2      // one workgroup of 8 waves per CU: 256 registers
+#elif BEVR_GATHER_ROWS
 #define BEVR_GATHER_KERNEL attn_gather_fwd_rows_kernel
 #define BEVR_GATHER_ROW_PARAMS , const int row0, const int n_rows
+#define BEVR_GATHER_WAVES_PER_SIMD 4
 #else
 #define BEVR_GATHER_KERNEL attn_gather_fwd_kernel
 #define BEVR_GATHER_ROW_PARAMS
+#define BEVR_GATHER_WAVES_PER_SIMD 4
 #endif
+// table_pk: the 16-bit pair table [heads][Wp][Hp]; split mode: table_pk2 [2][heads][Wp][Hp], plane 1 the lo parts
 template <int PREC, int NB, bool EXACT, bool DMA>
-__global__ __launch_bounds__(512, 4) void BEVR_GATHER_KERNEL(
+__global__ __launch_bounds__(512, BEVR_GATHER_WAVES_PER_SIMD) void BEVR_GATHER_KERNEL(
     bevr_attn_desc d, const char* __restrict__ Q, const char* __restrict__ K, const char* __restrict__ V,
     const char* __restrict__ key_ws, const uint32_t* __restrict__ table_pk, const float* __restrict__ mref,
     float* __restrict__ O, float* __restrict__ LSE, int* __restrict__ flags BEVR_GATHER_ROW_PARAMS) {
   constexpr bool BAND = BEVR_GATHER_ROWS != 0;
+  constexpr bool X3 = tap_split(PREC);
+  static_assert(X3 == (BEVR_GATHER_X3 != 0), "the split mode lives in its own translation unit");
+  static_assert(!X3 || BAND, "the split mode takes a row range");
+  constexpr int NP = tap_np<PREC>;            // images per operand
+  constexpr int ROWB = X3 ? 128 : 64;         // bytes of a Q / K / V row
+  typedef TapHalf<PREC> H16;                  // the 16-bit arithmetic the images are made with
 #if !BEVR_GATHER_ROWS
   constexpr int row0 = 0, n_rows = 0;      // the whole column
 #endif
@@ -158,20 +195,26 @@ __global__ __launch_bounds__(512, 4) void BEVR_GATHER_KERNEL(
   // behind the emission's matrix work.  A table shorter than a window column (small problems) goes through registers.
   const char* tbl = reinterpret_cast<const char*>(table_pk + (size_t)hd * d.Wp * d.Hp);
   const unsigned lane16 = (unsigned)lane * 16u;
+  const size_t tbl_plane = (size_t)d.heads * d.Wp * d.Hp * 4;      // split mode: bytes from the hi plane to the lo plane
   auto fill_one = [&](char* win, int c, int xc, int r0) {      // xc, r0: uniform
     static_assert(ROWS == 256, "one 16-byte load per lane and column");
+    BEVR_ASSERT(c >= 0 && c < WIN_COLS && xc >= 0 && xc < d.Wp && r0 >= 0 && (DMA ? r0 + ROWS <= d.Hp : r0 < d.Hp));
     if constexpr (DMA) {       // the launcher's choice: the table is at least a window column tall
       // scalar base + this lane's 16 bytes: no vector address arithmetic next to the accumulators
       const char* sbase = tbl + ((size_t)__builtin_amdgcn_readfirstlane(xc) * d.Hp + __builtin_amdgcn_readfirstlane(r0)) * 4;
       glds16(sbase + lane16, win + (c * PITCH) * 4);
+      if constexpr (X3) glds16(sbase + tbl_plane + lane16, win + L::WIN_PLANE + (c * PITCH) * 4);
     } else {
       const int rr = r0 + 4 * lane;
-      const char* src = tbl + ((size_t)xc * d.Hp + rr) * 4;
-      u32x4 v = {0u, 0u, 0u, 0u};
 #pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if (rr + k < d.Hp) v[k] = *reinterpret_cast<const uint32_t*>(src + 4 * k);
-      *reinterpret_cast<u32x4*>(win + (c * PITCH) * 4 + lane * 16) = v;
+      for (int pl = 0; pl < NP; ++pl) {
+        const char* src = tbl + pl * tbl_plane + ((size_t)xc * d.Hp + rr) * 4;
+        u32x4 v = {0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (rr + k < d.Hp) v[k] = *reinterpret_cast<const uint32_t*>(src + 4 * k);
+        *reinterpret_cast<u32x4*>(win + pl * L::WIN_PLANE + (c * PITCH) * 4 + lane * 16) = v;
+      }
     }
   };
   auto fill_share = [&](const int* fd, char* win, int nfill) {
@@ -188,8 +231,8 @@ __global__ __launch_bounds__(512, 4) void BEVR_GATHER_KERNEL(
     const int pg = prob * d.groups + hd / (d.heads / d.groups);
     const KeyW* kws = reinterpret_cast<const KeyW*>(key_ws) + (size_t)pg * d.Np;
     const StepBox* box = reinterpret_cast<const StepBox*>(key_ws + key_ws_box_offset(d)) + (size_t)pg * (d.Np / 32);
-    const char* Kp = K + (size_t)ph * d.Np * 64;
-    const char* Vp = V + (size_t)ph * d.Np * 64;
+    const char* Kp = K + (size_t)ph * d.Np * ROWB;
+    const char* Vp = V + (size_t)ph * d.Np * ROWB;
     const int n_steps = d.Np / GT;
 
     // One emission: the keys `sel` of a 64-key step, their weights and window addresses, and the fill list of its window
@@ -198,7 +241,7 @@ __global__ __launch_bounds__(512, 4) void BEVR_GATHER_KERNEL(
     struct Em {
       unsigned long long sel;
       int step, nfill, fd_xc, fd_r0, koff;
-      u32x2 w;
+      u32x2 w[NP];      // the packed weights of the key's two columns, per image
     };
     int step = -1;
     unsigned long long rem = 0ull;
@@ -208,7 +251,9 @@ __global__ __launch_bounds__(512, 4) void BEVR_GATHER_KERNEL(
     StepBox sb0_n = box[0], sb1_n = box[NT - 1];
     int ar = 0, xc = 0, x0 = 0, a0w = 0, cols = 0;
     bool fits = false;
-    u32x2 w_t = {0u, 0u};
+    u32x2 w_t[NP];
+#pragma unroll
+    for (int pl = 0; pl < NP; ++pl) w_t[pl] = u32x2{0u, 0u};
     auto advance = [&](Em& em) -> bool {
       while (rem == 0ull) {      // on to the next step with live keys
         if (++step >= n_steps) return false;
@@ -227,8 +272,13 @@ __global__ __launch_bounds__(512, 4) void BEVR_GATHER_KERNEL(
         const float xf = floorf(tx);
         xc = (int)xf + d.x_off;                        // padded table column of tap (., x)
         const float fx = tx - xf, fy = kw.fy;
-        w_t[0] = Half<PREC>::pack2((1.0f - fx) * (1.0f - fy), (1.0f - fx) * fy);
-        w_t[1] = Half<PREC>::pack2(fx * (1.0f - fy), fx * fy);
+        if constexpr (X3) {
+          TAP_SPLIT2((1.0f - fx) * (1.0f - fy), (1.0f - fx) * fy, w_t[0][0], w_t[NP - 1][0]);
+          TAP_SPLIT2(fx * (1.0f - fy), fx * fy, w_t[0][1], w_t[NP - 1][1]);
+        } else {
+          w_t[0][0] = H16::pack2((1.0f - fx) * (1.0f - fy), (1.0f - fx) * fy);
+          w_t[0][1] = H16::pack2(fx * (1.0f - fy), fx * fy);
+        }
         // the step's box: columns [x0, x1], rows [a0, a0 + rspan)
         x0 = (int)floorf(jrx + sb.bmin) + d.x_off;
         const int x1 = (int)floorf(jrx + sb.bmax) + 1 + d.x_off;
@@ -237,7 +287,8 @@ __global__ __launch_bounds__(512, 4) void BEVR_GATHER_KERNEL(
         a0w = max(0, min(sb.amin + d.y_off + (BAND ? row0 : 0), d.Hp - ROWS));
         rem = __ballot(live);
       }
-      em.w = w_t;
+      em.w[0] = w_t[0];
+      if constexpr (X3) em.w[NP - 1] = w_t[NP - 1];
       em.step = step;
       if (fits) {
         em.sel = rem;
@@ -275,18 +326,36 @@ __global__ __launch_bounds__(512, 4) void BEVR_GATHER_KERNEL(
 #pragma unroll
       for (int i = 0; i < GT / 16; ++i) {      // keys 16 i .. 16 i + 15: lane = (key, position)
         const int n = 16 * i + (lane >> 2), c = (lane & 3) ^ ((n >> 2) & 3);
-        glds16(Kp + (n0 + n) * 64 + 16 * c, bb + L::OFF_K + i * 1024);
+        if constexpr (X3) {      // elements 8 c .. 8 c + 7 of the split row: half c >> 1, chunk c & 1; the lo parts 32 bytes on
+          const char* src = Kp + (n0 + n) * ROWB + 64 * (c >> 1) + 16 * (c & 1);
+          glds16(src, bb + L::OFF_K + i * 1024);
+          glds16(src + 32, bb + L::OFF_K + L::K_IMG + i * 1024);
+        } else {
+          glds16(Kp + (n0 + n) * 64 + 16 * c, bb + L::OFF_K + i * 1024);
+        }
       }
 #pragma unroll
       for (int i = 0; i < NT; ++i) {           // keys 32 i .. 32 i + 31: lane = (key, 16-byte half of the 16 channels)
         const int n = 32 * i + (lane >> 1);
-        glds16(Vp + (n0 + n) * 64 + 16 * (lane & 1), bb + L::OFF_VLO + i * 1024);
-        glds16(Vp + (n0 + n) * 64 + 32 + 16 * (lane & 1), bb + L::OFF_VHI + i * 1024);
+        if constexpr (X3) {      // a split row: hi(ch 0..15) | lo(ch 0..15) | hi(ch 16..31) | lo(ch 16..31), 32 bytes each
+          const char* src = Vp + (n0 + n) * ROWB + 16 * (lane & 1);
+          glds16(src, bb + L::OFF_VLO + i * 1024);
+          glds16(src + 32, bb + L::OFF_VLO + L::V_IMG + i * 1024);
+          glds16(src + 64, bb + L::OFF_VHI + i * 1024);
+          glds16(src + 96, bb + L::OFF_VHI + L::V_IMG + i * 1024);
+        } else {
+          glds16(Vp + (n0 + n) * 64 + 16 * (lane & 1), bb + L::OFF_VLO + i * 1024);
+          glds16(Vp + (n0 + n) * 64 + 32 + 16 * (lane & 1), bb + L::OFF_VHI + i * 1024);
+        }
       }
       if (klane) {
         char* wk = bb + L::OFF_W + (kl >> 4) * 2048 + w_image_pos(kl & 15);
-        *reinterpret_cast<uint32_t*>(wk) = em.w[0];
-        *reinterpret_cast<uint32_t*>(wk + 256) = em.w[1];
+        *reinterpret_cast<uint32_t*>(wk) = em.w[0][0];
+        *reinterpret_cast<uint32_t*>(wk + 256) = em.w[0][1];
+        if constexpr (X3) {
+          *reinterpret_cast<uint32_t*>(wk + L::W_IMG) = em.w[NP - 1][0];
+          *reinterpret_cast<uint32_t*>(wk + L::W_IMG + 256) = em.w[NP - 1][1];
+        }
         // a key outside the emission: any address inside the window (its logit is masked)
         const bool in = em.sel >> kl & 1ull;
         *reinterpret_cast<unsigned*>(bb + L::OFF_OFF + kl * 4) = smem_base + L::OFF_WIN + (e & 1) * L::WIN + (in ? em.koff : 0);
@@ -353,7 +422,7 @@ __global__ __launch_bounds__(512, 4) void BEVR_GATHER_KERNEL(
   // ---- row-block waves --------------------------------------------------------------------------------------
   const int blk0 = wave * NB;
   const int qb = prob / d.q_div;
-  bf16x8 qf[NB];          // B operand of QK^T: Q[q][8 kg ..]
+  TapOp<NP> qf[NB];       // B operand of QK^T: Q[q][8 kg ..]
   f32x4 o_lo[NB], o_hi[NB];
   f32x4 negm[NB];         // minus the softmax reference: the accumulator start of every logit product
   f32x4 lacc[NB];         // row sum: a product of the ROUNDED weights with a ones operand (every register the same sum):
@@ -366,15 +435,18 @@ __global__ __launch_bounds__(512, 4) void BEVR_GATHER_KERNEL(
   for (int nb = 0; nb < NB; ++nb) {
     const int row = (BAND ? row0 : 0) + min(blk0 + nb, nblk - 1) * QB + li;
     const size_t mcol = (size_t)j * d.Sp + row;
-    qf[nb] = __builtin_bit_cast(
-        bf16x8, *reinterpret_cast<const u32x4*>(Q + ((((size_t)qb * d.heads + hd) * Mp + mcol) * 32 + 8 * kg) * 2));
+    if constexpr (X3)      // elements 8 kg .. 8 kg + 7 of the split row, the lo parts 32 bytes behind the hi parts
+      qf[nb] = tap_ld<NP>(Q + (((size_t)qb * d.heads + hd) * Mp + mcol) * ROWB + 64 * (kg >> 1) + 16 * (kg & 1), 32);
+    else
+      qf[nb].p[0] = __builtin_bit_cast(
+          bf16x8, *reinterpret_cast<const u32x4*>(Q + ((((size_t)qb * d.heads + hd) * Mp + mcol) * 32 + 8 * kg) * 2));
     o_lo[nb] = o_hi[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
     const float mr = EXACT ? 0.f : mref[(size_t)ph * Mp + mcol];
     negm[nb] = f32x4{-mr, -mr, -mr, -mr};
     lacc[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
     pmx[nb] = 0.f;
   }
-  const uint32_t one2 = Half<PREC>::pack2(1.0f, 1.0f);
+  const uint32_t one2 = H16::pack2(1.0f, 1.0f);
   const bf16x8 ones = __builtin_bit_cast(bf16x8, u32x4{one2, one2, one2, one2});
   const int t_off = (4 * kg + (li >> 2)) * 32 + (lane & 3) * 8;      // transposed reads of a [key][16] image
   const int k_off = li * 64 + 16 * (kg ^ (li >> 2));                 // this lane's K fragment in a 16-key block
@@ -414,17 +486,16 @@ __global__ __launch_bounds__(512, 4) void BEVR_GATHER_KERNEL(
       const unsigned livem = (unsigned)__builtin_amdgcn_readfirstlane((int)(t ? ct[2] : ct[1]));
       // (no shortcut for a tile or sub-tile without live keys -- strip emissions only: its keys are masked like any
       // other; every accumulator update stays unconditional, which keeps the accumulators in place)
-      const bf16x8 vlo = lds_tr8(bb + L::OFF_VLO + t * 1024 + t_off, 512);
-      const bf16x8 vhi = lds_tr8(bb + L::OFF_VHI + t * 1024 + t_off, 512);
-      u32x4 pw[NB];          // the tile's weights, packed: the B operand of PV
+      const TapOp<NP> vlo = tap_ld_tr<NP>(bb + L::OFF_VLO + t * 1024 + t_off, 512, L::V_IMG);
+      const TapOp<NP> vhi = tap_ld_tr<NP>(bb + L::OFF_VHI + t * 1024 + t_off, 512, L::V_IMG);
+      u32x4 pw[NB][NP];      // the tile's weights, packed: the B operand of PV
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2) {
         const int kb = 32 * t + 16 * s2;                 // first key of the sub-tile
-        const bf16x8 kf = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(bb + L::OFF_K + kb * 64 + k_off));
+        const TapOp<NP> kf = tap_ld<NP>(bb + L::OFF_K + kb * 64 + k_off, L::K_IMG);
         // W as the lanes hold it (w_image_pos): two 16-byte reads, no per-lane selection
-        const bf16x8 wa0 = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(bb + L::OFF_W + kb * 128 + lane * 16));
-        const bf16x8 wa1 =
-            __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(bb + L::OFF_W + kb * 128 + 1024 + lane * 16));
+        const TapOp<NP> wa0 = tap_ld<NP>(bb + L::OFF_W + kb * 128 + lane * 16, L::W_IMG);
+        const TapOp<NP> wa1 = tap_ld<NP>(bb + L::OFF_W + kb * 128 + 1024 + lane * 16, L::W_IMG);
         const int kq = 4 * (kg >> 1);
         // window addresses of keys kq .. kq + 3 (first bias product) and 8 + kq .. 8 + kq + 3 (second)
         const u32x4 oc0 = *reinterpret_cast<const u32x4*>(bb + L::OFF_OFF + (kb + kq) * 4);
@@ -432,28 +503,45 @@ __global__ __launch_bounds__(512, 4) void BEVR_GATHER_KERNEL(
         // both row blocks' logit chains first (independent: their matrix products interleave), then the weights.  A wave
         // whose second block lies past the column computes it on the clamped rows and drops it in the epilogue.
         f32x4 sv[NB];
-        u32x4 g0[NB], g1[NB];
+        u32x4 g0[NB][NP], g1[NB][NP];
 #pragma unroll
         for (int dd = 0; dd < 4; ++dd) {
           const lds_u32p p0 = (lds_u32p)(uintptr_t)(oc0[dd] + qoff0), p1 = (lds_u32p)(uintptr_t)(oc1[dd] + qoff0);
+#ifdef BEVR_DEBUG
+          {      // every tap read lies inside the emission's window (the hi plane; the lo plane is the same offset in its own)
+            const unsigned w0 = smem_base + L::OFF_WIN + (e & 1) * L::WIN, last = (unsigned)((NBX - 1) * OFF1) * 4u;
+            BEVR_ASSERT(oc0[dd] + qoff0 >= w0 && oc0[dd] + qoff0 + last + 4u <= w0 + L::WIN_PLANE);
+            BEVR_ASSERT(oc1[dd] + qoff0 >= w0 && oc1[dd] + qoff0 + last + 4u <= w0 + L::WIN_PLANE);
+          }
+#endif
+          if constexpr (X3) {      // the lo plane: the same address, WIN_PLANE further (an immediate offset; volatile as
+                                   // below: hi and lo would merge into a ds_read2st64_b32 whose pair feeds two operands)
+#pragma unroll
+            for (int nb = 0; nb < NBX; ++nb) {
+              g0[nb][0][dd] = ((vlds_u32p)p0)[nb * OFF1];
+              g1[nb][0][dd] = ((vlds_u32p)p1)[nb * OFF1];
+              g0[nb][NP - 1][dd] = ((vlds_u32p)p0)[nb * OFF1 + L::WIN_PLANE / 4];
+              g1[nb][NP - 1][dd] = ((vlds_u32p)p1)[nb * OFF1 + L::WIN_PLANE / 4];
+            }
+          } else
 #pragma unroll
           for (int nb = 0; nb < NBX; ++nb) {
             // (volatile: kept from merging with the first block's read into a ds_read2_b32, whose register PAIR would have to
             // be moved apart into the two blocks' operands -- vector instructions are what this loop is short of)
             if (nb == 0) {
-              g0[nb][dd] = p0[0];
-              g1[nb][dd] = p1[0];
+              g0[nb][0][dd] = p0[0];
+              g1[nb][0][dd] = p1[0];
             } else {
-              g0[nb][dd] = ((vlds_u32p)p0)[nb * OFF1];
-              g1[nb][dd] = ((vlds_u32p)p1)[nb * OFF1];
+              g0[nb][0][dd] = ((vlds_u32p)p0)[nb * OFF1];
+              g1[nb][0][dd] = ((vlds_u32p)p1)[nb * OFF1];
             }
           }
         }
 #pragma unroll
         for (int nb = 0; nb < NBX; ++nb) {
-          sv[nb] = mfma16<PREC>(kf, qf[nb], negm[nb]);
-          sv[nb] = mfma16<PREC>(wa0, __builtin_bit_cast(bf16x8, g0[nb]), sv[nb]);
-          sv[nb] = mfma16<PREC>(wa1, __builtin_bit_cast(bf16x8, g1[nb]), sv[nb]);
+          sv[nb] = tap_mm<PREC>(kf, qf[nb], negm[nb]);
+          sv[nb] = tap_mm<PREC>(wa0, tap_op(g0[nb]), sv[nb]);
+          sv[nb] = tap_mm<PREC>(wa1, tap_op(g1[nb]), sv[nb]);
         }
         if ((livem >> (16 * s2) & 0xffffu) != 0xffffu) {      // uniform: padding keys, or a strip emission
 #pragma unroll
@@ -481,24 +569,37 @@ __global__ __launch_bounds__(512, 4) void BEVR_GATHER_KERNEL(
               pmx[nb] *= al;
               sv[nb] -= delta;
               if (s2 == 1) {       // the first sub-tile's weights of this tile are in pw already
-                pw[nb][0] = Half<PREC>::pack2(Half<PREC>::lo(pw[nb][0]) * al, Half<PREC>::hi(pw[nb][0]) * al);
-                pw[nb][1] = Half<PREC>::pack2(Half<PREC>::lo(pw[nb][1]) * al, Half<PREC>::hi(pw[nb][1]) * al);
+#pragma unroll
+                for (int k = 0; k < 2; ++k) {
+                  if constexpr (X3)      // hi + lo is the weight PV contracts: rescaled and split again
+                    tap_pack2<PREC>((H16::lo(pw[nb][0][k]) + H16::lo(pw[nb][NP - 1][k])) * al,
+                                    (H16::hi(pw[nb][0][k]) + H16::hi(pw[nb][NP - 1][k])) * al, k, pw[nb]);
+                  else
+                    pw[nb][0][k] = H16::pack2(H16::lo(pw[nb][0][k]) * al, H16::hi(pw[nb][0][k]) * al);
+                }
               }
             }
           }
           const f32x2 pa = {fast_exp2(sv[nb][0]), fast_exp2(sv[nb][1])}, pb2 = {fast_exp2(sv[nb][2]), fast_exp2(sv[nb][3])};
-          pw[nb][2 * s2] = Half<PREC>::pack2(pa[0], pa[1]);
-          pw[nb][2 * s2 + 1] = Half<PREC>::pack2(pb2[0], pb2[1]);
+          if constexpr (X3) {
+            tap_pack2<PREC>(pa[0], pa[1], 2 * s2, pw[nb]);
+            tap_pack2<PREC>(pb2[0], pb2[1], 2 * s2 + 1, pw[nb]);
+          } else {
+            pw[nb][0][2 * s2] = H16::pack2(pa[0], pa[1]);
+            pw[nb][0][2 * s2 + 1] = H16::pack2(pb2[0], pb2[1]);
+          }
           pmx[nb] = fmaxf(fmaxf(fmaxf(pmx[nb], pa[0]), pa[1]), fmaxf(pb2[0], pb2[1]));
         }
         if constexpr (EXACT) first = false;
       }
 #pragma unroll
       for (int nb = 0; nb < NBX; ++nb) {
-        const bf16x8 pb = __builtin_bit_cast(bf16x8, pw[nb]);
-        o_lo[nb] = mfma16<PREC>(vlo, pb, o_lo[nb]);
-        o_hi[nb] = mfma16<PREC>(vhi, pb, o_hi[nb]);
-        lacc[nb] = mfma16<PREC>(ones, pb, lacc[nb]);
+        const TapOp<NP> pb = tap_op(pw[nb]);
+        o_lo[nb] = tap_mm<PREC>(vlo, pb, o_lo[nb]);
+        o_hi[nb] = tap_mm<PREC>(vhi, pb, o_hi[nb]);
+        // (split mode: ones . lo + ones . hi, the f32 sum of exactly the values PV contracts)
+#pragma unroll
+        for (int pl = NP - 1; pl >= 0; --pl) lacc[nb] = mfma16<PREC>(ones, pb.p[pl], lacc[nb]);
       }
     }
     PROF_T_FREE(c2);
@@ -582,10 +683,23 @@ int launch(const bevr_attn_desc& d, const void* Q, const void* K, const void* V,
 #else
 #define BEVR_GATHER_ROW_ARGS
 #endif
-#define BEVR_GATHER_LAUNCH(NB_, EX_, DMA_)                                                                           \
+#define BEVR_GATHER_LAUNCH_(NB_, EX_, DMA_)                                                                          \
   hipLaunchKernelGGL((BEVR_GATHER_KERNEL<PREC, NB_, EX_, DMA_>), dim3(grid), block, L::TOTAL, st, d,                \
                      (const char*)Q, (const char*)K, (const char*)V, (const char*)key_ws, (const uint32_t*)table_pk, \
                      mref, O, LSE, flags BEVR_GATHER_ROW_ARGS)
+#if BEVR_GATHER_X3
+  // more than 64 KB of dynamic LDS: the limit is raised per kernel AND per device, so on every launch (a "done once" flag
+  // would leave every device but the first at 64 KB)
+#define BEVR_GATHER_LAUNCH(NB_, EX_, DMA_)                                                                           \
+  do {                                                                                                               \
+    const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(&BEVR_GATHER_KERNEL<PREC, NB_, EX_, DMA_>), \
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, L::TOTAL);                 \
+    if (ea != hipSuccess) return (int)ea;                                                                            \
+    BEVR_GATHER_LAUNCH_(NB_, EX_, DMA_);                                                                             \
+  } while (0)
+#else
+#define BEVR_GATHER_LAUNCH(NB_, EX_, DMA_) BEVR_GATHER_LAUNCH_(NB_, EX_, DMA_)
+#endif
   const bool dma = d.Hp >= ROWS;        // else (small problems): the window columns are copied through registers
   for (int ex = 0; ex < 2; ++ex) {       // static reference, then the exact pass over the flagged columns
     if (nb == 1) {
@@ -599,12 +713,27 @@ int launch(const bevr_attn_desc& d, const void* Q, const void* K, const void* V,
     if (rc) return rc;
   }
 #undef BEVR_GATHER_LAUNCH
+#undef BEVR_GATHER_LAUNCH_
   return BEVR_OK;
 }
 
 }  // namespace
 
-#if !BEVR_GATHER_ROWS
+#if BEVR_GATHER_X3
+extern "C" int bevr_attn_gather_fwd_x3(const bevr_attn_desc* d, const void* Q, const void* K, const void* V,
+                                       const void* key_ws, const void* table_pk2, const float* mref, float* O,
+                                       float* LSE, int* flags, int row0, int n_rows, void* stream) {
+  int rc = bevr_check_desc(d);
+  if (rc) return rc;
+  if (!Q || !K || !V || !key_ws || !table_pk2 || !mref || !O || !LSE || !flags) return BEVR_E_NULL;
+  if (!bevr_aligned16(Q) || !bevr_aligned16(K) || !bevr_aligned16(V) || !bevr_aligned16(O) || !bevr_aligned16(key_ws))
+    return BEVR_E_ALIGN;
+  if (d->precision != BEVR_PREC_BF16X3) return BEVR_E_PRECISION;
+  if (row0 < 0 || row0 % QB != 0 || n_rows < 1 || n_rows > 14 * QB || n_rows > d->S - row0) return BEVR_E_SHAPE;
+  return launch<BEVR_PREC_BF16X3>(*d, Q, K, V, key_ws, table_pk2, mref, O, LSE, flags, row0, n_rows, (hipStream_t)stream);
+}
+
+#elif !BEVR_GATHER_ROWS
 extern "C" int bevr_attn_gather_fwd(const bevr_attn_desc* d, const void* Q, const void* K, const void* V,
                                     const void* key_ws, const void* table_pk, const float* mref, float* O, float* LSE,
                                     int* flags, void* stream) {

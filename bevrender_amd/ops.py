@@ -535,6 +535,7 @@ class K:
     """The attention kernels a route chooses among (include/bevrender_hip.h), each entry point spelled once."""
     FWD, FWD_DROP = "bevr_attn_fwd", "bevr_attn_fwd_dropout"
     GATHER, GATHER_ROWS = "bevr_attn_gather_fwd", "bevr_attn_gather_fwd_rows"
+    GATHER_X3 = "bevr_attn_gather_fwd_x3"
     BWD_Q, BWD_Q_DROP, SLAB_BWD_Q = "bevr_attn_bwd_q", "bevr_attn_bwd_q_dropout", "bevr_attn_slab_bwd_q"
     SLAB_BWD_Q_ROWS = "bevr_attn_slab_bwd_q_rows"
     BWD_K, BWD_K_DROP = "bevr_attn_bwd_k", "bevr_attn_bwd_k_dropout"
@@ -623,7 +624,10 @@ def attention_route(precision: int, groups: int, S: int, Wt: int, N: int, cell_s
         else:
             if gather_supported(precision, S):
                 gather = "whole" if len(gather_bands(S)) == 1 else "bands"
-            fwd = {None: K.FWD, "whole": K.GATHER, "bands": K.GATHER_ROWS}[gather]
+            if precision == _lib.PREC_BF16X3 and gather:     # one entry point, whole columns as the range (0, S)
+                fwd = K.GATHER_X3
+            else:
+                fwd = {None: K.FWD, "whole": K.GATHER, "bands": K.GATHER_ROWS}[gather]
             if slab_rows_supported(precision, S, Wt):       # off unless BEVR_SLAB_ROWS asks for it
                 bwd_q = K.SLAB_BWD_Q_ROWS
             else:
@@ -647,11 +651,26 @@ def gather_supported(precision, S) -> bool:
     """Does the forward over scattered keys run on the gather kernel (csrc/attn_gather_fwd.hip: bias on the matrix cores,
     table taps gathered from an LDS window) instead of the region kernel?  bf16 and fp16 operands, S <= 448 (the module's
     and the tap kernels' limit): a window column holds a key's taps for up to 224 BEV rows, a taller column runs as
-    bands (gather_bands); BEVR_GATHER=0 turns it off (A/B timing)."""
-    return precision in (_lib.PREC_BF16, _lib.PREC_F16) and S <= GATHER_MAX_S and os.environ.get("BEVR_GATHER", "1") != "0"
+    bands (gather_bands); BEVR_GATHER=0 turns it off (A/B timing).  The split-bf16 mode (BEVR_PREC_BF16X3:
+    csrc/attn_gather_fwd_x3.hip, bevr_attn_gather_fwd_x3) under the same limits when BEVR_GATHER_X3=1; the switch's
+    default is GATHER_X3_DEFAULT: off, that mode's earlier routing (the region kernel), until the pinned route table
+    changes with it."""
+    if S > GATHER_MAX_S or os.environ.get("BEVR_GATHER", "1") == "0":
+        return False
+    if precision == _lib.PREC_BF16X3:
+        return os.environ.get("BEVR_GATHER_X3", GATHER_X3_DEFAULT) != "0"
+    return precision in (_lib.PREC_BF16, _lib.PREC_F16)
 
 
 GATHER_MAX_S, GATHER_BAND_ROWS = 448, 224
+GATHER_X3_DEFAULT = "0"                           # BEVR_GATHER_X3 when unset (gather_supported)
+
+
+def gather_split_table(pair: torch.Tensor) -> torch.Tensor:
+    """The table operand of bevr_attn_gather_fwd_x3 (include/bevrender_hip.h: table_pk2) from the f32 pair table
+    (h, Wp, Hp, 2): (2, h, Wp, Hp, 2) bf16, plane 0 = bf16(pair), plane 1 = bf16(pair - plane 0).  Any device."""
+    hi = pair.to(torch.bfloat16)
+    return torch.stack((hi, (pair.float() - hi.float()).to(torch.bfloat16))).contiguous()
 
 
 def gather_bands(S):
@@ -740,20 +759,25 @@ def _fwd_cell(name, o):
 
 def _fwd_gather(name, o):
     g, Ttc = o.g, o.Ttc
-    pair_pk = o.pair.to(o.Qe.dtype)             # (h, Wp, Hp, 2) 16-bit: one dword per (column, row) entry
+    x3 = name == K.GATHER_X3
+    # (h, Wp, Hp, 2) 16-bit: one dword per (column, row) entry; split mode: a plane of hi parts and one of lo parts
+    pair_pk = gather_split_table(o.pair) if x3 else o.pair.to(o.Qe.dtype)
     # Tt is the table in log2 units already; two-stage maximum (a reduction to `heads` outputs in one stage
     # runs on `heads` workgroups: 0.6 ms for the 27 MB table)
     tmax = torch.maximum(Ttc.amax(-1).amax(-1), -Ttc.amin(-1).amin(-1))
-    qn = torch.linalg.vector_norm(o.Qe, dim=-1, dtype=torch.float32)          # (B, h, Mp)
+    # (split mode: Qe and Ke hold raw bf16 planes in a float container -- the norms come from the float rows)
+    qn = torch.linalg.vector_norm(o.Qp if x3 else o.Qe, dim=-1, dtype=torch.float32)          # (B, h, Mp)
     # static softmax reference: |Q_q . K_n| <= ||Q_q|| max_n ||K_n||, |bias| <= max |T2| (a convex combination;
     # 1 % for the 16-bit rounding of operands and weights), minus the headroom
     if o.kn2 is not None:      # of the unrounded rows: the rounding is inside the 1 % below
         kmx = o.kn2.sqrt()
+    elif x3:                   # the segment's projected K rows (B', N, h c) before they were packed
+        kmx = torch.linalg.vector_norm(o.krows.reshape(g.n_prob, g.N, g.heads, -1), dim=-1, dtype=torch.float32).amax(1)
     else:
         kmx = torch.linalg.vector_norm(o.Ke[:, :, :g.N], dim=-1, dtype=torch.float32).amax(-1)    # (B', h)
     ub = 1.01 * (qn.repeat_interleave(g.q_div, 0) * kmx[..., None] + tmax[None, :, None]) + 0.01
     mref = (ub - tap_headroom(g.precision)).contiguous()
-    bands = gather_bands(g.S) if name == K.GATHER_ROWS else [()]
+    bands = gather_bands(g.S) if name in (K.GATHER_ROWS, K.GATHER_X3) else [()]
     # scratch of one call's two passes: zeroed per call (per band)
     gflags = torch.zeros(len(bands), g.n_prob * g.heads * g.S, device=o.O.device, dtype=torch.int32)
     for bi, rows in enumerate(bands):       # rows = (row0, n_rows); (the timer's name is the route's, whichever entry point runs it)
@@ -830,7 +854,8 @@ def _tap_bwd_k(name, o):
             _stream(), flops=_attn_flops(o.g, 4), tag=_call_tag(o.g))
 
 
-_RUN = {K.FWD: _fwd_tile, K.FWD_DROP: _fwd_tile, K.GATHER: _fwd_gather, K.GATHER_ROWS: _fwd_gather, K.CELL_FWD: _fwd_cell,
+_RUN = {K.FWD: _fwd_tile, K.FWD_DROP: _fwd_tile, K.GATHER: _fwd_gather, K.GATHER_ROWS: _fwd_gather,
+        K.GATHER_X3: _fwd_gather, K.CELL_FWD: _fwd_cell,
         K.BWD_Q: _bwd_q_tile, K.BWD_Q_DROP: _bwd_q_tile, K.CELL_BWD_Q: _bwd_q_tile, K.SLAB_BWD_Q: _bwd_q_slab,
         K.SLAB_BWD_Q_ROWS: _bwd_q_slab_rows,
         K.BWD_K: _bwd_k_tile, K.BWD_K_DROP: _bwd_k_tile, K.CELL_BWD_K: _bwd_k_cell,
@@ -908,7 +933,7 @@ class _AttnCore(torch.autograd.Function):
         # plane 0: log2-sum-exp; plane 1: a bound of log2 of the row's largest softmax weight (rows past the grid: -inf here)
         LSE = torch.full((2, geom.n_prob, geom.heads, geom.Mp), float("-inf"), device=dev, dtype=torch.float32)
         need_bwd = any(ctx.needs_input_grad)
-        o = SimpleNamespace(Qe=Qe, pair=pair, Ttc=Ttc, O=O, LSE=LSE, drop=ctx.drop or ())
+        o = SimpleNamespace(Qe=Qe, Qp=Qp, pair=pair, Ttc=Ttc, O=O, LSE=LSE, drop=ctx.drop or ())
         saved = []
         for i, sg in enumerate(segs):
             g = dc_replace(geom, N=sg.n1 - sg.n0)
@@ -941,7 +966,8 @@ class _AttnCore(torch.autograd.Function):
             # per-key table coordinates + per-tile tap boxes, shared by the forward and the backward passes
             key_ws = torch.empty(L.bevr_attn_key_ws_bytes(C.byref(d)), device=dev, dtype=torch.uint8)
             _launch("bevr_attn_key_prep", C.byref(d), _ptr(ka), _ptr(kb), _ptr(key_ws), _stream())
-            o.__dict__.update(g=g, desc=d, Ke=Ke, Ve=Ve, Vt=Vt, key_ws=key_ws, kn2=kn2, chained=i > 0)
+            krows = None if fused else kv[:, sg.n0:sg.n1, :C2 // 2]      # the float K rows of the segment
+            o.__dict__.update(g=g, desc=d, Ke=Ke, Ve=Ve, Vt=Vt, key_ws=key_ws, kn2=kn2, krows=krows, chained=i > 0)
             _run(sg.fwd, o)
             saved += [Ke, Ve, Kt, ka, kb, key_ws]
         ctx.geom = geom

@@ -62,7 +62,9 @@ extern "C" {
  *    bevr_attn_tap_fwd, bevr_attn_tap_bwd_q and bevr_attn_tap_bwd_k accept BEVR_PREC_BF16X3 where they returned
  *    BEVR_E_PRECISION (operand format: "TAP entry points in BEVR_PREC_BF16X3" below);
  *    bevr_attn_slab_rows_ws_bytes / _slab_rows_prep / bevr_attn_slab_bwd_q_rows (the slab query-side backward over a band
- *    of BEV rows of every column: BEV sides up to 448; the three bevr_attn_slab_* entry points keep their contract). */
+ *    of BEV rows of every column: BEV sides up to 448; the three bevr_attn_slab_* entry points keep their contract);
+ *    bevr_attn_gather_fwd_x3 (the gather forward in BEVR_PREC_BF16X3, over a row range; bevr_attn_gather_fwd and
+ *    bevr_attn_gather_fwd_rows keep returning BEVR_E_PRECISION for that mode). */
 #define BEVR_ABI_VERSION 6
 
 enum {
@@ -391,6 +393,24 @@ int bevr_attn_gather_fwd(const bevr_attn_desc* d, const void* Q, const void* K, 
 int bevr_attn_gather_fwd_rows(const bevr_attn_desc* d, const void* Q, const void* K, const void* V,
                               const void* key_ws, const void* table_pk, const float* mref, float* O, float* LSE,
                               int* flags, int row0, int n_rows, void* stream);
+/* The gather forward in BEVR_PREC_BF16X3 (csrc/attn_gather_fwd_x3.hip: every product three bf16 MFMAs on hi + lo parts,
+ * f32 tolerance), over the BEV rows [row0, row0 + n_rows) of every column; a whole column of S <= 224 rows is the range
+ * (0, S).  Outputs, mref, flags, the padding rows (LSE floor mref - 36) and the row-range contract as
+ * bevr_attn_gather_fwd_rows in bf16; the band limit is 224 rows.  Checked in this order: the descriptor, NULL pointers,
+ * 16-byte alignment of Q / K / V / key_ws / O, the precision (any but BEVR_PREC_BF16X3: BEVR_E_PRECISION), the row range
+ * (row0 >= 0, row0 % 16 == 0, 1 <= n_rows <= 224, row0 + n_rows <= S, else BEVR_E_SHAPE).  Operands:
+ *   Q [n_prob / q_div][heads][Mp][32], K, V [n_prob][heads][Np][32]: float CONTAINERS in the split ROW format of this
+ *            mode's other entry points (bevr_pack_kv with BEVR_PREC_BF16X3 writes K and V): a row is 128 bytes, per
+ *            16-element half  hi(e0..7) | hi(e8..15) | lo(e0..7) | lo(e8..15)  bf16, hi = bf16(x), lo = bf16(x - hi).
+ *            V rows are not transposed.
+ *   table_pk2 [2][heads][Wp][Hp] dwords: plane 0 the bf16 pairs (hi(T2[y][x]), hi(T2[y + 1][x])) of the f32 pair table
+ *            table_pair, plane 1 the pairs of the lo parts, lo = bf16(T2 - hi(T2)), both round-to-nearest
+ *   key_ws, mref (headroom 64), O, LSE, flags: as bevr_attn_gather_fwd in bf16 (flags zeroed by the caller before EVERY
+ *            call); the key-side bilinear weights are computed in f32 and split like every other operand.
+ * Uses 152 KB of dynamic LDS (one workgroup per CU). */
+int bevr_attn_gather_fwd_x3(const bevr_attn_desc* d, const void* Q, const void* K, const void* V,
+                            const void* key_ws, const void* table_pk2, const float* mref, float* O, float* LSE,
+                            int* flags, int row0, int n_rows, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * SLAB entry points (csrc/attn_slab_bwd_q.hip): bevr_attn_bwd_q -- dQ and the rpe-table gradient of a key segment, same

@@ -3,8 +3,10 @@ SpatialCrossAttn (S = 200, 6 views, D = 5, 64 x 176 features, B samples), the pi
 (BEVR_TAP_X3=1, ops.attention_core(tap_pix=...)) against the earlier routing (BEVR_TAP_X3=0: every key sampled, projected
 and sent through the region / cell kernels).  The two routes alternate in ONE process (the switch is read per call), HIP
 events around each step, one warm-up step per route; medians with min and max.
+--gather: the A/B of the split-mode gather forward instead -- both routes with BEVR_TAP_X3=1, the scattered keys' forward
+on bevr_attn_gather_fwd_x3 (BEVR_GATHER_X3=1) against the region forward (BEVR_GATHER_X3=0, the parent's routing).
 
-    B=8 ITERS=5 python tools/ab_sca_x3.py [out.json]"""
+    B=8 ITERS=5 python tools/ab_sca_x3.py [--gather] [out.json]"""
 import json
 import math
 import os
@@ -55,11 +57,17 @@ def main():
     q = torch.randn(B, C, S, S, generator=gen).to(DEV).requires_grad_(True)
     x = torch.randn(B * V, C, Hi, Wi, generator=gen).to(DEV).requires_grad_(True)
     cot = torch.randn(B, C, S, S, generator=gen).to(DEV)
-    times = {"tap_x3": [], "parent_route": []}
+    argv = [a for a in sys.argv[1:] if a != "--gather"]
+    if "--gather" in sys.argv[1:]:
+        new, routes = "gather_x3", (("gather_x3", {"BEVR_TAP_X3": "1", "BEVR_GATHER_X3": "1"}),
+                                    ("parent_route", {"BEVR_TAP_X3": "1", "BEVR_GATHER_X3": "0"}))
+    else:
+        new, routes = "tap_x3", (("tap_x3", {"BEVR_TAP_X3": "1"}), ("parent_route", {"BEVR_TAP_X3": "0"}))
+    times = {new: [], "parent_route": []}
     kernels = {}
 
     def step(tag, sw, record):
-        os.environ["BEVR_TAP_X3"] = sw
+        os.environ.update(sw)
         for t in list(sca.parameters()) + [q, x]:
             t.grad = None
         if record:
@@ -75,22 +83,22 @@ def main():
         return e0.elapsed_time(e1)
 
     for it in range(iters + 1):
-        for tag, sw in (("tap_x3", "1"), ("parent_route", "0")):
+        for tag, sw in routes:
             ms = step(tag, sw, False)
             if it > 0:
                 times[tag].append(ms)
-    for tag, sw in (("tap_x3", "1"), ("parent_route", "0")):       # one more step of each with per-kernel events
+    for tag, sw in routes:       # one more step of each with per-kernel events
         step(tag, sw, True)
     res = {"what": "SCA block forward + backward, bf16x3, S=200, 6 views, B=%d; routes alternating in one process" % B,
-           "iters": iters}
+           "routes": {tag: sw for tag, sw in routes}, "iters": iters}
     for tag, v in times.items():
         res[tag] = {"median_ms": round(statistics.median(v), 1), "min_ms": round(min(v), 1), "max_ms": round(max(v), 1),
                     "all_ms": [round(t, 1) for t in v]}
-    res["ratio_new_over_parent"] = round(res["tap_x3"]["median_ms"] / res["parent_route"]["median_ms"], 3)
+    res["ratio_new_over_parent"] = round(res[new]["median_ms"] / res["parent_route"]["median_ms"], 3)
     res["kernels_ms_one_step"] = kernels
     print(json.dumps(res, indent=1))
-    if len(sys.argv) > 1:
-        with open(sys.argv[1], "w") as f:
+    if argv:
+        with open(argv[0], "w") as f:
             json.dump(res, f, indent=1)
 
 
