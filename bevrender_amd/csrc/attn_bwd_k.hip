@@ -16,8 +16,12 @@
 //    That slab is kept in LDS as a ring of table columns (f32, one value per entry): moving to column j + 1
 //    shifts the range right by rx, so only ~rx new table columns are fetched per BEV column.  Taps are then
 //    LDS reads at immediate offsets from two per-lane bases.
-//  * attn_bwd_k_gather_kernel: the general path (4 waves x 64 keys, taps gathered from L2) for blocks whose
+//  * attn_bwd_k_gather_kernel: the general path (4 waves x 3 x 32 keys, taps gathered from L2) for blocks whose
 //    slab does not fit the ring (keys of the block far apart in table space).
+//  * attn_bwd_k_gather_list_kernel (the _ws entry point): the same sweep, dispatched from a device work list.  The
+//    window kernel appends every block it hands over; a fixed grid of workgroups then takes (listed block, range of
+//    query tiles) items, so no workgroup is launched to find out that it has nothing to do and the few misfit blocks
+//    are spread over the whole device.
 #include "attn_kstage.h"
 
 #include "bevr_prof.h"
@@ -27,6 +31,8 @@ BEVR_PROF_DEFINE(bwd_k, 16)   // window kernel, waves 0 and 11, 8 slots each: ph
 namespace {
 
 constexpr int KEYS_WG = 384;    // keys per workgroup, both kernels: the unit of ownership
+// work list of the blocks the window kernel hands over: int [0] = count, [LIST_HEAD + i] = ph * n_kb + kblk
+constexpr int LIST_HEAD = 4;
 
 // bounding box of a key block in table coordinates (padded keys excluded)
 struct KBox { int amin, amax; float bmin, bmax; };
@@ -97,7 +103,8 @@ __global__ __launch_bounds__(TW, 3) void attn_bwd_k_win_kernel(
     const char* __restrict__ V, const float* __restrict__ key_a, const float* __restrict__ key_b,
     const char* __restrict__ table_pair, const char* __restrict__ dO, const char* __restrict__ dOt,
     const float* __restrict__ LSE, const float* __restrict__ delta, const float* __restrict__ grad_scale,
-    float* __restrict__ dK, float* __restrict__ dV, float* __restrict__ dkey_a, float* __restrict__ dkey_b BEVR_DROP_PARAMS) {
+    float* __restrict__ dK, float* __restrict__ dV, float* __restrict__ dkey_a, float* __restrict__ dkey_b,
+    int* __restrict__ slow_list BEVR_DROP_PARAMS) {
   // NT 32-query tiles are staged and processed per barrier.  With one tile per barrier the three waves of a SIMD
   // ran in lockstep -- MFMAs together, then the VALU-bound bias / exp / gradient loop together, then the barrier --
   // and each pipe idled while the other worked; with two, the waves drift apart inside an iteration and one wave's
@@ -170,6 +177,8 @@ __global__ __launch_bounds__(TW, 3) void attn_bwd_k_win_kernel(
         *reinterpret_cast<f32x4*>(vr + 8 * g4 + 4 * hi) = z;
       }
     }
+    // the work list of attn_bwd_k_gather_list_kernel (null: the full-grid gather kernel decides for itself)
+    if (slow_list && tid == 0) slow_list[LIST_HEAD + atomicAdd(slow_list, 1)] = ph * n_kb + kblk;
     return;
   }
   if (box.amax < box.amin) {             // only padded keys: their gradients are zero
@@ -462,28 +471,30 @@ __global__ __launch_bounds__(TW, 3) void attn_bwd_k_win_kernel(
 constexpr int TG = 256;   // 4 waves x 3 x 32 keys
 constexpr int KW = 3;
 constexpr int GSPLIT = 4;  // workgroups per key block: the few blocks on this path would otherwise run ~6 ms each, alone
+// List dispatch: the shortest range of query tiles an item may have.  An item loads the block's K / V fragments (48 KB
+// in the 16-bit modes) and ends with 384 x 66 float atomics (101 KB added), against 8 KB of query rows and 12 288
+// gathered pairs per tile.  A tile takes a workgroup ~4.5 us (350 tiles in 1.4 to 2.2 ms, measured on the full-grid
+// launch), so with one workgroup on each of 256 compute units items of 32 tiles add 256 x 101 KB per 144 us = 0.18 TB/s,
+// a seventh of the device's float-atomic rate, and the fixed part stays under a tenth of an item's time.
+constexpr int GATHER_MIN_TILES = 32;
+constexpr int GATHER_ITEM_TILES = 4;     // an item's fixed part (fragment loads, atomic epilogue) priced in tiles
 
-template <int PREC>
-__global__ __launch_bounds__(TG) void attn_bwd_k_gather_kernel(
-    bevr_attn_desc d, const char* __restrict__ Q, const char* __restrict__ Qt, const char* __restrict__ K,
+// The gather sweep of one share of a misfit block: the KEYS_WG keys of (ph, kblk) against query tiles [it_first, it_end),
+// the partial dK / dV / d(a, b) ADDED to rows the window kernel cleared.  FULL_GRID: the caller is launched for every
+// block and the fit decision is recomputed here (red: TG / 64 KBox slots in LDS); a block that fits leaves before any
+// operand is loaded.  Otherwise the block comes off the window kernel's list, which is the decision.
+template <int PREC, bool FULL_GRID>
+__device__ __forceinline__ void gather_sweep(
+    const bevr_attn_desc& d, const char* __restrict__ Q, const char* __restrict__ Qt, const char* __restrict__ K,
     const char* __restrict__ V, const float* __restrict__ key_a, const float* __restrict__ key_b,
     const char* __restrict__ table_pair, const char* __restrict__ dO, const char* __restrict__ dOt,
     const float* __restrict__ LSE, const float* __restrict__ delta, const float* __restrict__ grad_scale,
-    float* __restrict__ dK, float* __restrict__ dV, float* __restrict__ dkey_a, float* __restrict__ dkey_b BEVR_DROP_PARAMS) {
+    float* __restrict__ dK, float* __restrict__ dV, float* __restrict__ dkey_a, float* __restrict__ dkey_b,
+    char* smem, KBox* red, int ph, int kblk, int it_first, int it_end BEVR_DROP_PARAMS) {
   typedef LdsK<PREC> L;
   const float kp16 = PREC == BEVR_PREC_F16 ? grad_scale[2] : 0.f, c2_16 = PREC == BEVR_PREC_F16 ? grad_scale[3] : 1.f;
   const float ds_inv = PREC == BEVR_PREC_F16 ? grad_scale[4] : 1.f, p_inv = PREC == BEVR_PREC_F16 ? grad_scale[5] : 1.f;
   constexpr int EB = L::EB;
-  __shared__ __attribute__((aligned(16))) char smem[2 * L::BUF];
-  __shared__ __attribute__((aligned(16))) KBox red[4];
-
-  const int n_kb = (d.Np + KEYS_WG - 1) / KEYS_WG;
-  const int n_ph = d.n_prob * d.heads;
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-  const int ph = (slot / (n_kb * GSPLIT)) * 8 + xcd;
-  if (ph >= n_ph) return;
-  const int kblk = (slot % (n_kb * GSPLIT)) / GSPLIT;
-  const int split = slot % GSPLIT;   // this workgroup's share of the query sweep
   const int prob = ph / d.heads, hd = ph % d.heads;
   const int grp = hd / (d.heads / d.groups);
   const int qb = prob / d.q_div;
@@ -512,8 +523,7 @@ __global__ __launch_bounds__(TG) void attn_bwd_k_gather_kernel(
     key_idx[w] = key;
     kc[w] = make_keyc(ka[key], kb[key], d);
   }
-  KBox box;
-  {
+  if constexpr (FULL_GRID) {
     // the unit's box decides the owner: the same reduction over the same keys as the window kernel
     int a_lo = 0x7fffffff, a_hi = (int)0x80000000;
     float b_lo = 3.0e38f, b_hi = -3.0e38f;
@@ -527,9 +537,9 @@ __global__ __launch_bounds__(TG) void attn_bwd_k_gather_kernel(
         b_lo = fminf(b_lo, bc); b_hi = fmaxf(b_hi, bc);
       }
     }
-    box = wg_key_box(a_lo, a_hi, b_lo, b_hi, red, TG / 64, wave, lane);
+    const KBox box = wg_key_box(a_lo, a_hi, b_lo, b_hi, red, TG / 64, wave, lane);
+    if (make_slab(box, d, L::WCAP, ceilf(rx)).fits) return;   // the window kernel owns this block (uniform exit)
   }
-  if (make_slab(box, d, L::WCAP, ceilf(rx)).fits) return;   // the window kernel owns this block (uniform exit)
 
   Frag<PREC> kf[KW], vf[KW];
 #pragma unroll
@@ -551,9 +561,7 @@ __global__ __launch_bounds__(TG) void attn_bwd_k_gather_kernel(
   qs.init(tid, Q + ((size_t)(qb * d.heads + hd) * Mp) * 32 * EB, dO + ((size_t)ph * Mp) * 32 * EB,
           Qt + ((size_t)(qb * d.heads + hd) * 32) * Mp * EB, dOt + ((size_t)ph * 32) * Mp * EB,
           LSE + (size_t)ph * Mp, delta + (size_t)ph * Mp, Mp, kp16);
-  const int n_all = d.S * n_rb;
-  const int chunk = (n_all + GSPLIT - 1) / GSPLIT;
-  const int it_first = split * chunk, n_it = min(n_all, it_first + chunk);
+  const int n_it = it_end;
   if (it_first >= n_it) return;   // uniform
   qs.load(tid, (size_t)(it_first / n_rb) * d.Sp + (it_first % n_rb) * 32);
   qs.store(tid, smem);
@@ -661,39 +669,120 @@ __global__ __launch_bounds__(TG) void attn_bwd_k_gather_kernel(
   }
 }
 
+// one workgroup per (block, quarter of the query sweep) of the whole grid: each finds out for itself whether the block is its own
+template <int PREC>
+__global__ __launch_bounds__(TG) void attn_bwd_k_gather_kernel(
+    bevr_attn_desc d, const char* __restrict__ Q, const char* __restrict__ Qt, const char* __restrict__ K,
+    const char* __restrict__ V, const float* __restrict__ key_a, const float* __restrict__ key_b,
+    const char* __restrict__ table_pair, const char* __restrict__ dO, const char* __restrict__ dOt,
+    const float* __restrict__ LSE, const float* __restrict__ delta, const float* __restrict__ grad_scale,
+    float* __restrict__ dK, float* __restrict__ dV, float* __restrict__ dkey_a, float* __restrict__ dkey_b BEVR_DROP_PARAMS) {
+  __shared__ __attribute__((aligned(16))) char smem[2 * LdsK<PREC>::BUF];
+  __shared__ __attribute__((aligned(16))) KBox red[TG / 64];
+  const int n_kb = (d.Np + KEYS_WG - 1) / KEYS_WG;
+  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+  const int ph = (slot / (n_kb * GSPLIT)) * 8 + xcd;
+  if (ph >= d.n_prob * d.heads) return;
+  const int kblk = (slot % (n_kb * GSPLIT)) / GSPLIT;
+  const int split = slot % GSPLIT;   // this workgroup's share of the query sweep
+  const int n_all = d.S * (d.Sp / 32);
+  const int chunk = (n_all + GSPLIT - 1) / GSPLIT;
+  gather_sweep<PREC, true>(d, Q, Qt, K, V, key_a, key_b, table_pair, dO, dOt, LSE, delta, grad_scale, dK, dV, dkey_a,
+                           dkey_b, smem, red, ph, kblk, split * chunk, min(n_all, (split + 1) * chunk) BEVR_DROP_ARGS);
+}
+
+#if !BEVR_DROP
+// A fixed grid of workgroups shares the listed blocks out as (block, range of query tiles) items, item i to workgroup
+// i mod gridDim.x.  The list is complete: the window launch precedes this one on the stream, and nothing here waits for
+// another workgroup.  An empty list costs each workgroup the one read of the count.
+template <int PREC>
+__global__ __launch_bounds__(TG) void attn_bwd_k_gather_list_kernel(
+    bevr_attn_desc d, const char* __restrict__ Q, const char* __restrict__ Qt, const char* __restrict__ K,
+    const char* __restrict__ V, const float* __restrict__ key_a, const float* __restrict__ key_b,
+    const char* __restrict__ table_pair, const char* __restrict__ dO, const char* __restrict__ dOt,
+    const float* __restrict__ LSE, const float* __restrict__ delta, const float* __restrict__ grad_scale,
+    float* __restrict__ dK, float* __restrict__ dV, float* __restrict__ dkey_a, float* __restrict__ dkey_b,
+    const int* __restrict__ slow_list) {
+  __shared__ __attribute__((aligned(16))) char smem[2 * LdsK<PREC>::BUF];
+  const int n_list = slow_list[0];
+  if (n_list <= 0) return;
+  const int n_kb = (d.Np + KEYS_WG - 1) / KEYS_WG;
+  const int n_all = d.S * (d.Sp / 32);
+  // Ranges per block, chosen from the list length.  Items cost the same (every tile is computed in full) and go to the
+  // workgroups in turn, so the launch lasts (rounds of items) x (an item's time): the split with the smallest such
+  // product wins, among those whose ranges are no shorter than GATHER_MIN_TILES.  Every workgroup finds the same one.
+  int chunk = n_all;
+  long long best = 0x7fffffffffffffffLL;
+  for (int r = 1; r <= max(1, n_all / GATHER_MIN_TILES); ++r) {
+    const int ch = (n_all + r - 1) / r, nr = (n_all + ch - 1) / ch;     // nr: no empty range
+    const long long rounds = ((long long)n_list * nr + gridDim.x - 1) / gridDim.x;
+    const long long cost = rounds * (ch + GATHER_ITEM_TILES);
+    if (cost < best) { best = cost; chunk = ch; }
+  }
+  const int n_rng = (n_all + chunk - 1) / chunk;
+  // consecutive items are different blocks: the workgroups running side by side add into different rows
+  for (int item = blockIdx.x; item < n_list * n_rng; item += gridDim.x) {
+    const int unit = slow_list[LIST_HEAD + item % n_list], rng = item / n_list;
+    gather_sweep<PREC, false>(d, Q, Qt, K, V, key_a, key_b, table_pair, dO, dOt, LSE, delta, grad_scale, dK, dV, dkey_a,
+                              dkey_b, smem, nullptr, unit / n_kb, unit % n_kb, rng * chunk, min(n_all, (rng + 1) * chunk));
+  }
+}
+
+// workgroups the device holds at once: compute units x the kernel's residency (asked once per kernel)
+template <typename Kern>
+int resident_workgroups(Kern kern, int threads) {
+  int dev = 0, cus = 0, per_cu = 0;
+  if (hipGetDevice(&dev) != hipSuccess ||
+      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, threads, 0) != hipSuccess)
+    return 0;
+  return cus * per_cu;
+}
+#endif
+
+// slow_list: null -- the full-grid gather launch; else the work list (cleared here, filled by the window launch) and the
+// list launch of at most max_wg workgroups (0: what the device holds)
 template <int PREC>
 int launch(const bevr_attn_desc& d, const void* Q, const void* Qt, const void* K, const void* V, const float* key_a,
            const float* key_b, const float* table_pair, const void* dO, const void* dOt, const float* LSE,
-           const float* delta, const float* gs, float* dK, float* dV, float* dka, float* dkb, hipStream_t st BEVR_DROP_PARAMS) {
+           const float* delta, const float* gs, float* dK, float* dV, float* dka, float* dkb, int* slow_list, int max_wg,
+           hipStream_t st BEVR_DROP_PARAMS) {
   const int n_kb = (d.Np + KEYS_WG - 1) / KEYS_WG;
   const int n_ph = d.n_prob * d.heads;
   const int grid = ((n_ph + 7) / 8) * 8 * n_kb;
+  int rc;
+  if (slow_list) {
+    // the list kernel counts items (listed block, range) in an int
+    if ((long long)n_ph * n_kb * (d.S * (d.Sp / 32) / GATHER_MIN_TILES + 1) > 0x7fffffffLL) return BEVR_E_SHAPE;
+    rc = (int)hipMemsetAsync(slow_list, 0, LIST_HEAD * sizeof(int), st);
+    if (rc) return rc;
+  }
   hipLaunchKernelGGL((attn_bwd_k_win_kernel<PREC>), dim3(grid), dim3(TW), 0, st, d, (const char*)Q, (const char*)Qt,
                      (const char*)K, (const char*)V, key_a, key_b, (const char*)table_pair, (const char*)dO,
-                     (const char*)dOt, LSE, delta, gs, dK, dV, dka, dkb BEVR_DROP_ARGS);
-  int rc = (int)hipGetLastError();
+                     (const char*)dOt, LSE, delta, gs, dK, dV, dka, dkb, slow_list BEVR_DROP_ARGS);
+  rc = (int)hipGetLastError();
   if (rc) return rc;
+#if !BEVR_DROP
+  if (slow_list) {
+    static const int resident = resident_workgroups(attn_bwd_k_gather_list_kernel<PREC>, TG);
+    if (resident <= 0) return (int)hipErrorInvalidDevice;
+    const int n_wg = max_wg > 0 && max_wg < resident ? max_wg : resident;
+    hipLaunchKernelGGL((attn_bwd_k_gather_list_kernel<PREC>), dim3(n_wg), dim3(TG), 0, st, d, (const char*)Q,
+                       (const char*)Qt, (const char*)K, (const char*)V, key_a, key_b, (const char*)table_pair,
+                       (const char*)dO, (const char*)dOt, LSE, delta, gs, dK, dV, dka, dkb, (const int*)slow_list);
+    return (int)hipGetLastError();
+  }
+#endif
   hipLaunchKernelGGL((attn_bwd_k_gather_kernel<PREC>), dim3(grid * GSPLIT), dim3(TG), 0, st, d, (const char*)Q,
                      (const char*)Qt, (const char*)K, (const char*)V, key_a, key_b, (const char*)table_pair,
                      (const char*)dO, (const char*)dOt, LSE, delta, gs, dK, dV, dka, dkb BEVR_DROP_ARGS);
   return (int)hipGetLastError();
 }
 
-}  // namespace
-
-#if BEVR_DROP
-extern "C" int bevr_attn_bwd_k_dropout(const bevr_attn_desc* d, const void* Q, const void* Qt, const void* K, const void* V,
-                                       const float* key_a, const float* key_b, const float* table_pair, const void* dO,
-                                       const void* dOt, const float* LSE, const float* delta, const float* grad_scale,
-                                       float* dK, float* dV, float* dkey_a, float* dkey_b, unsigned drop_thr,
-                                       unsigned drop_seed, void* stream) {
-  if (drop_thr >= 65536u) return BEVR_E_SHAPE;
-#else
-extern "C" int bevr_attn_bwd_k(const bevr_attn_desc* d, const void* Q, const void* Qt, const void* K, const void* V,
-                               const float* key_a, const float* key_b, const float* table_pair, const void* dO,
-                               const void* dOt, const float* LSE, const float* delta, const float* grad_scale,
-                               float* dK, float* dV, float* dkey_a, float* dkey_b, void* stream) {
-#endif
+int run(const bevr_attn_desc* d, const void* Q, const void* Qt, const void* K, const void* V, const float* key_a,
+        const float* key_b, const float* table_pair, const void* dO, const void* dOt, const float* LSE, const float* delta,
+        const float* grad_scale, float* dK, float* dV, float* dkey_a, float* dkey_b, int* slow_list, int max_wg,
+        void* stream BEVR_DROP_PARAMS) {
   int rc = bevr_check_desc(d);
   if (rc) return rc;
   if (!Q || !Qt || !K || !V || !key_a || !key_b || !table_pair || !dO || !dOt || !LSE || !delta || !dK || !dV ||
@@ -705,13 +794,54 @@ extern "C" int bevr_attn_bwd_k(const bevr_attn_desc* d, const void* Q, const voi
   hipStream_t st = (hipStream_t)stream;
   if (d->precision == BEVR_PREC_BF16)
     return launch<BEVR_PREC_BF16>(*d, Q, Qt, K, V, key_a, key_b, table_pair, dO, dOt, LSE, delta, grad_scale, dK, dV,
-                                  dkey_a, dkey_b, st BEVR_DROP_ARGS);
+                                  dkey_a, dkey_b, slow_list, max_wg, st BEVR_DROP_ARGS);
   if (d->precision == BEVR_PREC_F16)
     return launch<BEVR_PREC_F16>(*d, Q, Qt, K, V, key_a, key_b, table_pair, dO, dOt, LSE, delta, grad_scale, dK, dV,
-                                 dkey_a, dkey_b, st BEVR_DROP_ARGS);
+                                 dkey_a, dkey_b, slow_list, max_wg, st BEVR_DROP_ARGS);
   if (d->precision == BEVR_PREC_BF16X3)
     return launch<BEVR_PREC_BF16X3>(*d, Q, Qt, K, V, key_a, key_b, table_pair, dO, dOt, LSE, delta, grad_scale, dK, dV,
-                               dkey_a, dkey_b, st BEVR_DROP_ARGS);
+                                    dkey_a, dkey_b, slow_list, max_wg, st BEVR_DROP_ARGS);
   return launch<BEVR_PREC_F32>(*d, Q, Qt, K, V, key_a, key_b, table_pair, dO, dOt, LSE, delta, grad_scale, dK, dV,
-                               dkey_a, dkey_b, st BEVR_DROP_ARGS);
+                               dkey_a, dkey_b, slow_list, max_wg, st BEVR_DROP_ARGS);
 }
+
+}  // namespace
+
+#if BEVR_DROP
+extern "C" int bevr_attn_bwd_k_dropout(const bevr_attn_desc* d, const void* Q, const void* Qt, const void* K, const void* V,
+                                       const float* key_a, const float* key_b, const float* table_pair, const void* dO,
+                                       const void* dOt, const float* LSE, const float* delta, const float* grad_scale,
+                                       float* dK, float* dV, float* dkey_a, float* dkey_b, unsigned drop_thr,
+                                       unsigned drop_seed, void* stream) {
+  if (drop_thr >= 65536u) return BEVR_E_SHAPE;
+  return run(d, Q, Qt, K, V, key_a, key_b, table_pair, dO, dOt, LSE, delta, grad_scale, dK, dV, dkey_a, dkey_b, nullptr, 0,
+             stream, drop_thr, drop_seed);
+}
+#else
+extern "C" int bevr_attn_bwd_k(const bevr_attn_desc* d, const void* Q, const void* Qt, const void* K, const void* V,
+                               const float* key_a, const float* key_b, const float* table_pair, const void* dO,
+                               const void* dOt, const float* LSE, const float* delta, const float* grad_scale,
+                               float* dK, float* dV, float* dkey_a, float* dkey_b, void* stream) {
+  return run(d, Q, Qt, K, V, key_a, key_b, table_pair, dO, dOt, LSE, delta, grad_scale, dK, dV, dkey_a, dkey_b, nullptr, 0,
+             stream);
+}
+
+extern "C" size_t bevr_attn_bwd_k_ws_bytes(const bevr_attn_desc* d) {
+  if (bevr_check_desc(d)) return 0;
+  const size_t n_kb = ((size_t)d->Np + KEYS_WG - 1) / KEYS_WG;
+  return (LIST_HEAD + (size_t)d->n_prob * d->heads * n_kb) * sizeof(int);
+}
+
+extern "C" int bevr_attn_bwd_k_ws(const bevr_attn_desc* d, const void* Q, const void* Qt, const void* K, const void* V,
+                                  const float* key_a, const float* key_b, const float* table_pair, const void* dO,
+                                  const void* dOt, const float* LSE, const float* delta, const float* grad_scale,
+                                  float* dK, float* dV, float* dkey_a, float* dkey_b, void* ws, int max_workgroups,
+                                  void* stream) {
+  if (!ws) return BEVR_E_NULL;
+  if (!bevr_aligned16(ws)) return BEVR_E_ALIGN;
+  if (max_workgroups < 0) return BEVR_E_SHAPE;
+  return run(d, Q, Qt, K, V, key_a, key_b, table_pair, dO, dOt, LSE, delta, grad_scale, dK, dV, dkey_a, dkey_b, (int*)ws,
+             max_workgroups, stream);
+}
+#endif
+

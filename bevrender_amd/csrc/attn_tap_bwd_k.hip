@@ -50,24 +50,40 @@ __device__ __forceinline__ bool tile_fits(const StepBox& sb, float jrx, int a0w,
   return sb.amax >= sb.amin && da >= 0 && da <= NRX && box_fits(sb, jrx) && dx >= 0 && dx <= NCW - CELL_C;
 }
 
-// SLOW = false: the (tile, column) pairs that take the matrix path; SLOW = true: the others, by the per-pair gather (a
-// workgroup without any leaves at once: every workgroup of a cell-sorted segment).  Two launches: with both bodies in one
-// loop the matrix path reloaded loop invariants from scratch on every slab.
-template <int PREC, bool SLOW>
-__global__ __launch_bounds__(64 * (NKW + 1), tap_bwd_k_waves(PREC)) void attn_tap_bwd_k_kernel(
-    bevr_attn_desc d, const char* __restrict__ G, const char* __restrict__ H, const char* __restrict__ tap_ws,
+// The slow pairs have two dispatches.  MODE_SLOW launches the main grid again: every workgroup tests its tiles against
+// every column and leaves if all fit; one that stays keeps the main launch's shape (producer, a barrier per step) through
+// all S columns.  MODE_LIST takes them from a device work list: the main launch appends each tile that has an unfit
+// column, and a fixed grid of waves runs (listed tile, range of BEV columns) items.  An item belongs to a WAVE, not to a
+// workgroup: the tiles of a workgroup are unfit in different columns, so a shared producer would stage the union of
+// their columns and every wave would wait at the barriers of columns it skips; a wave that stages the 2 KB of G | H rows
+// of its own slab into its own LDS buffer stages exactly what it computes and meets no barrier at all.
+constexpr int MODE_FIT = 0, MODE_SLOW = 1, MODE_LIST = 2;
+constexpr int LIST_HEAD = 4;           // work list: int [0] = count, [LIST_HEAD + i] = ph * (Np / 32) + tile
+constexpr int LIST_WAVES = 4;          // waves per workgroup of the list launch (independent of each other)
+// The shortest range of BEV columns of an item.  An item reads its 32 tap records, forms their weights and ends with 128
+// float atomics, a few microseconds; an unfit column is nslab slabs of per-pair gathers at ~3.3 us each (measured on the
+// full-grid launch: a tile unfit in all 200 columns of 7 slabs held its workgroup for 4.7 ms), 23 us at S = 200.  Eight
+// columns keep the fixed part of a mostly unfit tile's item under 5 %.
+constexpr int LIST_MIN_COLS = 8;
+constexpr int LIST_ITEMS_PER_WAVE = 4; // items aimed at per resident wave: their cost varies with the unfit columns
+
+// MODE_FIT: the (tile, column) pairs that take the matrix path; MODE_SLOW / MODE_LIST: the others, by the per-pair gather
+// (MODE_SLOW: a workgroup without any leaves at once: every workgroup of a cell-sorted segment).  Separate launches: with
+// both bodies in one loop the matrix path reloaded loop invariants from scratch on every slab.
+// (ph, wg): the problem-head and the workgroup of NKW tiles of the main launch's grid -- the tile's window origin follows
+// from it in every mode; tslot: the tile's place in it (MODE_FIT / MODE_SLOW: the wave); columns [j_first, j_end).
+template <int PREC, int MODE>
+__device__ __forceinline__ void tap_bwd_k_body(
+    const bevr_attn_desc& d, const char* __restrict__ G, const char* __restrict__ H, const char* __restrict__ tap_ws,
     const float* __restrict__ table_t, float* __restrict__ dkey_a, float* __restrict__ dkey_b,
-    float* __restrict__ dkey_y, float* __restrict__ dkey_x, int n_wg_ph TAP_DROP_PARAMS) {
+    float* __restrict__ dkey_y, float* __restrict__ dkey_x, char* smem, int ph, int wg, int tslot, int j_first, int j_end,
+    int* __restrict__ slow_list TAP_DROP_PARAMS) {
   typedef LdsKp<PREC> L;
+  constexpr bool SLOW = MODE != MODE_FIT;
   constexpr bool X3 = tap_split(PREC);
   constexpr int NP = tap_np<PREC>;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
 
   const int n_ph = d.n_prob * d.heads;
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-  const int ph = (slot / n_wg_ph) * 8 + xcd;
-  if (ph >= n_ph) return;
-  const int wg = slot % n_wg_ph;
   const int prob = ph / d.heads, hd = ph % d.heads;
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
@@ -83,7 +99,8 @@ __global__ __launch_bounds__(64 * (NKW + 1), tap_bwd_k_waves(PREC)) void attn_ta
   const int win_bytes = 4 * NCW * NRWD * 4;                   // [kind hi / lo][row parity][NCW columns][NRWD dwords]
   char* win_base = smem + 2 * L::BUF;
   // the key waves' records live in LDS between their uses (column start, column end): 8 registers less in the slab loop
-  TapRec* stash = reinterpret_cast<TapRec*>(win_base + 3 * win_bytes) + wave * 32;
+  // (MODE_LIST: no windows; LIST_WAVES pairs of slab buffers, one pair per wave, then the records)
+  TapRec* stash = reinterpret_cast<TapRec*>(MODE == MODE_LIST ? smem + LIST_WAVES * 2 * L::SLAB : win_base + 3 * win_bytes) + wave * 32;
 
   // the workgroup's window origin: the lowest table row / leftmost coordinate of its tiles (rows: for every column)
   int a0w = 0x7fffffff;
@@ -99,7 +116,7 @@ __global__ __launch_bounds__(64 * (NKW + 1), tap_bwd_k_waves(PREC)) void attn_ta
     }
   }
   if (a0w == 0x7fffffff) { a0w = 0; bminw = 0.f; }
-  if constexpr (SLOW) {
+  if constexpr (MODE == MODE_SLOW) {
     bool unfit = false;     // the same for every wave of the workgroup: all of them leave, or none
     for (int t = 0; t < NKW; ++t) {
       const int tile = wg * NKW + t;
@@ -111,7 +128,7 @@ __global__ __launch_bounds__(64 * (NKW + 1), tap_bwd_k_waves(PREC)) void attn_ta
     if (!__any(unfit)) return;
   }
 
-  if (wave == NKW) {
+  if (MODE != MODE_LIST && wave == NKW) {
     // ---- producer: the G and H rows of slab (j, i0) -> LDS one step ahead of the key waves, and the table window of the
     // NEXT column in slices, one per slab of the current one.  THREE windows: while the slices of column j + 1 are written
     // the key waves may still be one step behind, in the last slab of column j - 1 ---------------------------------------
@@ -223,7 +240,7 @@ __global__ __launch_bounds__(64 * (NKW + 1), tap_bwd_k_waves(PREC)) void attn_ta
   }
 
   // ---- key waves ---------------------------------------------------------------------------------------------------
-  const int tile = wg * NKW + wave;
+  const int tile = wg * NKW + tslot;
   const bool have_tile = tile < n_tiles;            // uniform; a wave without a tile only keeps the barriers
   const TapRec* recs = reinterpret_cast<const TapRec*>(tap_ws) + (size_t)prob * d.Np;
   const int tl = have_tile ? tile : 0;
@@ -392,7 +409,8 @@ __global__ __launch_bounds__(64 * (NKW + 1), tap_bwd_k_waves(PREC)) void attn_ta
     }
   };
 
-  for (int j = 0; j < d.S; ++j) {
+  bool any_unfit = false;     // the tile has an unfit column in the range: left to the slow pass / computed here (uniform)
+  for (int j = j_first; j < j_end; ++j) {
     jrx = (float)j * rx;
 #if BEVR_DROP
     hcol = (uint32_t)(j * d.Sp + 4 * g) * 0x85EBCA77u;
@@ -401,6 +419,34 @@ __global__ __launch_bounds__(64 * (NKW + 1), tap_bwd_k_waves(PREC)) void attn_ta
     const int dx = x0 - (int)floorf(jrx + bminw);
     const bool fit = tile_fits(sb, jrx, a0w, bminw);    // uniform over the wave
     const bool mine = have_tile && sb.amax >= sb.amin && fit != SLOW;   // this launch's share of the (tile, column) pairs
+    if constexpr (MODE == MODE_FIT) any_unfit = any_unfit || (have_tile && sb.amax >= sb.amin && !fit);
+    if constexpr (MODE == MODE_LIST) {
+      // a column that fits costs this one test; an unfit one: its slabs' G | H rows through the wave's own pair of
+      // buffers, the next slab's rows in flight under this one's gathers.  LDS accesses of one wave complete in order:
+      // the fences only keep the compiler from moving the reads of a buffer over the stores that fill it
+      if (!mine) continue;
+      any_unfit = true;
+#pragma unroll
+      for (int kb = 0; kb < 2; ++kb)
+        if (g >= 2) bk[kb] = TapOp<NP>{};
+      char* wbuf = smem + wave * 2 * L::SLAB;
+      const char* Gs = G + ((size_t)ph * Mp + (size_t)j * d.Sp) * 32 + lane * 16;
+      const char* Hs = H + ((size_t)ph * Mp + (size_t)j * d.Sp) * 32 + lane * 16;
+      u32x4 gv = gload16(Gs), hv = gload16(Hs);
+      for (int s = 0; s < nslab; ++s) {
+        char* bb = wbuf + (s & 1) * L::SLAB;
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        *reinterpret_cast<u32x4*>(bb + L::OFF_G + lane * 16) = gv;
+        *reinterpret_cast<u32x4*>(bb + L::OFF_H + lane * 16) = hv;
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        if (s + 1 < nslab) {
+          gv = gload16(Gs + (size_t)(s + 1) * 1024);
+          hv = gload16(Hs + (size_t)(s + 1) * 1024);
+        }
+        slab(std::false_type{}, bb, 32 * s);
+      }
+      continue;
+    }
     // this key's coordinates inside the chunk for this column
     auto chunk_coords = [&](int kb, float& tcol, float& trow) {
       const TapRec rk = stash[16 * kb + li];
@@ -456,9 +502,14 @@ __global__ __launch_bounds__(64 * (NKW + 1), tap_bwd_k_waves(PREC)) void attn_ta
       }
     }
   }
-  __syncthreads();   // the producer's closing barrier
+  if constexpr (MODE != MODE_LIST) __syncthreads();   // the producer's closing barrier
 
   if (!have_tile) return;
+  if (MODE == MODE_LIST && !any_unfit) return;   // every column of the range fits: nothing to add
+  if constexpr (MODE == MODE_FIT) {
+    // the work list of the list launch (null: the full-grid slow launch finds its tiles itself)
+    if (slow_list && any_unfit && lane == 0) slow_list[LIST_HEAD + atomicAdd(slow_list, 1)] = ph * n_tiles + tile;
+  }
   // ---- per key: tap-weight gradients -> sampling-position gradient; everything summed over the four lane groups ----
 #pragma unroll
   for (int kb = 0; kb < 2; ++kb) {
@@ -490,9 +541,72 @@ __global__ __launch_bounds__(64 * (NKW + 1), tap_bwd_k_waves(PREC)) void attn_ta
   }
 }
 
+// the main grid: one workgroup per NKW tiles of a problem-head
+template <int PREC, bool SLOW>
+__global__ __launch_bounds__(64 * (NKW + 1), tap_bwd_k_waves(PREC)) void attn_tap_bwd_k_kernel(
+    bevr_attn_desc d, const char* __restrict__ G, const char* __restrict__ H, const char* __restrict__ tap_ws,
+    const float* __restrict__ table_t, float* __restrict__ dkey_a, float* __restrict__ dkey_b,
+    float* __restrict__ dkey_y, float* __restrict__ dkey_x, int n_wg_ph, int* __restrict__ slow_list TAP_DROP_PARAMS) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+  const int ph = (slot / n_wg_ph) * 8 + xcd;
+  if (ph >= d.n_prob * d.heads) return;
+  tap_bwd_k_body<PREC, SLOW ? MODE_SLOW : MODE_FIT>(d, G, H, tap_ws, table_t, dkey_a, dkey_b, dkey_y, dkey_x, smem, ph,
+                                                    slot % n_wg_ph, __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), 0,
+                                                    d.S, slow_list TAP_DROP_ARGS);
+}
+
+#if !BEVR_DROP && !BEVR_TAP_X3
+// The list launch: every wave claims (listed tile, range of BEV columns) items from the counter list[1] until they run
+// out -- the items' cost varies with the number of unfit columns, so they are claimed, not dealt.  The list is complete
+// (the main launch precedes this one on the stream); a claim never waits, and every wave reaches the exit.  An empty
+// list costs a wave the one read of the count.
+// Three waves per SIMD: 163 registers without scratch; at the main grid's four the staging registers spill (152 bytes a lane).
+template <int PREC>
+__global__ __launch_bounds__(64 * LIST_WAVES, 3) void attn_tap_bwd_k_list_kernel(
+    bevr_attn_desc d, const char* __restrict__ G, const char* __restrict__ H, const char* __restrict__ tap_ws,
+    const float* __restrict__ table_t, float* __restrict__ dkey_a, float* __restrict__ dkey_b,
+    float* __restrict__ dkey_y, float* __restrict__ dkey_x, int* __restrict__ list) {
+  static_assert(tap_np<PREC> == 1, "the waves stage one image per operand");
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int n_list = __builtin_amdgcn_readfirstlane(list[0]);
+  if (n_list <= 0) return;
+  const int n_tiles = d.Np / 32;
+  // ranges per tile from the list length: LIST_ITEMS_PER_WAVE items per wave of the grid, none shorter than LIST_MIN_COLS
+  const int want = (LIST_ITEMS_PER_WAVE * LIST_WAVES * (int)gridDim.x + n_list - 1) / n_list;
+  const int n_rng0 = max(1, min(want, d.S / LIST_MIN_COLS));
+  const int cols = (d.S + n_rng0 - 1) / n_rng0;
+  const int n_rng = (d.S + cols - 1) / cols;          // no empty range
+  const int n_item = n_list * n_rng;
+  for (;;) {
+    int item = 0;
+    if ((threadIdx.x & 63) == 0) item = atomicAdd(list + 1, 1);
+    item = __builtin_amdgcn_readfirstlane(item);
+    if (item >= n_item) return;
+    const int unit = list[LIST_HEAD + item % n_list], rng = item / n_list;
+    const int tile = unit % n_tiles;
+    tap_bwd_k_body<PREC, MODE_LIST>(d, G, H, tap_ws, table_t, dkey_a, dkey_b, dkey_y, dkey_x, smem, unit / n_tiles,
+                                    tile / NKW, tile % NKW, rng * cols, min(d.S, (rng + 1) * cols), nullptr);
+  }
+}
+
+// workgroups the device holds at once: compute units x the kernel's residency (asked once per kernel)
+template <typename Kern>
+int resident_workgroups(Kern kern, int threads, size_t lds) {
+  int dev = 0, cus = 0, per_cu = 0;
+  if (hipGetDevice(&dev) != hipSuccess ||
+      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, threads, lds) != hipSuccess)
+    return 0;
+  return cus * per_cu;
+}
+#endif
+
+// slow_list: null -- the slow pairs by the main grid launched again; else the work list (cleared here, filled by the
+// main launch) and the list launch of at most max_wg workgroups (0: what the device holds)
 template <int PREC>
 int launch(const bevr_attn_desc& d, const void* G, const void* H, const void* tap_ws, const float* table_t, float* dkey_a,
-           float* dkey_b, float* dkey_y, float* dkey_x, hipStream_t st TAP_DROP_PARAMS) {
+           float* dkey_b, float* dkey_y, float* dkey_x, int* slow_list, int max_wg, hipStream_t st TAP_DROP_PARAMS) {
   typedef LdsKp<PREC> L;
   const int n_ph = d.n_prob * d.heads;
   const int n_tiles = d.Np / 32;
@@ -501,12 +615,30 @@ int launch(const bevr_attn_desc& d, const void* G, const void* H, const void* ta
   if (lds > 160 * 1024) return BEVR_E_SHAPE;
   const long long grid = (long long)((n_ph + 7) / 8) * 8 * n_wg_ph;
   if (grid > 0x7fffffffLL) return BEVR_E_SHAPE;
+  int rc;
+  if (slow_list) {
+    // the list kernel counts items (listed tile, range) in an int
+    if ((long long)n_ph * n_tiles * (d.S / LIST_MIN_COLS + 1) > 0x7fffffffLL) return BEVR_E_SHAPE;
+    rc = (int)hipMemsetAsync(slow_list, 0, LIST_HEAD * sizeof(int), st);
+    if (rc) return rc;
+  }
   hipLaunchKernelGGL((attn_tap_bwd_k_kernel<PREC, false>), dim3((unsigned)grid), dim3(64 * (NKW + 1)), lds, st, d, (const char*)G,
-                     (const char*)H, (const char*)tap_ws, table_t, dkey_a, dkey_b, dkey_y, dkey_x, n_wg_ph TAP_DROP_ARGS);
-  const int rc = (int)hipGetLastError();
+                     (const char*)H, (const char*)tap_ws, table_t, dkey_a, dkey_b, dkey_y, dkey_x, n_wg_ph, slow_list TAP_DROP_ARGS);
+  rc = (int)hipGetLastError();
   if (rc) return rc;
+#if !BEVR_DROP && !BEVR_TAP_X3
+  if (slow_list) {
+    const size_t lds_list = LIST_WAVES * (2 * L::SLAB + 32 * sizeof(TapRec));
+    static const int resident = resident_workgroups(attn_tap_bwd_k_list_kernel<PREC>, 64 * LIST_WAVES, lds_list);
+    if (resident <= 0) return (int)hipErrorInvalidDevice;
+    const int n_wg = max_wg > 0 && max_wg < resident ? max_wg : resident;
+    hipLaunchKernelGGL((attn_tap_bwd_k_list_kernel<PREC>), dim3(n_wg), dim3(64 * LIST_WAVES), lds_list, st, d, (const char*)G,
+                       (const char*)H, (const char*)tap_ws, table_t, dkey_a, dkey_b, dkey_y, dkey_x, slow_list);
+    return (int)hipGetLastError();
+  }
+#endif
   hipLaunchKernelGGL((attn_tap_bwd_k_kernel<PREC, true>), dim3((unsigned)grid), dim3(64 * (NKW + 1)), lds, st, d, (const char*)G,
-                     (const char*)H, (const char*)tap_ws, table_t, dkey_a, dkey_b, dkey_y, dkey_x, n_wg_ph TAP_DROP_ARGS);
+                     (const char*)H, (const char*)tap_ws, table_t, dkey_a, dkey_b, dkey_y, dkey_x, n_wg_ph, (int*)nullptr TAP_DROP_ARGS);
   return (int)hipGetLastError();
 }
 
@@ -516,31 +648,59 @@ int launch(const bevr_attn_desc& d, const void* G, const void* H, const void* ta
 // the split-mode instantiations: this translation unit is attn_tap_bwd_k_x3.hip, entered from bevr_attn_tap_bwd_k
 int bevr_tap_bwd_k_x3(const bevr_attn_desc& d, const void* G, const void* H, const void* tap_ws, const float* table_t,
                       float* dkey_a, float* dkey_b, float* dkey_y, float* dkey_x, hipStream_t st) {
-  return launch<BEVR_PREC_BF16X3>(d, G, H, tap_ws, table_t, dkey_a, dkey_b, dkey_y, dkey_x, st);
+  return launch<BEVR_PREC_BF16X3>(d, G, H, tap_ws, table_t, dkey_a, dkey_b, dkey_y, dkey_x, nullptr, 0, st);
 }
 #else
-#if BEVR_DROP
-extern "C" int bevr_attn_tap_bwd_k_dropout(const bevr_attn_desc* d, const void* G, const void* H, const void* tap_ws,
-                                           const float* table_t, float* dkey_a, float* dkey_b, float* dkey_y,
-                                           float* dkey_x, unsigned key0, unsigned drop_thr, unsigned drop_seed,
-                                           void* stream) {
-  if (drop_thr >= 65536u) return BEVR_E_SHAPE;
-#else
-extern "C" int bevr_attn_tap_bwd_k(const bevr_attn_desc* d, const void* G, const void* H, const void* tap_ws,
-                                   const float* table_t, float* dkey_a, float* dkey_b, float* dkey_y, float* dkey_x,
-                                   void* stream) {
-#endif
+namespace {
+// slow_list: null for the full-grid slow launch (and always in the split mode, which has no list kernel)
+int run(const bevr_attn_desc* d, const void* G, const void* H, const void* tap_ws, const float* table_t, float* dkey_a,
+        float* dkey_b, float* dkey_y, float* dkey_x, int* slow_list, int max_wg, void* stream TAP_DROP_PARAMS) {
   int rc = bevr_check_desc(d);
   if (rc) return rc;
   if (!G || !H || !tap_ws || !table_t || !dkey_a || !dkey_b || !dkey_y || !dkey_x) return BEVR_E_NULL;
   if (d->groups != 1) return BEVR_E_SHAPE;
   if (!bevr_aligned16(G) || !bevr_aligned16(H) || !bevr_aligned16(tap_ws)) return BEVR_E_ALIGN;
   hipStream_t st = (hipStream_t)stream;
-  if (d->precision == BEVR_PREC_BF16) return launch<BEVR_PREC_BF16>(*d, G, H, tap_ws, table_t, dkey_a, dkey_b, dkey_y, dkey_x, st TAP_DROP_ARGS);
-  if (d->precision == BEVR_PREC_F16) return launch<BEVR_PREC_F16>(*d, G, H, tap_ws, table_t, dkey_a, dkey_b, dkey_y, dkey_x, st TAP_DROP_ARGS);
+  if (d->precision == BEVR_PREC_BF16)
+    return launch<BEVR_PREC_BF16>(*d, G, H, tap_ws, table_t, dkey_a, dkey_b, dkey_y, dkey_x, slow_list, max_wg, st TAP_DROP_ARGS);
+  if (d->precision == BEVR_PREC_F16)
+    return launch<BEVR_PREC_F16>(*d, G, H, tap_ws, table_t, dkey_a, dkey_b, dkey_y, dkey_x, slow_list, max_wg, st TAP_DROP_ARGS);
 #if !BEVR_DROP
-  if (d->precision == BEVR_PREC_BF16X3) return bevr_tap_bwd_k_x3(*d, G, H, tap_ws, table_t, dkey_a, dkey_b, dkey_y, dkey_x, st);
+  if (d->precision == BEVR_PREC_BF16X3 && !slow_list)
+    return bevr_tap_bwd_k_x3(*d, G, H, tap_ws, table_t, dkey_a, dkey_b, dkey_y, dkey_x, st);
 #endif
   return BEVR_E_PRECISION;
 }
+}  // namespace
+
+#if BEVR_DROP
+extern "C" int bevr_attn_tap_bwd_k_dropout(const bevr_attn_desc* d, const void* G, const void* H, const void* tap_ws,
+                                           const float* table_t, float* dkey_a, float* dkey_b, float* dkey_y,
+                                           float* dkey_x, unsigned key0, unsigned drop_thr, unsigned drop_seed,
+                                           void* stream) {
+  if (drop_thr >= 65536u) return BEVR_E_SHAPE;
+  return run(d, G, H, tap_ws, table_t, dkey_a, dkey_b, dkey_y, dkey_x, nullptr, 0, stream, key0, drop_thr, drop_seed);
+}
+#else
+extern "C" int bevr_attn_tap_bwd_k(const bevr_attn_desc* d, const void* G, const void* H, const void* tap_ws,
+                                   const float* table_t, float* dkey_a, float* dkey_b, float* dkey_y, float* dkey_x,
+                                   void* stream) {
+  return run(d, G, H, tap_ws, table_t, dkey_a, dkey_b, dkey_y, dkey_x, nullptr, 0, stream);
+}
+
+extern "C" size_t bevr_attn_tap_bwd_k_ws_bytes(const bevr_attn_desc* d) {
+  if (bevr_check_desc(d)) return 0;
+  return (LIST_HEAD + (size_t)d->n_prob * d->heads * (d->Np / 32)) * sizeof(int);
+}
+
+extern "C" int bevr_attn_tap_bwd_k_ws(const bevr_attn_desc* d, const void* G, const void* H, const void* tap_ws,
+                                      const float* table_t, float* dkey_a, float* dkey_b, float* dkey_y, float* dkey_x,
+                                      void* ws, int max_workgroups, void* stream) {
+  if (!ws) return BEVR_E_NULL;
+  if (!bevr_aligned16(ws)) return BEVR_E_ALIGN;
+  if (max_workgroups < 0) return BEVR_E_SHAPE;
+  return run(d, G, H, tap_ws, table_t, dkey_a, dkey_b, dkey_y, dkey_x, (int*)ws, max_workgroups, stream);
+}
+#endif
 #endif  // BEVR_TAP_X3
+

@@ -522,11 +522,13 @@ def dropout_keep_mask(seed: int, thr16: int, n_ph: int, S: int, N: int, device="
     return (x >> 16) >= thr16
 
 
-def _launch(entry, *args, flops=None, nbytes=0.0, tag="", timer=None, label=None):
+def _launch(entry, *args, flops=None, nbytes=0.0, tag="", timer=None, label=None, symbol=None):
     """One call of the C entry point `entry` (named once per call site) and the check of its return code.  flops given:
     through KERNEL_TIMER.run under the timer name `timer` (default: the entry point's), else untimed -- the timer's
-    records are bench.py's roofline counts.  label: the name in the error message where it is not the entry point's."""
-    fn = getattr(_lib.lib(), entry)
+    records are bench.py's roofline counts.  label: the name in the error message where it is not the entry point's.
+    symbol: the library symbol where the launch stays the route's `entry` in every record but another form of it runs
+    (the key-side backward's _ws forms)."""
+    fn = getattr(_lib.lib(), symbol or entry)
     rc = fn(*args) if flops is None else KERNEL_TIMER.run(timer or entry, flops, fn, *args, nbytes=nbytes, tag=tag)
     _lib.check(rc, label or entry)
 
@@ -831,7 +833,27 @@ def _bwd_k(name, o, *keys):
             _stream(), flops=_attn_flops(o.g, 4), tag=_call_tag(o.g))
 
 
+def bwd_k_list() -> bool:
+    """Do the key-side backward entry points bevr_attn_bwd_k and bevr_attn_tap_bwd_k hand their rare slow units (key
+    blocks / tiles that miss the main kernel's LDS window) to the second launch through a device work list (the _ws
+    entry points, include/bevrender_hip.h)?  BEVR_BWDK_LIST=0: the entry points without a list, whose second launch
+    covers the whole grid again (A/B timing).  Same results up to the order of the float atomics."""
+    return os.environ.get("BEVR_BWDK_LIST", "1") != "0"
+
+
+def _list_ws(ws_bytes, o, like):
+    """the work list of a _ws entry point: per-call scratch, its counters cleared by the entry point itself"""
+    return torch.empty(getattr(_lib.lib(), ws_bytes)(C.byref(o.desc)), device=like.device, dtype=torch.uint8)
+
+
 def _bwd_k_tile(name, o):       # the keys' table coordinates themselves
+    if name == K.BWD_K and bwd_k_list():     # (the launch keeps the route's name in every record, whichever symbol runs)
+        ws = _list_ws("bevr_attn_bwd_k_ws_bytes", o, o.dK)
+        _launch(name, C.byref(o.desc), _ptr(o.Qe), _ptr(o.Qt), _ptr(o.Ke), _ptr(o.Ve), _ptr(o.ka), _ptr(o.kb),
+                _ptr(o.pair), _ptr(o.dOe), _ptr(o.dOt), _ptr(o.LSE), _ptr(o.delta), _ptr(o.gscale), _ptr(o.dK), _ptr(o.dV),
+                _ptr(o.da), _ptr(o.db), _ptr(ws), 0, _stream(), flops=_attn_flops(o.g, 4), tag=_call_tag(o.g),
+                symbol="bevr_attn_bwd_k_ws")
+        return
     _bwd_k(name, o, _ptr(o.ka), _ptr(o.kb))
 
 
@@ -850,6 +872,12 @@ def _tap_bwd_q(name, o):
 
 
 def _tap_bwd_k(name, o):
+    # (the work list: the 16-bit modes without dropout -- the split mode and the dropout variant have no _ws entry point)
+    if name == K.TAP_BWD_K and o.desc.precision in (_lib.PREC_BF16, _lib.PREC_F16) and bwd_k_list():
+        ws = _list_ws("bevr_attn_tap_bwd_k_ws_bytes", o, o.dk[0])
+        _launch(name, C.byref(o.desc), _ptr(o.Gq), _ptr(o.H16), _ptr(o.ws), _ptr(o.Ttc), *[_ptr(t) for t in o.dk], _ptr(ws),
+                0, _stream(), flops=_attn_flops(o.g, 4), tag=_call_tag(o.g), symbol="bevr_attn_tap_bwd_k_ws")
+        return
     _launch(name, C.byref(o.desc), _ptr(o.Gq), _ptr(o.H16), _ptr(o.ws), _ptr(o.Ttc), *[_ptr(t) for t in o.dk], *o.drop,
             _stream(), flops=_attn_flops(o.g, 4), tag=_call_tag(o.g))
 

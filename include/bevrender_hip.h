@@ -194,6 +194,24 @@ int bevr_attn_bwd_k(const bevr_attn_desc* d, const void* Q, const void* Qt, cons
                     const void* dO, const void* dOt, const float* LSE, const float* delta, const float* grad_scale,
                     float* dK, float* dV, float* dkey_a, float* dkey_b, void* stream);
 
+/* bevr_attn_bwd_k with the rare key blocks of the general path (a block of 384 consecutive keys whose table slab does
+ * not fit the main kernel's LDS ring) dispatched from a device work list: the main launch appends each such block to
+ * `ws`, and a second launch of a FIXED number of workgroups shares (listed block, range of query tiles) items out --
+ * instead of one workgroup per block of the whole grid that first finds out whether it has anything to do.  All four
+ * precisions.  Same arguments and results as bevr_attn_bwd_k; the blocks of the general path are summed with float
+ * atomics over a different split of the query sweep, so their dK / dV / dkey_* differ from bevr_attn_bwd_k's in the
+ * order of the sums (as two runs of bevr_attn_bwd_k differ), every other block's rows are bit-equal.
+ *   ws              device scratch of bevr_attn_bwd_k_ws_bytes(d) bytes, 16-byte aligned: a count and one int per
+ *                   (problem-head, key block).  The entry point clears the count on `stream` itself; the contents
+ *                   afterwards are unspecified.  One ws per call in flight.
+ *   max_workgroups  0: as many workgroups as the device holds at once; > 0: at most that many (tests: items then
+ *                   outnumber the workgroups).  < 0: BEVR_E_SHAPE. */
+size_t bevr_attn_bwd_k_ws_bytes(const bevr_attn_desc* d);
+int bevr_attn_bwd_k_ws(const bevr_attn_desc* d, const void* Q, const void* Qt, const void* K, const void* V,
+                       const float* key_a, const float* key_b, const float* table_pair,
+                       const void* dO, const void* dOt, const float* LSE, const float* delta, const float* grad_scale,
+                       float* dK, float* dV, float* dkey_a, float* dkey_b, void* ws, int max_workgroups, void* stream);
+
 /* Attention dropout (nn.Dropout on the softmax weights: model/SCA_deform_attn.py:155,402-409,
  * model/TSA_deform_attn.py:90,313-323): the three entry points above with a keep mask.  The mask is not stored: pair
  * (problem-head ph = prob * heads + head, packed query mq, key n) is kept iff
@@ -326,6 +344,22 @@ int bevr_attn_tap_bwd_q(const bevr_attn_desc* d, const void* G, const void* H, c
  *   wrong dkey_a / dkey_b (tests/test_gpu_tap.py::test_tap_bwd_k_through_the_c_abi_as_the_header_describes). */
 int bevr_attn_tap_bwd_k(const bevr_attn_desc* d, const void* G, const void* H, const void* tap_ws,
                         const float* table, float* dkey_a, float* dkey_b, float* dkey_y, float* dkey_x, void* stream);
+
+/* bevr_attn_tap_bwd_k with the (32-key tile, BEV column) pairs whose taps do not fit one table chunk dispatched from a
+ * device work list: the main launch appends each tile that has such a column to `ws`, and a second launch of a FIXED
+ * number of waves claims (listed tile, range of BEV columns) items -- instead of the whole grid launched again to look
+ * for them.  BEVR_PREC_BF16 and BEVR_PREC_F16 (BEVR_PREC_BF16X3: BEVR_E_PRECISION -- the split mode and the dropout
+ * variant keep the entry points without a work list).  Same arguments and results as bevr_attn_tap_bwd_k up to the
+ * order of the float atomics every dkey_* is summed with.
+ *   ws              device scratch of bevr_attn_tap_bwd_k_ws_bytes(d) bytes, 16-byte aligned: two counters and one int
+ *                   per (problem-head, tile).  The entry point clears the counters on `stream` itself; the contents
+ *                   afterwards are unspecified.  One ws per call in flight.
+ *   max_workgroups  0: as many workgroups (of four waves) as the device holds at once; > 0: at most that many.
+ *                   < 0: BEVR_E_SHAPE. */
+size_t bevr_attn_tap_bwd_k_ws_bytes(const bevr_attn_desc* d);
+int bevr_attn_tap_bwd_k_ws(const bevr_attn_desc* d, const void* G, const void* H, const void* tap_ws,
+                           const float* table, float* dkey_a, float* dkey_b, float* dkey_y, float* dkey_x,
+                           void* ws, int max_workgroups, void* stream);
 
 /* Attention dropout on the tap entry points: the three above with the keep mask of bevr_attn_*_dropout (same hash, same
  * drop_thr = round(p * 65536) < 65536, BEVR_E_SHAPE otherwise).  The pair (ph, mq, key n' of this segment) is hashed
