@@ -29,6 +29,7 @@ SYMBOLS = [
     "bevr_attn_bwd_k", "bevr_attn_fwd_dropout", "bevr_attn_bwd_q_dropout", "bevr_attn_bwd_k_dropout", "bevr_attn_cell_fwd", "bevr_attn_cell_bwd_q", "bevr_attn_cell_bwd_k", "bevr_attn_tap_ws_bytes", "bevr_attn_tap_prep", "bevr_attn_tap_fwd", "bevr_attn_tap_bwd_q", "bevr_attn_tap_bwd_k", "bevr_attn_tap_fwd_dropout", "bevr_attn_tap_bwd_q_dropout", "bevr_attn_tap_bwd_k_dropout", "bevr_attn_gather_fwd", "bevr_attn_gather_fwd_rows", "bevr_attn_gather_fwd_x3", "bevr_attn_slab_ws_bytes", "bevr_attn_slab_prep", "bevr_attn_slab_bwd_q", "bevr_attn_slab_rows_ws_bytes", "bevr_attn_slab_rows_prep", "bevr_attn_slab_bwd_q_rows", "bevr_sample_fwd", "bevr_sample_bwd", "bevr_sample_fwd_bf16", "bevr_sample_bwd_bf16", "bevr_project_bev_grid", "bevr_project_bev_grid_masked", "bevr_corr_fwd",
     "bevr_corr_bwd", "bevr_recall_rank", "bevr_dwconv_fwd", "bevr_dwconv_bwd_w", "bevr_dwconv_res_gelu", "bevr_affine_warp_fwd", "bevr_affine_warp_bwd",
     "bevr_attn_bwd_k_ws_bytes", "bevr_attn_bwd_k_ws", "bevr_attn_tap_bwd_k_ws_bytes", "bevr_attn_tap_bwd_k_ws",
+    "bevr_attn_slab_x3_ws_bytes", "bevr_attn_slab_x3_prep", "bevr_attn_slab_bwd_q_x3",
     "bevr_offset_head_fwd", "bevr_offset_head_bwd", "bevr_key_positions_fwd", "bevr_key_positions_bwd", "bevr_kv_project", "bevr_layernorm_fwd", "bevr_layernorm_bwd", "bevr_merge_views_fwd", "bevr_merge_views_bwd", "bevr_merge_tap_fwd", "bevr_merge_tap_bwd", "bevr_attn_bwd_prep", "bevr_pack_kv", "bevr_unpack_dkv",
 ]
 
@@ -112,6 +113,9 @@ def lib() -> C.CDLL:
         L.bevr_attn_slab_rows_ws_bytes.argtypes = [dp]
         L.bevr_attn_slab_rows_prep.argtypes = [dp, fp, fp, vp, vp, vp]
         L.bevr_attn_slab_bwd_q_rows.argtypes = [dp, vp, vp, vp, vp, fp, vp, fp, fp, fp, fp, fp, ip, ip, vp]
+        L.bevr_attn_slab_x3_ws_bytes.argtypes = [dp]
+        L.bevr_attn_slab_x3_prep.argtypes = [dp, fp, fp, vp, vp, vp]
+        L.bevr_attn_slab_bwd_q_x3.argtypes = [dp, vp, vp, vp, vp, fp, vp, fp, fp, fp, fp, fp, vp]
         L.bevr_sample_fwd.argtypes = [fp, fp, fp] + [ip] * 5 + [vp]
         L.bevr_sample_bwd.argtypes = [fp] * 5 + [ip] * 5 + [vp]
         L.bevr_sample_fwd_bf16.argtypes = [vp, fp, fp] + [ip] * 5 + [vp]
@@ -143,7 +147,7 @@ def lib() -> C.CDLL:
         for name in SYMBOLS:
             fn = getattr(L, name)
             if name in ("bevr_attn_key_ws_bytes", "bevr_attn_tap_ws_bytes", "bevr_attn_slab_ws_bytes",
-                        "bevr_attn_slab_rows_ws_bytes", "bevr_attn_bwd_k_ws_bytes", "bevr_attn_tap_bwd_k_ws_bytes"):
+                        "bevr_attn_slab_rows_ws_bytes", "bevr_attn_slab_x3_ws_bytes", "bevr_attn_bwd_k_ws_bytes", "bevr_attn_tap_bwd_k_ws_bytes"):
                 fn.restype = C.c_size_t
             elif name not in ("bevr_strerror",):
                 fn.restype = C.c_int

@@ -43,8 +43,15 @@
 // pair's window row is A + ROW0 + i whichever band i lies in, so the indexing and the clamping argument are the ones
 // above (a window cut to the band's rows would clamp a key with A = -15 seen from row 217 onto the wrong, non-zero, row).
 // The entry points are bevr_attn_slab_rows_ws_bytes / _slab_rows_prep / bevr_attn_slab_bwd_q_rows.
+//
+// BEVR_SLAB_X3 = 1 (attn_slab_bwd_q_x3.hip, a translation unit of its own for the same reason): BEVR_PREC_BF16X3, S <= 211.
+// This file gives it the constants, the workspace, the preparation kernels, the launch and the entry points
+// (bevr_attn_slab_x3_ws_bytes / _slab_x3_prep / bevr_attn_slab_bwd_q_x3); the kernel body is that file's own.
 #ifndef BEVR_SLAB_ROWS
 #define BEVR_SLAB_ROWS 0
+#endif
+#ifndef BEVR_SLAB_X3
+#define BEVR_SLAB_X3 0
 #endif
 #include "attn_tile.h"
 #include "attn_tap.h"
@@ -53,7 +60,11 @@
 
 // clocks summed over the emissions of wave 0 (a worker, at 0), wave 6 (the last worker, at 16) and the producer (at 32) of
 // every workgroup, 16 slots each
+#if BEVR_SLAB_X3
+BEVR_PROF_DEFINE(slab_x3, 48)
+#else
 BEVR_PROF_DEFINE(slab, 48)
+#endif
 
 namespace {
 
@@ -68,7 +79,13 @@ constexpr int SNRB = 7;            // row blocks per column (S <= 217) -- BEVR_S
 constexpr int SNWORK = SNRB;       // worker waves: one per row block, BOTH 32-key halves of an emission each
 constexpr int STHREADS = (SNWORK + 1) * 64;   // 8 waves = 2 per SIMD: 256 registers per wave (see the kernel)
 constexpr int SEK = 64;            // keys per emission
+#if BEVR_SLAB_X3
+constexpr int SKROW = 128;         // split-mode rows, unpadded: their 16-byte chunks are swizzled (attn_slab_bwd_q_x3.hip)
+constexpr int SLAB_CELL = 16;      // bytes per table cell in LDS: the f32 pair (T[y], T[y+1]) and the 64-bit gradient cell
+#else
 constexpr int SKROW = 80;          // bytes per staged K / V row (64 + 16: conflict-free fragment reads)
+constexpr int SLAB_CELL = 12;      // bytes per table cell in LDS: the 16-bit pair and the 64-bit gradient cell
+#endif
 constexpr float SLAB_EPS = 0.02f;  // slack of the key runs (in table columns): the kernel's own floor() decides membership
 
 // per key, in the problem's b-sorted order (bevr_attn_slab_prep)
@@ -76,17 +93,26 @@ struct SlabKey { int A; float fy; float b; int pad; };
 
 // per-(column, key) constants of an emission, written by the producer (lane = key); a worker lane reads ONE record per
 // half and the key-row loop takes its constants from those registers by DPP (process)
+#if BEVR_SLAB_X3
+struct SlabCK {
+  float w00, w01, w10, w11;   // tap weights (1-fx)(1-fy), (1-fx)fy, fx(1-fy), fx fy in f32, as the region kernel's f32 layout
+  int cell;                   // BYTE offset of the key's first tap's value entry (8-byte entries) for window row offset 0
+  int row;                    // its row part, A + ROW0 (the clamped body separates the two)
+  int pad0, pad1;
+};
+#else
 struct SlabCK {
   unsigned wA, wB;   // tap weights of column X / X + 1 as packed 16-bit pairs (row y, row y + 1)
   int cell;          // window index of the key's first tap for window row offset 0: colbase + row
   int row;           // its row part, A + ROW0 (the clamped body separates the two)
 };
+#endif
 
 struct SlabLds {
   static constexpr int K_BYTES = SEK * SKROW;
   static constexpr int OFF_V = K_BYTES;
   static constexpr int OFF_CK = 2 * K_BYTES;
-  static constexpr int OFF_CT = OFF_CK + SEK * 16;     // 2 x u32x4: {flags, j, amin0, amax0}, {amin1, amax1, 0, 0}
+  static constexpr int OFF_CT = OFF_CK + SEK * (int)sizeof(SlabCK);     // 2 x u32x4: {flags, j, amin0, amax0}, {amin1, amax1, 0, 0}
   static constexpr int BUF = OFF_CT + 32;
 };
 enum { SF_DONE = 1, SF_FIRST = 2, SF_LAST = 4 };
@@ -96,7 +122,7 @@ __host__ __device__ inline int slab_rows(int S) { return SLAB_ROW0 + S + SLAB_PA
 // columns in LDS: column 0 is the KILL column (values -big, masked keys point there; its right neighbour is a real column,
 // read with weight 0), columns 1 .. sw + 1 the slab's sw owned columns and the right tap column of the last one
 __host__ __device__ inline size_t slab_lds_bytes(int S, int sw, int rp = SLAB_RP) {
-  return (size_t)(sw + 2) * rp * 12 + 2 * SlabLds::BUF + 64;
+  return (size_t)(sw + 2) * rp * SLAB_CELL + 2 * SlabLds::BUF + 64;
 }
 __host__ __device__ inline int slab_width(int S, int rp = SLAB_RP) {
   int sw = SLAB_W_MAX;
@@ -212,6 +238,16 @@ __global__ __launch_bounds__(256) void slab_ranges_kernel(bevr_attn_desc d, cons
 // LDS-only barrier is not enough here: the producer's global loads are consumed by its own LDS stores before the barrier
 #define SLAB_BARRIER() __syncthreads()
 
+#if BEVR_SLAB_X3
+// the split-bf16 body: defined in attn_slab_bwd_q_x3.hip, behind this file's launch and entry points
+template <int PREC>
+__global__ __launch_bounds__(STHREADS, 1) void attn_slab_bwd_q_kernel(
+    bevr_attn_desc d, const char* __restrict__ Q, const char* __restrict__ Ks, const char* __restrict__ Vs,
+    const SlabKey* __restrict__ skeys, const int* __restrict__ kbeg, const int* __restrict__ kend,
+    const int4* __restrict__ items, int* __restrict__ cnt, const char* __restrict__ table_pair,
+    const char* __restrict__ dO, const float* __restrict__ LSE, const float* __restrict__ delta,
+    const float* __restrict__ grad_scale, float* __restrict__ dQ, float* __restrict__ dtable, int n_slab, int sw, int R);
+#else
 // BEVR_SLAB_ROWS: RP the row pitch, row0 (a multiple of SQROWS) the first BEV row of the launch's band, n_rb_band <= SNRB its
 // row blocks: worker wave w owns row block row0 / SQROWS + w of the column
 #if BEVR_SLAB_ROWS
@@ -675,6 +711,7 @@ __global__ __launch_bounds__(STHREADS, 1) void attn_slab_bwd_q_kernel(
   }
   PROF_FLUSH(slab, producer ? 32 : (wave ? 16 : 0), lane == 0 && (wave == 0 || wave == SNWORK - 1 || producer));
 }
+#endif   // !BEVR_SLAB_X3
 
 #if BEVR_SLAB_ROWS
 #define SLAB_KERNEL(PREC, RP) attn_slab_bwd_q_kernel<PREC, RP>
@@ -739,7 +776,18 @@ bool slab_band_ok(const bevr_attn_desc& d, int row0, int n_rows) {
 }
 #define SLAB_WS_BYTES bevr_attn_slab_rows_ws_bytes
 #define SLAB_PREP bevr_attn_slab_rows_prep
+#define SLAB_PREC_OK is16
+#elif BEVR_SLAB_X3
+__host__ __device__ constexpr bool slab_prec_x3(int prec) { return prec == BEVR_PREC_BF16X3; }
+bool slab_shape_ok(const bevr_attn_desc& d) {
+  return slab_prec_x3(d.precision) && slab_n_rb(d.S) <= SNRB && slab_rows(d.S) <= SLAB_RP && SLAB_CH <= 64 &&
+         slab_lds_bytes(d.S, slab_width(d.S)) <= 160 * 1024;
+}
+#define SLAB_WS_BYTES bevr_attn_slab_x3_ws_bytes
+#define SLAB_PREP bevr_attn_slab_x3_prep
+#define SLAB_PREC_OK slab_prec_x3
 #else
+#define SLAB_PREC_OK is16
 bool slab_shape_ok(const bevr_attn_desc& d) {
   return is16(d.precision) && slab_n_rb(d.S) <= SNRB && slab_rows(d.S) <= SLAB_RP && SLAB_CH <= 64 &&
          slab_lds_bytes(d.S, slab_width(d.S)) <= 160 * 1024;
@@ -760,7 +808,7 @@ extern "C" int SLAB_PREP(const bevr_attn_desc* d, const float* key_a, const floa
   int rc = bevr_check_desc(d);
   if (rc) return rc;
   if (!key_a || !key_b || !order || !slab_ws_) return BEVR_E_NULL;
-  if (!is16(d->precision)) return BEVR_E_PRECISION;
+  if (!SLAB_PREC_OK(d->precision)) return BEVR_E_PRECISION;
   if (!slab_shape_ok(*d)) return BEVR_E_SHAPE;
   if (!bevr_aligned16(slab_ws_)) return BEVR_E_ALIGN;
   const SlabWs w = slab_ws(*d);
@@ -784,6 +832,10 @@ extern "C" int bevr_attn_slab_bwd_q_rows(const bevr_attn_desc* d, const void* Q,
                                          const void* slab_ws_, const float* table_pair, const void* dO, const float* LSE,
                                          const float* delta, const float* grad_scale, float* dQ, float* dtable, int row0,
                                          int n_rows, void* stream) {
+#elif BEVR_SLAB_X3
+extern "C" int bevr_attn_slab_bwd_q_x3(const bevr_attn_desc* d, const void* Q, const void* Ks, const void* Vs,
+                                       const void* slab_ws_, const float* table_pair, const void* dO, const float* LSE,
+                                       const float* delta, const float* grad_scale, float* dQ, float* dtable, void* stream) {
 #else
 extern "C" int bevr_attn_slab_bwd_q(const bevr_attn_desc* d, const void* Q, const void* Ks, const void* Vs,
                                     const void* slab_ws_, const float* table_pair, const void* dO, const float* LSE,
@@ -793,7 +845,7 @@ extern "C" int bevr_attn_slab_bwd_q(const bevr_attn_desc* d, const void* Q, cons
   if (rc) return rc;
   if (!Q || !Ks || !Vs || !slab_ws_ || !table_pair || !dO || !LSE || !delta || !grad_scale || !dQ || !dtable)
     return BEVR_E_NULL;
-  if (!is16(d->precision)) return BEVR_E_PRECISION;
+  if (!SLAB_PREC_OK(d->precision)) return BEVR_E_PRECISION;
   if (!slab_shape_ok(*d)) return BEVR_E_SHAPE;
 #if BEVR_SLAB_ROWS
   if (!slab_band_ok(*d, row0, n_rows)) return BEVR_E_SHAPE;
@@ -810,6 +862,8 @@ extern "C" int bevr_attn_slab_bwd_q(const bevr_attn_desc* d, const void* Q, cons
                 : launch<BEVR_PREC_BF16, SLAB_RP_A>(*d, Q, Ks, Vs, slab_ws_, table_pair, dO, LSE, delta, grad_scale, dQ, dtable, row0, nb, st);
   return tall ? launch<BEVR_PREC_F16, SLAB_RP_B>(*d, Q, Ks, Vs, slab_ws_, table_pair, dO, LSE, delta, grad_scale, dQ, dtable, row0, nb, st)
               : launch<BEVR_PREC_F16, SLAB_RP_A>(*d, Q, Ks, Vs, slab_ws_, table_pair, dO, LSE, delta, grad_scale, dQ, dtable, row0, nb, st);
+#elif BEVR_SLAB_X3
+  return launch<BEVR_PREC_BF16X3>(*d, Q, Ks, Vs, slab_ws_, table_pair, dO, LSE, delta, grad_scale, dQ, dtable, 0, 0, st);
 #else
   if (d->precision == BEVR_PREC_BF16)
     return launch<BEVR_PREC_BF16>(*d, Q, Ks, Vs, slab_ws_, table_pair, dO, LSE, delta, grad_scale, dQ, dtable, 0, 0, st);

@@ -4,7 +4,8 @@
 // per-kernel __device__ array that bevr_debug_prof_<tag>(out, reset) copies out or clears.  Without BEVR_PROF every
 // macro below expands to nothing, and so it does in the VARIANT translation units (BEVR_DROP, BEVR_TAP_X3,
 // BEVR_GATHER_ROWS, BEVR_SLAB_ROWS: a kernel's source compiled a second time), which would define the array and its reader
-// again.  Include it after those four have their defaults (bevr_common.h, attn_tap.h, attn_gather_fwd.hip,
+// again (BEVR_SLAB_X3 is not one of them: attn_slab_bwd_q_x3.hip has a kernel body of its own and its own tag, slab_x3).
+// Include it after those four have their defaults (bevr_common.h, attn_tap.h, attn_gather_fwd.hip,
 // attn_slab_bwd_q.hip).
 //
 //   BEVR_PROF_DEFINE(tag, n)      file scope: the n counters and their reader

@@ -540,6 +540,7 @@ class K:
     GATHER_X3 = "bevr_attn_gather_fwd_x3"
     BWD_Q, BWD_Q_DROP, SLAB_BWD_Q = "bevr_attn_bwd_q", "bevr_attn_bwd_q_dropout", "bevr_attn_slab_bwd_q"
     SLAB_BWD_Q_ROWS = "bevr_attn_slab_bwd_q_rows"
+    SLAB_BWD_Q_X3 = "bevr_attn_slab_bwd_q_x3"
     BWD_K, BWD_K_DROP = "bevr_attn_bwd_k", "bevr_attn_bwd_k_dropout"
     CELL_FWD, CELL_BWD_Q, CELL_BWD_K = "bevr_attn_cell_fwd", "bevr_attn_cell_bwd_q", "bevr_attn_cell_bwd_k"
     TAP_FWD, TAP_FWD_DROP = "bevr_attn_tap_fwd", "bevr_attn_tap_fwd_dropout"
@@ -632,6 +633,8 @@ def attention_route(precision: int, groups: int, S: int, Wt: int, N: int, cell_s
                 fwd = {None: K.FWD, "whole": K.GATHER, "bands": K.GATHER_ROWS}[gather]
             if slab_rows_supported(precision, S, Wt):       # off unless BEVR_SLAB_ROWS asks for it
                 bwd_q = K.SLAB_BWD_Q_ROWS
+            elif precision == _lib.PREC_BF16X3:             # off unless BEVR_SLAB_X3 asks for it
+                bwd_q = K.SLAB_BWD_Q_X3 if slab_supported(precision, S, Wt) else K.BWD_Q
             else:
                 bwd_q = K.SLAB_BWD_Q if slab_supported(precision, S, Wt) else K.BWD_Q
             segs.append(KeySegment("region", 0, n_region, fwd, bwd_q, K.BWD_K))
@@ -691,11 +694,22 @@ def slab_supported(precision, S, Wt=None) -> bool:
     LDS column).  With Wt given: only tables at least twice as wide as TSA's (rx >= 2 table columns per BEV column: SCA) --
     on TSA's regular key grid the query-tile kernel's window hardly moves and it is the faster one (0.91 against 0.77 T
     pairs/s on the benchmark, profiles/r05_*); BEVR_SLAB=0 turns the kernel off, BEVR_SLAB=2 forces it for every table
-    (A/B timing, tests).  Same results up to the order of the float atomics and one rounding of the tap weights."""
+    (A/B timing, tests).  Same results up to the order of the float atomics and one rounding of the tap weights.
+    The split-bf16 mode (BEVR_PREC_BF16X3: csrc/attn_slab_bwd_q_x3.hip, bevr_attn_slab_bwd_q_x3) under the same rules when
+    BEVR_SLAB_X3 is set and not 0; the switch's default is SLAB_X3_DEFAULT: off, that mode's earlier routing (the
+    query-tile kernel), until the pinned route table changes with it."""
     mode = os.environ.get("BEVR_SLAB", "1")
-    if mode == "0" or precision not in (_lib.PREC_BF16, _lib.PREC_F16) or S > 211:
+    if mode == "0" or S > 211:
+        return False
+    if precision == _lib.PREC_BF16X3:
+        if os.environ.get("BEVR_SLAB_X3", SLAB_X3_DEFAULT) == "0":
+            return False
+    elif precision not in (_lib.PREC_BF16, _lib.PREC_F16):
         return False
     return mode == "2" or Wt is None or Wt - 1 >= 4 * (S - 1)
+
+
+SLAB_X3_DEFAULT = "0"                             # BEVR_SLAB_X3 when unset (slab_supported)
 
 
 SLAB_ROWS_MAX_S, SLAB_BAND_BLOCKS = 448, 7
@@ -812,9 +826,14 @@ def _slab_operands(o, ws_bytes, prep):
 
 def _bwd_q_slab(name, o):
     g = o.g
-    Ks, Vs, sws = _slab_operands(o, "bevr_attn_slab_ws_bytes", "bevr_attn_slab_prep")
+    if name == K.SLAB_BWD_Q_X3:     # split rows in float containers: sorted and gathered as they stand
+        Ks, Vs, sws = _slab_operands(o, "bevr_attn_slab_x3_ws_bytes", "bevr_attn_slab_x3_prep")
+    else:
+        Ks, Vs, sws = _slab_operands(o, "bevr_attn_slab_ws_bytes", "bevr_attn_slab_prep")
+    # (the timer's name is the slab route's, whichever entry point runs it)
     _launch(name, C.byref(o.desc), _ptr(o.Qe), _ptr(Ks), _ptr(Vs), _ptr(sws), _ptr(o.pair), _ptr(o.dOe), _ptr(o.LSE),
-            _ptr(o.delta), _ptr(o.gscale), _ptr(o.dQ), _ptr(o.dT), _stream(), flops=_attn_flops(g, 3), tag=_call_tag(g))
+            _ptr(o.delta), _ptr(o.gscale), _ptr(o.dQ), _ptr(o.dT), _stream(), flops=_attn_flops(g, 3), tag=_call_tag(g),
+            timer=K.SLAB_BWD_Q)
 
 
 def _bwd_q_slab_rows(name, o):
@@ -885,7 +904,7 @@ def _tap_bwd_k(name, o):
 _RUN = {K.FWD: _fwd_tile, K.FWD_DROP: _fwd_tile, K.GATHER: _fwd_gather, K.GATHER_ROWS: _fwd_gather,
         K.GATHER_X3: _fwd_gather, K.CELL_FWD: _fwd_cell,
         K.BWD_Q: _bwd_q_tile, K.BWD_Q_DROP: _bwd_q_tile, K.CELL_BWD_Q: _bwd_q_tile, K.SLAB_BWD_Q: _bwd_q_slab,
-        K.SLAB_BWD_Q_ROWS: _bwd_q_slab_rows,
+        K.SLAB_BWD_Q_ROWS: _bwd_q_slab_rows, K.SLAB_BWD_Q_X3: _bwd_q_slab,
         K.BWD_K: _bwd_k_tile, K.BWD_K_DROP: _bwd_k_tile, K.CELL_BWD_K: _bwd_k_cell,
         K.TAP_FWD: _tap_fwd, K.TAP_FWD_DROP: _tap_fwd, K.TAP_BWD_Q: _tap_bwd_q, K.TAP_BWD_Q_DROP: _tap_bwd_q,
         K.TAP_BWD_K: _tap_bwd_k, K.TAP_BWD_K_DROP: _tap_bwd_k}

@@ -64,7 +64,9 @@ extern "C" {
  *    bevr_attn_slab_rows_ws_bytes / _slab_rows_prep / bevr_attn_slab_bwd_q_rows (the slab query-side backward over a band
  *    of BEV rows of every column: BEV sides up to 448; the three bevr_attn_slab_* entry points keep their contract);
  *    bevr_attn_gather_fwd_x3 (the gather forward in BEVR_PREC_BF16X3, over a row range; bevr_attn_gather_fwd and
- *    bevr_attn_gather_fwd_rows keep returning BEVR_E_PRECISION for that mode). */
+ *    bevr_attn_gather_fwd_rows keep returning BEVR_E_PRECISION for that mode);
+ *    bevr_attn_slab_x3_ws_bytes / _slab_x3_prep / bevr_attn_slab_bwd_q_x3 (the slab query-side backward in
+ *    BEVR_PREC_BF16X3, S <= 211; the 16-bit slab entry points keep returning BEVR_E_PRECISION for that mode). */
 #define BEVR_ABI_VERSION 6
 
 enum {
@@ -490,6 +492,22 @@ int bevr_attn_slab_rows_prep(const bevr_attn_desc* d, const float* key_a, const 
 int bevr_attn_slab_bwd_q_rows(const bevr_attn_desc* d, const void* Q, const void* Ks, const void* Vs, const void* slab_ws,
                               const float* table_pair, const void* dO, const float* LSE, const float* delta,
                               const float* grad_scale, float* dQ, float* dtable, int row0, int n_rows, void* stream);
+/* The same in BEVR_PREC_BF16X3 (csrc/attn_slab_bwd_q_x3.hip: the three matrix products as three-term split-bf16 products,
+ * bias taps and table gradient per pair in f32), S <= 211.  A slab cell is the f32 pair and the gradient cell, 16 bytes,
+ * so the slab is narrower (15 table columns against 24) and the workspace has entry points of its own.
+ *   bevr_attn_slab_x3_ws_bytes / _slab_x3_prep: as bevr_attn_slab_ws_bytes / _slab_prep, for this kernel's slab width
+ *           (0 / BEVR_E_SHAPE for S > 211, 0 / BEVR_E_PRECISION for any mode but BEVR_PREC_BF16X3); not interchangeable
+ *           with the other slab workspaces.
+ *   bevr_attn_slab_bwd_q_x3: operands and checks of bevr_attn_slab_bwd_q, in its order (NULL, precision, shape,
+ *           alignment).  Q, Ks, Vs and dO are the mode's 128-byte split rows (hi and lo bf16 images per 16-element half,
+ *           as bevr_attn_bwd_q takes Q, K and dO in this mode; Ks / Vs: the K / V rows of bevr_pack_kv in the sorted order),
+ *           table_pair the f32 pair table.  BEVR_E_PRECISION for any mode but BEVR_PREC_BF16X3. */
+size_t bevr_attn_slab_x3_ws_bytes(const bevr_attn_desc* d);
+int bevr_attn_slab_x3_prep(const bevr_attn_desc* d, const float* key_a, const float* key_b, const int32_t* order,
+                           void* slab_ws, void* stream);
+int bevr_attn_slab_bwd_q_x3(const bevr_attn_desc* d, const void* Q, const void* Ks, const void* Vs, const void* slab_ws,
+                            const float* table_pair, const void* dO, const float* LSE, const float* delta,
+                            const float* grad_scale, float* dQ, float* dtable, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Bilinear feature sampling, align_corners=True, zero padding (grid_sample semantics).

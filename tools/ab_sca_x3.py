@@ -5,8 +5,11 @@ and sent through the region / cell kernels).  The two routes alternate in ONE pr
 events around each step, one warm-up step per route; medians with min and max.
 --gather: the A/B of the split-mode gather forward instead -- both routes with BEVR_TAP_X3=1, the scattered keys' forward
 on bevr_attn_gather_fwd_x3 (BEVR_GATHER_X3=1) against the region forward (BEVR_GATHER_X3=0, the parent's routing).
+--slab: the A/B of the split-mode slab backward -- both routes with BEVR_TAP_X3=1 and BEVR_GATHER_X3=0 (the defaults' forward),
+the scattered keys' query-side backward on bevr_attn_slab_bwd_q_x3 (BEVR_SLAB_X3=1) against the query-tile kernel
+(BEVR_SLAB_X3=0, the parent's routing).
 
-    B=8 ITERS=5 python tools/ab_sca_x3.py [--gather] [out.json]"""
+    B=8 ITERS=5 python tools/ab_sca_x3.py [--gather | --slab] [out.json]"""
 import json
 import math
 import os
@@ -57,8 +60,11 @@ def main():
     q = torch.randn(B, C, S, S, generator=gen).to(DEV).requires_grad_(True)
     x = torch.randn(B * V, C, Hi, Wi, generator=gen).to(DEV).requires_grad_(True)
     cot = torch.randn(B, C, S, S, generator=gen).to(DEV)
-    argv = [a for a in sys.argv[1:] if a != "--gather"]
-    if "--gather" in sys.argv[1:]:
+    argv = [a for a in sys.argv[1:] if a not in ("--gather", "--slab")]
+    if "--slab" in sys.argv[1:]:
+        new, routes = "slab_x3", (("slab_x3", {"BEVR_TAP_X3": "1", "BEVR_GATHER_X3": "0", "BEVR_SLAB_X3": "1"}),
+                                  ("parent_route", {"BEVR_TAP_X3": "1", "BEVR_GATHER_X3": "0", "BEVR_SLAB_X3": "0"}))
+    elif "--gather" in sys.argv[1:]:
         new, routes = "gather_x3", (("gather_x3", {"BEVR_TAP_X3": "1", "BEVR_GATHER_X3": "1"}),
                                     ("parent_route", {"BEVR_TAP_X3": "1", "BEVR_GATHER_X3": "0"}))
     else:

@@ -1,5 +1,5 @@
 """Phase clock breakdown (s_memtime stamps, csrc/bevr_prof.h) of one attention kernel on the SCA block of prof_sca.py:
-    python tools/prof_phases.py <fwd|bwd_q|bwd_k|gather|slab>
+    python tools/prof_phases.py <fwd|bwd_q|bwd_k|gather|slab|slab_x3>
 Needs the instrumented build: make -C bevrender_amd/csrc PROF=1 OUTDIR=../lib_prof"""
 import os, sys, ctypes as C
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -16,6 +16,8 @@ KERNELS = {
                   names=["top(slide)", "frag+mfma", "taps+valu", "dv/dk mfma", "stage store", "barrier", "total", "n_it"]),
     "gather": dict(slots=32, warm=0, iters=2, env={}),
     "slab": dict(slots=48, warm=2, iters=1, env={}),
+    # the split-bf16 slab kernel (csrc/attn_slab_bwd_q_x3.hip): the block in that mode, the switch on
+    "slab_x3": dict(slots=48, warm=2, iters=1, env={"PREC": "bf16x3", "BEVR_TAP_X3": "1", "BEVR_SLAB_X3": "1"}),
 }
 GATHER_PRODUCER = ["", "advance+stage", "", "wait fills+kv", "barrier wait", "n", "issue fills", ""]
 GATHER_ROWBLOCK = ["barrier wait", "compute", "wait fills", "", "loop total", "n", "", ""]
@@ -67,7 +69,7 @@ def main(tag):
     torch.cuda.synchronize()
     reader(buf, 0)
     v = list(buf)
-    {"gather": report_gather, "slab": report_slab}.get(tag, lambda v_: report_waves(k, v_))(v)
+    {"gather": report_gather, "slab": report_slab, "slab_x3": report_slab}.get(tag, lambda v_: report_waves(k, v_))(v)
 
 
 if __name__ == "__main__":

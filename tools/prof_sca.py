@@ -1,4 +1,5 @@
-"""SCA block at the benchmark geometry (ring rig, S=200, D=5, 6 views, k-d ordered keys), 1 sample, fwd+bwd."""
+"""SCA block at the benchmark geometry (ring rig, S=200, D=5, 6 views, k-d ordered keys), 1 sample, fwd+bwd.
+PREC=bf16x3 (or f32, f16): the operand mode; default bf16."""
 import os, sys, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -17,7 +18,8 @@ def run(iters=None):
     T, K = ring_rig(V, 704, 256)
     proj = BEV2CameraProjector(imu_to_rgb={0: T}, K={0: K}, vehicle_type_code=0, img_width=704, img_height=256,
                                ori_img_width=704, ori_img_height=256, device=dev)
-    sca = SpatialCrossAttn({"X": 50, "Y": 50, "Z": 2}, proj, S, D, -1.0, C, h, 1, 1, 3, B, True, n_views=V, precision="bf16").to(dev)
+    sca = SpatialCrossAttn({"X": 50, "Y": 50, "Z": 2}, proj, S, D, -1.0, C, h, 1, 1, 3, B, True, n_views=V,
+                           precision=os.environ.get("PREC", "bf16")).to(dev)
     for m in sca.modules():
         # WIDE=1: large learned offsets (keys scattered over the table: the fallback paths); default: module init
         if os.environ.get("WIDE") and isinstance(m, torch.nn.Conv2d):
