@@ -30,6 +30,7 @@ SYMBOLS = [
     "bevr_corr_bwd", "bevr_recall_rank", "bevr_dwconv_fwd", "bevr_dwconv_bwd_w", "bevr_dwconv_res_gelu", "bevr_affine_warp_fwd", "bevr_affine_warp_bwd",
     "bevr_attn_bwd_k_ws_bytes", "bevr_attn_bwd_k_ws", "bevr_attn_tap_bwd_k_ws_bytes", "bevr_attn_tap_bwd_k_ws",
     "bevr_attn_slab_x3_ws_bytes", "bevr_attn_slab_x3_prep", "bevr_attn_slab_bwd_q_x3",
+    "bevr_attn_tap_fwd_x3_dropout", "bevr_attn_tap_bwd_q_x3_dropout", "bevr_attn_tap_bwd_k_x3_dropout",
     "bevr_offset_head_fwd", "bevr_offset_head_bwd", "bevr_key_positions_fwd", "bevr_key_positions_bwd", "bevr_kv_project", "bevr_layernorm_fwd", "bevr_layernorm_bwd", "bevr_merge_views_fwd", "bevr_merge_views_bwd", "bevr_merge_tap_fwd", "bevr_merge_tap_bwd", "bevr_attn_bwd_prep", "bevr_pack_kv", "bevr_unpack_dkv",
 ]
 
@@ -104,6 +105,9 @@ def lib() -> C.CDLL:
         L.bevr_attn_tap_fwd_dropout.argtypes = [dp, vp, vp, fp, fp, fp, fp, vp, u32, u32, u32, vp]
         L.bevr_attn_tap_bwd_q_dropout.argtypes = [dp, vp, vp, vp, fp, fp, fp, u32, u32, u32, vp]
         L.bevr_attn_tap_bwd_k_dropout.argtypes = [dp, vp, vp, vp, fp, fp, fp, fp, fp, u32, u32, u32, vp]
+        L.bevr_attn_tap_fwd_x3_dropout.argtypes = L.bevr_attn_tap_fwd_dropout.argtypes
+        L.bevr_attn_tap_bwd_q_x3_dropout.argtypes = L.bevr_attn_tap_bwd_q_dropout.argtypes
+        L.bevr_attn_tap_bwd_k_x3_dropout.argtypes = L.bevr_attn_tap_bwd_k_dropout.argtypes
         L.bevr_attn_gather_fwd.argtypes = [dp, vp, vp, vp, vp, vp, fp, fp, fp, vp, vp]
         L.bevr_attn_gather_fwd_rows.argtypes = [dp, vp, vp, vp, vp, vp, fp, fp, fp, vp, ip, ip, vp]
         L.bevr_attn_gather_fwd_x3.argtypes = [dp, vp, vp, vp, vp, vp, fp, fp, fp, vp, ip, ip, vp]

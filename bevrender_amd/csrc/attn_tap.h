@@ -225,6 +225,15 @@ __device__ __forceinline__ bool tap_drop_keep(uint32_t hrow, uint32_t kh, uint32
 __device__ __forceinline__ bool tap_drop_keep8(uint32_t hrow, uint32_t kh0, int k, uint32_t thr16) {
   return tap_drop_keep(hrow, kh0 + (uint32_t)(16 * (k >> 2) + (k & 3)) * 0xC2B2AE3Du, thr16);
 }
+// Split mode: what a DROPPED pair keeps of the H product, -delta, out of its four bf16 parts.  hi2 / lo2: the dword at
+// slots TAP_CHI, TAP_CLO of the row's hi and lo image, (p0, p2) and (p1, p3); smallest parts first: the float they were
+// split from, bit for bit (the kept pairs get the same four parts through the matrix product against w = 1).  In both
+// modes slot TAP_ONE of H (the kept mass's cotangent, droppable) is not part of it; in split mode that slot holds a
+// (hi, lo) pair like the tap slots, contracted with w = (1, 0) to hi + lo
+__device__ __forceinline__ float tap_drop_ndel4(uint32_t hi2, uint32_t lo2) {
+  typedef Half<BEVR_PREC_BF16> B;
+  return ((B::hi(lo2) + B::hi(hi2)) + B::lo(lo2)) + B::lo(hi2);
+}
 #else
 #define TAP_DROP_PARAMS
 #define TAP_DROP_ARGS

@@ -331,6 +331,8 @@ __device__ __forceinline__ void tap_bwd_k_body(
     for (int r = 0; r < 8; ++r) {
       const uint32_t c2 = *reinterpret_cast<const uint32_t*>(base + L::OFF_H + (16 * (r >> 2) + 4 * g + (r & 3)) * 32 + TAP_CHI * 2);
       ndel[r] = TapHalf<PREC>::lo(c2) + TapHalf<PREC>::hi(c2);
+      if constexpr (X3)
+        ndel[r] = tap_drop_ndel4(c2, *reinterpret_cast<const uint32_t*>(base + L::OFF_LO + L::OFF_H + (16 * (r >> 2) + 4 * g + (r & 3)) * 32 + TAP_CHI * 2));
     }
 #endif
 #pragma unroll
@@ -644,7 +646,25 @@ int launch(const bevr_attn_desc& d, const void* G, const void* H, const void* ta
 
 }  // namespace
 
-#if BEVR_TAP_X3
+#if BEVR_TAP_X3 && BEVR_DROP
+// the split-mode instantiations with the keep mask: this translation unit is attn_tap_bwd_k_x3_drop.hip, an entry point
+// of its own (the arguments and checks of bevr_attn_tap_bwd_k_dropout; BEVR_PREC_BF16X3 alone; the slow pairs by the main
+// grid launched again: no work list)
+extern "C" int bevr_attn_tap_bwd_k_x3_dropout(const bevr_attn_desc* d, const void* G, const void* H, const void* tap_ws,
+                                              const float* table_t, float* dkey_a, float* dkey_b, float* dkey_y,
+                                              float* dkey_x, unsigned key0, unsigned drop_thr, unsigned drop_seed,
+                                              void* stream) {
+  if (drop_thr >= 65536u) return BEVR_E_SHAPE;
+  int rc = bevr_check_desc(d);
+  if (rc) return rc;
+  if (!G || !H || !tap_ws || !table_t || !dkey_a || !dkey_b || !dkey_y || !dkey_x) return BEVR_E_NULL;
+  if (d->groups != 1) return BEVR_E_SHAPE;
+  if (!bevr_aligned16(G) || !bevr_aligned16(H) || !bevr_aligned16(tap_ws)) return BEVR_E_ALIGN;
+  if (d->precision != BEVR_PREC_BF16X3) return BEVR_E_PRECISION;
+  return launch<BEVR_PREC_BF16X3>(*d, G, H, tap_ws, table_t, dkey_a, dkey_b, dkey_y, dkey_x, nullptr, 0,
+                                  (hipStream_t)stream TAP_DROP_ARGS);
+}
+#elif BEVR_TAP_X3
 // the split-mode instantiations: this translation unit is attn_tap_bwd_k_x3.hip, entered from bevr_attn_tap_bwd_k
 int bevr_tap_bwd_k_x3(const bevr_attn_desc& d, const void* G, const void* H, const void* tap_ws, const float* table_t,
                       float* dkey_a, float* dkey_b, float* dkey_y, float* dkey_x, hipStream_t st) {

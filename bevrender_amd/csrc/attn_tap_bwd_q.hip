@@ -15,8 +15,11 @@
 
 namespace {
 
-// (split mode: every operand twice -- the fat NB = 4 instantiation gets the registers of 2 waves per SIMD)
-constexpr int tap_bwd_q_waves(int prec, int nb) { return tap_split(prec) && nb == 4 ? 2 : 4; }
+// (split mode: every operand twice -- the fat NB = 4 instantiation gets the registers of 2 waves per SIMD; with the keep
+// mask NB = 2 spills 84 bytes a lane at the 128 registers of 4 waves: 3)
+constexpr int tap_bwd_q_waves(int prec, int nb) {
+  return tap_split(prec) && nb == 4 ? 2 : tap_split(prec) && BEVR_DROP && nb == 2 ? 3 : 4;
+}
 template <int PREC, int NB>
 __global__ __launch_bounds__(512, tap_bwd_q_waves(PREC, NB)) void attn_tap_bwd_q_kernel(
     bevr_attn_desc d, const char* __restrict__ G, const char* __restrict__ H, const char* __restrict__ tap_ws, const char* __restrict__ table_pair,
@@ -79,6 +82,7 @@ __global__ __launch_bounds__(512, tap_bwd_q_waves(PREC, NB)) void attn_tap_bwd_q
     hrow[nb] = bevr_drop_row(drop_seed, (uint32_t)ph, (uint32_t)(j * d.Sp + min(blk0 + nb, nblk - 1) * QB + li));
     const uint32_t c2 = *reinterpret_cast<const uint32_t*>(H + (mqv[nb] * TAP_SLOTS + TAP_CHI) * 2);
     ndel[nb] = TapHalf<PREC>::lo(c2) + TapHalf<PREC>::hi(c2);
+    if constexpr (tap_split(PREC)) ndel[nb] = tap_drop_ndel4(c2, *reinterpret_cast<const uint32_t*>(H + g_lo + (mqv[nb] * TAP_SLOTS + TAP_CHI) * 2));
   }
 #endif
   const int a_off = (kg < 2 ? L::OFF_TAPS : L::OFF_CELLS) + li * 32 + (kg & 1) * 16;     // + tile * 1024 + sub * 512
@@ -211,7 +215,23 @@ int launch(const bevr_attn_desc& d, const void* G, const void* H, const void* ta
 
 }  // namespace
 
-#if BEVR_TAP_X3
+#if BEVR_TAP_X3 && BEVR_DROP
+// the split-mode instantiations with the keep mask: this translation unit is attn_tap_bwd_q_x3_drop.hip, an entry point
+// of its own (the arguments and checks of bevr_attn_tap_bwd_q_dropout; BEVR_PREC_BF16X3 alone)
+extern "C" int bevr_attn_tap_bwd_q_x3_dropout(const bevr_attn_desc* d, const void* G, const void* H, const void* tap_ws,
+                                              const float* table_pair, float* dG, float* dtable, unsigned key0,
+                                              unsigned drop_thr, unsigned drop_seed, void* stream) {
+  if (drop_thr >= 65536u) return BEVR_E_SHAPE;
+  int rc = bevr_check_desc(d);
+  if (rc) return rc;
+  if (!G || !H || !tap_ws || !table_pair || !dG || !dtable) return BEVR_E_NULL;
+  if (d->groups != 1) return BEVR_E_SHAPE;
+  if (!bevr_aligned16(G) || !bevr_aligned16(H) || !bevr_aligned16(tap_ws) || !bevr_aligned16(table_pair) || !bevr_aligned16(dG))
+    return BEVR_E_ALIGN;
+  if (d->precision != BEVR_PREC_BF16X3) return BEVR_E_PRECISION;
+  return launch<BEVR_PREC_BF16X3>(*d, G, H, tap_ws, table_pair, dG, dtable, (hipStream_t)stream TAP_DROP_ARGS);
+}
+#elif BEVR_TAP_X3
 // the split-mode instantiations: this translation unit is attn_tap_bwd_q_x3.hip, entered from bevr_attn_tap_bwd_q
 int bevr_tap_bwd_q_x3(const bevr_attn_desc& d, const void* G, const void* H, const void* tap_ws, const float* table_pair,
                       float* dG, float* dtable, hipStream_t st) {

@@ -37,8 +37,11 @@ namespace {
 #else
 #define TAP_FWD_WAVES(NB_) ((NB_) == 4 ? 4 : 6)
 #endif
-// (split mode: every operand twice -- 4 waves per SIMD, the fat NB = 4 instantiation 2)
-constexpr int tap_fwd_waves(int prec, int nb) { return tap_split(prec) ? (nb == 4 ? 2 : 4) : TAP_FWD_WAVES(nb); }
+// (split mode: every operand twice -- 4 waves per SIMD, the fat NB = 4 instantiation 2; with the keep mask NB = 2 spills
+// ~100 bytes a lane at the 128 registers of 4 waves: 3)
+constexpr int tap_fwd_waves(int prec, int nb) {
+  return tap_split(prec) ? (nb == 4 ? 2 : BEVR_DROP && nb == 2 ? 3 : 4) : TAP_FWD_WAVES(nb);
+}
 template <int PREC, int NB, bool EXACT>
 __global__ __launch_bounds__(512, tap_fwd_waves(PREC, NB)) void attn_tap_fwd_kernel(
     bevr_attn_desc d, const char* __restrict__ G, const char* __restrict__ tap_ws,
@@ -257,7 +260,23 @@ int launch(const bevr_attn_desc& d, const void* G, const void* tap_ws, const flo
 
 }  // namespace
 
-#if BEVR_TAP_X3
+#if BEVR_TAP_X3 && BEVR_DROP
+// the split-mode instantiations with the keep mask: this translation unit is attn_tap_fwd_x3_drop.hip, an entry point of
+// its own (the arguments and checks of bevr_attn_tap_fwd_dropout; BEVR_PREC_BF16X3 alone)
+extern "C" int bevr_attn_tap_fwd_x3_dropout(const bevr_attn_desc* d, const void* G, const void* tap_ws,
+                                            const float* table_pair, float* mref, float* R, float* lsum, int* flags,
+                                            unsigned key0, unsigned drop_thr, unsigned drop_seed, void* stream) {
+  if (drop_thr >= 65536u) return BEVR_E_SHAPE;
+  if (!lsum) return BEVR_E_NULL;
+  int rc = bevr_check_desc(d);
+  if (rc) return rc;
+  if (!G || !tap_ws || !table_pair || !mref || !R || !flags) return BEVR_E_NULL;
+  if (d->groups != 1) return BEVR_E_SHAPE;
+  if (!bevr_aligned16(G) || !bevr_aligned16(tap_ws) || !bevr_aligned16(table_pair) || !bevr_aligned16(R)) return BEVR_E_ALIGN;
+  if (d->precision != BEVR_PREC_BF16X3) return BEVR_E_PRECISION;
+  return launch<BEVR_PREC_BF16X3>(*d, G, tap_ws, table_pair, mref, R, flags, (hipStream_t)stream BEVR_TAP_FWD_DROP_ARGS);
+}
+#elif BEVR_TAP_X3
 // the split-mode instantiations: this translation unit is attn_tap_fwd_x3.hip, entered from bevr_attn_tap_fwd
 int bevr_tap_fwd_x3(const bevr_attn_desc& d, const void* G, const void* tap_ws, const float* table_pair, float* mref,
                     float* R, int* flags, hipStream_t st) {

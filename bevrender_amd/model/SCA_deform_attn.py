@@ -149,7 +149,9 @@ class SCADeformableAttention(nn.Module):
         scattered keys are sampled and projected then.
         Attention dropout (training mode, attn_drop_rate > 0): the keep mask lives in the region kernels and in the tap
         kernels.  A split that runs on the tap kernels is kept (scattered keys: region dropout kernels, pinned keys: tap
-        dropout kernels, one mask); any other split is dropped and every key runs on the region kernels."""
+        dropout kernels, one mask); any other split is dropped and every key runs on the region kernels.  The split-bf16
+        mode keeps the split with a mask when BEVR_TAP_X3=1 and BEVR_TAP_X3_DROP=1 (ops.tap_supported(..., dropout=True)):
+        the pinned keys are then neither sampled nor projected in training with dropout either."""
         B, V, C, Hi, Wi = x.shape
         S = query.shape[-1]
         if V != self.n_views:
@@ -166,11 +168,13 @@ class SCADeformableAttention(nn.Module):
             # independently; the split is simply not used then
             cell_split = None
         # the K | V source, each condition once: the fused source where the kernel covers the call; the tap segment beside
-        # projected rows in the split-bf16 mode (no fused source there; no keep mask on that route); else projected rows
+        # projected rows in the split-bf16 mode (no fused source there; with a keep mask only when the split-mode tap
+        # dropout kernels are switched on: BEVR_TAP_X3_DROP, ops.tap_supported); else projected rows
         source = "kv"
         if x.is_cuda and ops.kv_source_supported(C, self.n_heads, g, self.precision):
             source = "kv_source"
-        elif x.is_cuda and pinned and cell_split is not None and drop is None and self.precision == ops._lib.PREC_BF16X3:
+        elif (x.is_cuda and pinned and cell_split is not None and self.precision == ops._lib.PREC_BF16X3
+              and (drop is None or ops.tap_supported(self.precision, g, dropout=True))):
             source = "tap_pix"
         tap_source = False
         if cell_split is not None:

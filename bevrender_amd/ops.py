@@ -546,6 +546,8 @@ class K:
     TAP_FWD, TAP_FWD_DROP = "bevr_attn_tap_fwd", "bevr_attn_tap_fwd_dropout"
     TAP_BWD_Q, TAP_BWD_Q_DROP = "bevr_attn_tap_bwd_q", "bevr_attn_tap_bwd_q_dropout"
     TAP_BWD_K, TAP_BWD_K_DROP = "bevr_attn_tap_bwd_k", "bevr_attn_tap_bwd_k_dropout"
+    TAP_FWD_X3_DROP, TAP_BWD_Q_X3_DROP = "bevr_attn_tap_fwd_x3_dropout", "bevr_attn_tap_bwd_q_x3_dropout"
+    TAP_BWD_K_X3_DROP = "bevr_attn_tap_bwd_k_x3_dropout"
 
 
 @dataclass(frozen=True)
@@ -591,11 +593,19 @@ def attention_route(precision: int, groups: int, S: int, Wt: int, N: int, cell_s
     tap_source=True with dropout and a split that would otherwise be kept.  Raises attention_core's routing ValueErrors.
     Reads the A/B switches itself (BEVR_KNORM, BEVR_MERGE_TAP) or through gather_supported, slab_supported,
     slab_rows_supported, tap_supported and kv_source_supported."""
+    # tap_pix with a keep mask (the split-bf16 mode behind BEVR_TAP_X3_DROP) follows kv_source's rules below, but where
+    # those would drop the split it has no projected rows of the pinned keys to fall back to: ValueError
+    # (the split mode alone: tap_pix is its route -- the 16-bit modes have the fused K | V source and keep refusing)
+    pix_drop = (dropout and source == "tap_pix" and precision == _lib.PREC_BF16X3
+                and tap_supported(precision, groups, dropout=True))
     if dropout:
-        if source == "tap_pix":
+        if source == "tap_pix" and not pix_drop:
             raise ValueError("tap_pix has no attention dropout: pass every key's projected rows and no tap segment")
-        if not (tap_source and cell_split is not None and source == "kv_source"
+        if not (tap_source and cell_split is not None and (source == "kv_source" or pix_drop)
                 and tap_supported(precision, groups, dropout=True) and 16 * ((S + 15) // 16) <= 448):
+            if pix_drop:
+                raise ValueError("tap_pix with attention dropout needs tap_source, cell_split and S <= 448: the pinned "
+                                 "keys have no projected rows to fall back to")
             cell_split, tap_source = None, None
     if source == "kv_source" and not kv_source_supported(C, heads, groups, precision):
         raise ValueError("kv_source needs a 16-bit operand mode, C % 16 == 0 and (C / groups) % 4 == 0")
@@ -605,6 +615,10 @@ def attention_route(precision: int, groups: int, S: int, Wt: int, N: int, cell_s
     if dropout and tap_source and tap_source != "pinned" and split < N:
         # no region segment beside it (split == 0): the route dropout always took for such a call
         if not (split > 0 and keys_in_tap_grid(split)):
+            if pix_drop:
+                raise ValueError("tap_pix with attention dropout: tap_source=True is checked, and the keys [cell_split, N) "
+                                 "do not all sample inside the tap grid beside a region segment (cell_split > 0); they "
+                                 "have no projected rows to fall back to")
             tap_source, split = None, N
     tap = bool(tap_source) and split < N
     if tap and (source == "kv" or not tap_supported(precision, groups, dropout=dropout) or 16 * ((S + 15) // 16) > 448):
@@ -638,7 +652,9 @@ def attention_route(precision: int, groups: int, S: int, Wt: int, N: int, cell_s
             else:
                 bwd_q = K.SLAB_BWD_Q if slab_supported(precision, S, Wt) else K.BWD_Q
             segs.append(KeySegment("region", 0, n_region, fwd, bwd_q, K.BWD_K))
-    if tap and dropout:
+    if tap and dropout and precision == _lib.PREC_BF16X3:
+        segs.append(KeySegment("tap", split, N, K.TAP_FWD_X3_DROP, K.TAP_BWD_Q_X3_DROP, K.TAP_BWD_K_X3_DROP))
+    elif tap and dropout:
         segs.append(KeySegment("tap", split, N, K.TAP_FWD_DROP, K.TAP_BWD_Q_DROP, K.TAP_BWD_K_DROP))
     elif tap:
         segs.append(KeySegment("tap", split, N, K.TAP_FWD, K.TAP_BWD_Q, K.TAP_BWD_K))
@@ -907,7 +923,8 @@ _RUN = {K.FWD: _fwd_tile, K.FWD_DROP: _fwd_tile, K.GATHER: _fwd_gather, K.GATHER
         K.SLAB_BWD_Q_ROWS: _bwd_q_slab_rows, K.SLAB_BWD_Q_X3: _bwd_q_slab,
         K.BWD_K: _bwd_k_tile, K.BWD_K_DROP: _bwd_k_tile, K.CELL_BWD_K: _bwd_k_cell,
         K.TAP_FWD: _tap_fwd, K.TAP_FWD_DROP: _tap_fwd, K.TAP_BWD_Q: _tap_bwd_q, K.TAP_BWD_Q_DROP: _tap_bwd_q,
-        K.TAP_BWD_K: _tap_bwd_k, K.TAP_BWD_K_DROP: _tap_bwd_k}
+        K.TAP_BWD_K: _tap_bwd_k, K.TAP_BWD_K_DROP: _tap_bwd_k,
+        K.TAP_FWD_X3_DROP: _tap_fwd, K.TAP_BWD_Q_X3_DROP: _tap_bwd_q, K.TAP_BWD_K_X3_DROP: _tap_bwd_k}
 
 
 def _run(name, o):
@@ -1166,7 +1183,10 @@ def attention_core(query: torch.Tensor, kproj: Optional[torch.Tensor], vproj: Op
     keys; the pinned keys [cell_split, N) are never sampled or projected: feat (B*views, Hi, Wi, C) (any strides; only its
     top-left 4 x 3 pixels are read) and Wkv / bkv give G = Q Kpix^T, Gb and O = Rn Vpix + bv as with kv_source.  The
     scattered segment runs through the region kernels in the precision's own layout and the two segments merge through
-    (O, LSE) in float.  No attention dropout on this route (ValueError): the caller keeps every key in `kv` then.
+    (O, LSE) in float.  Attention dropout on this route needs BEVR_TAP_X3_DROP=1 in the split-bf16 mode (tap_supported(...,
+    dropout=True): the region dropout kernels beside csrc/attn_tap_*_x3_drop.hip, one mask; a split the call cannot keep --
+    the checked tap_source=True contract fails, cell_split == 0, S > 448 -- is a ValueError, there being no projected rows of
+    the pinned keys to fall back to); otherwise ValueError: the caller keeps every key in `kv` then.
     attn_drop = (p, seed): dropout on the softmax weights (the reference's attn_drop, :402-409): a weight is kept with
     probability 1 - p (p rounded to 1/65536) and scaled by 1 / (1 - p); the mask is the function dropout_keep_mask of
     (seed, problem-head, query, key) that the forward and backward kernels share.  With tap_source (and a call the tap
@@ -1290,6 +1310,7 @@ TAP_HEADROOM_F16 = 8.0                            # fp16 operands: the weights 2
 
 
 TAP_X3_DEFAULT = "0"                              # BEVR_TAP_X3 when unset (tap_supported)
+TAP_X3_DROP_DEFAULT = "0"                         # BEVR_TAP_X3_DROP when unset (tap_supported(..., dropout=True))
 
 
 def tap_headroom(precision: int) -> float:
@@ -1323,8 +1344,9 @@ def _tap_operand(rows: torch.Tensor, x3: bool, ed=torch.bfloat16, dead: float = 
     """The G / H operand of the tap entry points from rows (..., 12) float, in either format: the 16-bit pack (..., 16) of
     dtype ed, or (x3) the split planes (2, ..., 16) bf16, plane 0 = hi = bf16(x), plane 1 = lo = bf16(x - hi).  Slots 0..11
     the rows, 12 and 13 the row offset (zero here: _set_offset), slot 14 = dead (-1e30 for G, the logit of a masked key),
-    slot 15 = slot15 (H with dropout: the kept mass's cotangent) or zero.  Returns (operand, the rows as the kernels
-    contract them: rounded, or hi + lo)."""
+    slot 15 = slot15 (H with dropout: the kept mass's cotangent; x3: in both planes, hi = bf16(x), lo = bf16(x - hi), as
+    the tap slots -- include/bevrender_hip.h, bevr_attn_tap_*_x3_dropout) or zero.  Returns (operand, the rows as the
+    kernels contract them: rounded, or hi + lo)."""
     rows = rows.float()
     shape = tuple(rows.shape[:-1]) + (TAP_SLOTS,)
     if x3:
@@ -1339,6 +1361,8 @@ def _tap_operand(rows: torch.Tensor, x3: bool, ed=torch.bfloat16, dead: float = 
     main[..., 14] = dead
     if slot15 is not None:
         main[..., 15] = slot15
+        if x3:
+            op[1][..., 15] = (slot15.float() - main[..., 15].float()).to(torch.bfloat16)
     return op, (op[0][..., :TAP_N].float() + op[1][..., :TAP_N].float() if x3 else op[..., :TAP_N].float())
 
 
@@ -1445,7 +1469,9 @@ class _TapAttn(torch.autograd.Function):
         delta = (Rn * Hv).sum(-1)
         if drop:
             # delta = sum_n P keep (w . H + H_one) = (Rn' . H + m' H_one) / D  (Rn', m' carry D, and so does H)
-            delta = (delta + mass[0] * H16[..., 15].float()) / Dk
+            # (H_one as the kernel contracts it: the rounded value; split mode: hi + lo)
+            h_one = H16[0][..., 15].float() + H16[1][..., 15].float() if x3 else H16[..., 15].float()
+            delta = (delta + mass[0] * h_one) / Dk
         if dLSE is not None:
             delta = delta - dLSE
         _set_offset(H16, -delta, x3)
@@ -1470,14 +1496,18 @@ class _TapAttn(torch.autograd.Function):
 def tap_supported(precision: int, groups: int, dropout: bool = False) -> bool:
     """The 16-bit operand modes (fp16 since round 5: headroom 8 and a power-of-two scale on the cotangents, see
     _TapAttn); BEVR_TAP=0 keeps the pinned keys on the cell kernels.  The split-bf16 mode (BEVR_PREC_BF16X3:
-    csrc/attn_tap_*_x3.hip, operands by tap_split_rows) without attention dropout (`dropout`: the call has a keep mask --
-    the tap dropout kernels are 16-bit only) when BEVR_TAP_X3=1; BEVR_TAP_X3=0 is that mode's earlier routing, every key
-    through the region / cell kernels.  The switch's default is TAP_X3_DEFAULT: off until the SCA block is MEASURED faster
-    on the new route (tools/ab_sca_x3.py)."""
+    csrc/attn_tap_*_x3.hip, operands by tap_split_rows) when BEVR_TAP_X3=1; BEVR_TAP_X3=0 is that mode's earlier routing,
+    every key through the region / cell kernels.  The switch's default is TAP_X3_DEFAULT: off until the SCA block is
+    MEASURED faster on the new route (tools/ab_sca_x3.py).  With attention dropout (`dropout`: the
+    call has a keep mask) the split mode needs a second switch on top of that one, BEVR_TAP_X3_DROP set and not "0"
+    (csrc/attn_tap_*_x3_drop.hip; default TAP_X3_DROP_DEFAULT: off); without it a call with a mask keeps every key on the
+    region dropout kernels, as before the split mode's tap kernels had a mask."""
     if groups != 1 or os.environ.get("BEVR_TAP", "1") == "0":
         return False
     if precision == _lib.PREC_BF16X3:
-        return not dropout and os.environ.get("BEVR_TAP_X3", TAP_X3_DEFAULT) != "0"
+        if os.environ.get("BEVR_TAP_X3", TAP_X3_DEFAULT) == "0":
+            return False
+        return not dropout or os.environ.get("BEVR_TAP_X3_DROP", TAP_X3_DROP_DEFAULT) != "0"
     return precision in (_lib.PREC_BF16, _lib.PREC_F16)
 
 

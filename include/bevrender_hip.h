@@ -66,7 +66,10 @@ extern "C" {
  *    bevr_attn_gather_fwd_x3 (the gather forward in BEVR_PREC_BF16X3, over a row range; bevr_attn_gather_fwd and
  *    bevr_attn_gather_fwd_rows keep returning BEVR_E_PRECISION for that mode);
  *    bevr_attn_slab_x3_ws_bytes / _slab_x3_prep / bevr_attn_slab_bwd_q_x3 (the slab query-side backward in
- *    BEVR_PREC_BF16X3, S <= 211; the 16-bit slab entry points keep returning BEVR_E_PRECISION for that mode). */
+ *    BEVR_PREC_BF16X3, S <= 211; the 16-bit slab entry points keep returning BEVR_E_PRECISION for that mode);
+ *    bevr_attn_tap_fwd_x3_dropout, bevr_attn_tap_bwd_q_x3_dropout, bevr_attn_tap_bwd_k_x3_dropout (attention dropout on
+ *    the tap entry points in BEVR_PREC_BF16X3; the three _dropout entry points keep returning BEVR_E_PRECISION for that
+ *    mode). */
 #define BEVR_ABI_VERSION 6
 
 enum {
@@ -303,7 +306,8 @@ int bevr_attn_cell_bwd_k(const bevr_attn_desc* d, const void* Q, const void* Qt,
  *       caller (scratch)
  *
  * TAP entry points in BEVR_PREC_BF16X3 (bevr_attn_tap_fwd, _bwd_q, _bwd_k; the _dropout entry points and BEVR_PREC_F32
- * return BEVR_E_PRECISION; bevr_attn_tap_prep and bevr_attn_tap_ws_bytes do not look at the precision).  The CALLER
+ * return BEVR_E_PRECISION -- the mode's keep mask has entry points of its own, bevr_attn_tap_*_x3_dropout below;
+ * bevr_attn_tap_prep and bevr_attn_tap_ws_bytes do not look at the precision).  The CALLER
  * splits G and H; the kernels split what they form themselves (tap and bias-cell weights, the table's chunk, P and dS)
  * and multiply in three bf16 products, lo hi + hi lo + hi hi (the logit contraction in all four), everything per pair in f32.  tap_ws, tables, mref, R,
  * flags, dG, dtable, dkey_* are as in the 16-bit modes (float).
@@ -392,6 +396,34 @@ int bevr_attn_tap_bwd_q_dropout(const bevr_attn_desc* d, const void* G, const vo
 int bevr_attn_tap_bwd_k_dropout(const bevr_attn_desc* d, const void* G, const void* H, const void* tap_ws,
                                 const float* table, float* dkey_a, float* dkey_b, float* dkey_y, float* dkey_x,
                                 unsigned key0, unsigned drop_thr, unsigned drop_seed, void* stream);
+
+/* Attention dropout on the TAP entry points in BEVR_PREC_BF16X3: the three _dropout entry points above in split
+ * arithmetic, entry points of their own.  Arguments, checks (in the same order) and semantics are those of
+ * bevr_attn_tap_*_dropout; the operands are those of "TAP entry points in BEVR_PREC_BF16X3"; every precision but
+ * BEVR_PREC_BF16X3 returns BEVR_E_PRECISION.  The operand words that differ from either:
+ *   G, H   the two bf16 planes [2][n_prob][heads][Mp][16] (hi, lo), slots 0..14 as in the split mode without dropout:
+ *          H slots 0..11 = D ln2 (dO_q . Vpix_t) as hi = bf16(x), lo = bf16(x - hi); slots 12, 13 the FOUR bf16 parts of
+ *          Hc = -ln2 delta_q, slot 12 = (hi p0, lo p1), slot 13 = (hi p2, lo p3), never dropped: a dropped pair keeps
+ *          p0 + p1 + p2 + p3, read by the kernel from both planes and summed smallest first; slot 14 zero
+ *   H slot 15   D ln2 (dO_q . bv), the cotangent of the kept mass (droppable): where the 16-bit dropout entry points take
+ *          ONE 16-bit value, here the slot carries a value in BOTH planes, hi = bf16(x) and lo = bf16(x - hi), against the
+ *          key side's w = 1 = (hi 1, lo 0): the product adds hi + lo (x to 2^-17 relative).  The caller's delta must use
+ *          that sum.  G slot 15 stays zero
+ *   lsum   [n_prob][heads][Mp] float WRITTEN: sum_n 2^(S[n][q] - mref[q]) over ALL keys, summed in float from the weights
+ *          before they are split; R (float) holds the kept weights, rows 12, 13, 15 the kept mass.  Columns are flagged on
+ *          lsum and recomputed with an online maximum, which rewrites R, lsum and mref of the flagged columns
+ *   key0, drop_thr, drop_seed   as above: the same hash at key0 + n', one keep decision per key over masked passes, so a
+ *          region segment (bevr_attn_*_dropout in BEVR_PREC_BF16X3) and a tap segment with key0 = split share ONE mask
+ * bevr_attn_tap_bwd_k_x3_dropout launches its main grid again for the pairs that miss the table window (no work list). */
+int bevr_attn_tap_fwd_x3_dropout(const bevr_attn_desc* d, const void* G, const void* tap_ws, const float* table_pair,
+                                 float* mref, float* R, float* lsum, int32_t* flags, unsigned key0, unsigned drop_thr,
+                                 unsigned drop_seed, void* stream);
+int bevr_attn_tap_bwd_q_x3_dropout(const bevr_attn_desc* d, const void* G, const void* H, const void* tap_ws,
+                                   const float* table_pair, float* dG, float* dtable, unsigned key0, unsigned drop_thr,
+                                   unsigned drop_seed, void* stream);
+int bevr_attn_tap_bwd_k_x3_dropout(const bevr_attn_desc* d, const void* G, const void* H, const void* tap_ws,
+                                   const float* table, float* dkey_a, float* dkey_b, float* dkey_y, float* dkey_x,
+                                   unsigned key0, unsigned drop_thr, unsigned drop_seed, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Gather kernel: the FORWARD of bevr_attn_fwd for SCATTERED keys with the relative-position bias on the matrix cores

@@ -8,8 +8,12 @@ on bevr_attn_gather_fwd_x3 (BEVR_GATHER_X3=1) against the region forward (BEVR_G
 --slab: the A/B of the split-mode slab backward -- both routes with BEVR_TAP_X3=1 and BEVR_GATHER_X3=0 (the defaults' forward),
 the scattered keys' query-side backward on bevr_attn_slab_bwd_q_x3 (BEVR_SLAB_X3=1) against the query-tile kernel
 (BEVR_SLAB_X3=0, the parent's routing).
+--drop P: the block in training mode with attention dropout at rate P -- both routes with BEVR_TAP_X3=1, the pinned keys
+on the split-mode tap dropout kernels (BEVR_TAP_X3_DROP=1: bevr_attn_tap_*_x3_dropout beside the region dropout kernels on
+the scattered keys) against the parent's routing (the switch unset: every key sampled, projected and sent through the
+region dropout kernels).  Each step draws its own mask seed; the routes' work does not depend on it.
 
-    B=8 ITERS=5 python tools/ab_sca_x3.py [--gather | --slab] [out.json]"""
+    B=8 ITERS=5 python tools/ab_sca_x3.py [--gather | --slab | --drop P] [out.json]"""
 import json
 import math
 import os
@@ -50,18 +54,28 @@ def main():
     T, K = ring_rig(V, img_w, img_h)
     proj = BEV2CameraProjector(imu_to_rgb={0: T}, K={0: K}, vehicle_type_code=0, img_width=img_w, img_height=img_h,
                                ori_img_width=img_w, ori_img_height=img_h, device=DEV)
+    argv = sys.argv[1:]
+    drop_p = 0.0
+    if "--drop" in argv:
+        k = argv.index("--drop")
+        drop_p = float(argv[k + 1])
+        del argv[k:k + 2]
     sca = SpatialCrossAttn({"X": 50, "Y": 50, "Z": 2}, proj, S, D, -1.0, C, h, 1, 1, 3, B, True, n_views=V,
-                           precision=_lib.PREC_BF16X3)
+                           attn_drop_rate=drop_p, precision=_lib.PREC_BF16X3)
     gen = torch.Generator().manual_seed(11)
     with torch.no_grad():
         for prm in sca.parameters():
             prm.copy_(torch.randn(prm.shape, generator=gen) * (0.3 if prm.dim() == 1 else 1.0 / math.sqrt(max(1, prm[0].numel()))))
-    sca = sca.to(DEV)
+    sca = sca.to(DEV)          # (a fresh module is in training mode: attn_drop_rate > 0 draws a mask per step)
     q = torch.randn(B, C, S, S, generator=gen).to(DEV).requires_grad_(True)
     x = torch.randn(B * V, C, Hi, Wi, generator=gen).to(DEV).requires_grad_(True)
     cot = torch.randn(B, C, S, S, generator=gen).to(DEV)
-    argv = [a for a in sys.argv[1:] if a not in ("--gather", "--slab")]
-    if "--slab" in sys.argv[1:]:
+    argv = [a for a in argv if a not in ("--gather", "--slab")]
+    if drop_p > 0.0:
+        # (the parent's route: the switch UNSET, as a process that never heard of it)
+        new, routes = "tap_x3_drop", (("tap_x3_drop", {"BEVR_TAP_X3": "1", "BEVR_TAP_X3_DROP": "1"}),
+                                      ("parent_route", {"BEVR_TAP_X3": "1", "BEVR_TAP_X3_DROP": None}))
+    elif "--slab" in sys.argv[1:]:
         new, routes = "slab_x3", (("slab_x3", {"BEVR_TAP_X3": "1", "BEVR_GATHER_X3": "0", "BEVR_SLAB_X3": "1"}),
                                   ("parent_route", {"BEVR_TAP_X3": "1", "BEVR_GATHER_X3": "0", "BEVR_SLAB_X3": "0"}))
     elif "--gather" in sys.argv[1:]:
@@ -73,7 +87,11 @@ def main():
     kernels = {}
 
     def step(tag, sw, record):
-        os.environ.update(sw)
+        for k_, v_ in sw.items():
+            if v_ is None:
+                os.environ.pop(k_, None)
+            else:
+                os.environ[k_] = v_
         for t in list(sca.parameters()) + [q, x]:
             t.grad = None
         if record:
@@ -95,7 +113,8 @@ def main():
                 times[tag].append(ms)
     for tag, sw in routes:       # one more step of each with per-kernel events
         step(tag, sw, True)
-    res = {"what": "SCA block forward + backward, bf16x3, S=200, 6 views, B=%d; routes alternating in one process" % B,
+    res = {"what": "SCA block forward + backward, bf16x3, S=200, 6 views, B=%d%s; routes alternating in one process"
+                   % (B, ", training mode, attention dropout p=%g" % drop_p if drop_p > 0.0 else ""),
            "routes": {tag: sw for tag, sw in routes}, "iters": iters}
     for tag, v in times.items():
         res[tag] = {"median_ms": round(statistics.median(v), 1), "min_ms": round(min(v), 1), "max_ms": round(max(v), 1),

@@ -17,8 +17,8 @@ import sys
 import torch
 
 DEV = "cuda"
-SWITCHES = ("BEVR_GATHER", "BEVR_SLAB", "BEVR_KNORM", "BEVR_MERGE_TAP", "BEVR_TAP", "BEVR_TAP_X3", "BEVR_FUSED_KV", "BEVR_CELL",
-            "BEVR_BWDK_LIST")
+SWITCHES = ("BEVR_GATHER", "BEVR_SLAB", "BEVR_KNORM", "BEVR_MERGE_TAP", "BEVR_TAP", "BEVR_TAP_X3", "BEVR_TAP_X3_DROP", "BEVR_FUSED_KV",
+            "BEVR_CELL", "BEVR_BWDK_LIST")
 
 
 def core_case(ops, prec, seed, S=16, D=3, N=None, h=2, c=16, V=2, B=1, g=1, split=None, source="kv", tap_source=None,
