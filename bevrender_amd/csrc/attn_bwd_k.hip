@@ -23,6 +23,7 @@
 //    query tiles) items, so no workgroup is launched to find out that it has nothing to do and the few misfit blocks
 //    are spread over the whole device.
 #include "attn_kstage.h"
+#include "attn_host.h"
 
 #include "bevr_prof.h"
 
@@ -31,8 +32,7 @@ BEVR_PROF_DEFINE(bwd_k, 16)   // window kernel, waves 0 and 11, 8 slots each: ph
 namespace {
 
 constexpr int KEYS_WG = 384;    // keys per workgroup, both kernels: the unit of ownership
-// work list of the blocks the window kernel hands over: int [0] = count, [LIST_HEAD + i] = ph * n_kb + kblk
-constexpr int LIST_HEAD = 4;
+// work list of the blocks the window kernel hands over (attn_host.h): unit i = ph * n_kb + kblk
 
 // bounding box of a key block in table coordinates (padded keys excluded)
 struct KBox { int amin, amax; float bmin, bmax; };
@@ -728,16 +728,6 @@ __global__ __launch_bounds__(TG) void attn_bwd_k_gather_list_kernel(
   }
 }
 
-// workgroups the device holds at once: compute units x the kernel's residency (asked once per kernel)
-template <typename Kern>
-int resident_workgroups(Kern kern, int threads) {
-  int dev = 0, cus = 0, per_cu = 0;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, threads, 0) != hipSuccess)
-    return 0;
-  return cus * per_cu;
-}
 #endif
 
 // slow_list: null -- the full-grid gather launch; else the work list (cleared here, filled by the window launch) and the
@@ -754,28 +744,29 @@ int launch(const bevr_attn_desc& d, const void* Q, const void* Qt, const void* K
   if (slow_list) {
     // the list kernel counts items (listed block, range) in an int
     if ((long long)n_ph * n_kb * (d.S * (d.Sp / 32) / GATHER_MIN_TILES + 1) > 0x7fffffffLL) return BEVR_E_SHAPE;
-    rc = (int)hipMemsetAsync(slow_list, 0, LIST_HEAD * sizeof(int), st);
+    rc = bevr_list_clear(slow_list, st);
     if (rc) return rc;
   }
-  hipLaunchKernelGGL((attn_bwd_k_win_kernel<PREC>), dim3(grid), dim3(TW), 0, st, d, (const char*)Q, (const char*)Qt,
-                     (const char*)K, (const char*)V, key_a, key_b, (const char*)table_pair, (const char*)dO,
-                     (const char*)dOt, LSE, delta, gs, dK, dV, dka, dkb, slow_list BEVR_DROP_ARGS);
+  // the operands the three kernels share; each adds its own tail
+#define BEVR_BWD_K_ARGS                                                                                               \
+  d, (const char*)Q, (const char*)Qt, (const char*)K, (const char*)V, key_a, key_b, (const char*)table_pair,          \
+      (const char*)dO, (const char*)dOt, LSE, delta, gs, dK, dV, dka, dkb
+  hipLaunchKernelGGL((attn_bwd_k_win_kernel<PREC>), dim3(grid), dim3(TW), 0, st, BEVR_BWD_K_ARGS,
+                     slow_list BEVR_DROP_ARGS);
   rc = (int)hipGetLastError();
   if (rc) return rc;
 #if !BEVR_DROP
   if (slow_list) {
-    static const int resident = resident_workgroups(attn_bwd_k_gather_list_kernel<PREC>, TG);
-    if (resident <= 0) return (int)hipErrorInvalidDevice;
-    const int n_wg = max_wg > 0 && max_wg < resident ? max_wg : resident;
-    hipLaunchKernelGGL((attn_bwd_k_gather_list_kernel<PREC>), dim3(n_wg), dim3(TG), 0, st, d, (const char*)Q,
-                       (const char*)Qt, (const char*)K, (const char*)V, key_a, key_b, (const char*)table_pair,
-                       (const char*)dO, (const char*)dOt, LSE, delta, gs, dK, dV, dka, dkb, (const int*)slow_list);
+    const int n_wg = bevr_list_workgroups<&attn_bwd_k_gather_list_kernel<PREC>>(max_wg, TG, 0);
+    if (n_wg <= 0) return (int)hipErrorInvalidDevice;
+    hipLaunchKernelGGL((attn_bwd_k_gather_list_kernel<PREC>), dim3(n_wg), dim3(TG), 0, st, BEVR_BWD_K_ARGS,
+                       (const int*)slow_list);
     return (int)hipGetLastError();
   }
 #endif
-  hipLaunchKernelGGL((attn_bwd_k_gather_kernel<PREC>), dim3(grid * GSPLIT), dim3(TG), 0, st, d, (const char*)Q,
-                     (const char*)Qt, (const char*)K, (const char*)V, key_a, key_b, (const char*)table_pair,
-                     (const char*)dO, (const char*)dOt, LSE, delta, gs, dK, dV, dka, dkb BEVR_DROP_ARGS);
+  hipLaunchKernelGGL((attn_bwd_k_gather_kernel<PREC>), dim3(grid * GSPLIT), dim3(TG), 0, st,
+                     BEVR_BWD_K_ARGS BEVR_DROP_ARGS);
+#undef BEVR_BWD_K_ARGS
   return (int)hipGetLastError();
 }
 
@@ -791,18 +782,10 @@ int run(const bevr_attn_desc* d, const void* Q, const void* Qt, const void* K, c
   if (!bevr_aligned16(Q) || !bevr_aligned16(Qt) || !bevr_aligned16(K) || !bevr_aligned16(V) || !bevr_aligned16(dO) ||
       !bevr_aligned16(dOt) || !bevr_aligned16(dK) || !bevr_aligned16(dV) || !bevr_aligned16(table_pair))
     return BEVR_E_ALIGN;
-  hipStream_t st = (hipStream_t)stream;
-  if (d->precision == BEVR_PREC_BF16)
-    return launch<BEVR_PREC_BF16>(*d, Q, Qt, K, V, key_a, key_b, table_pair, dO, dOt, LSE, delta, grad_scale, dK, dV,
-                                  dkey_a, dkey_b, slow_list, max_wg, st BEVR_DROP_ARGS);
-  if (d->precision == BEVR_PREC_F16)
-    return launch<BEVR_PREC_F16>(*d, Q, Qt, K, V, key_a, key_b, table_pair, dO, dOt, LSE, delta, grad_scale, dK, dV,
-                                 dkey_a, dkey_b, slow_list, max_wg, st BEVR_DROP_ARGS);
-  if (d->precision == BEVR_PREC_BF16X3)
-    return launch<BEVR_PREC_BF16X3>(*d, Q, Qt, K, V, key_a, key_b, table_pair, dO, dOt, LSE, delta, grad_scale, dK, dV,
-                                    dkey_a, dkey_b, slow_list, max_wg, st BEVR_DROP_ARGS);
-  return launch<BEVR_PREC_F32>(*d, Q, Qt, K, V, key_a, key_b, table_pair, dO, dOt, LSE, delta, grad_scale, dK, dV,
-                               dkey_a, dkey_b, slow_list, max_wg, st BEVR_DROP_ARGS);
+  return bevr_for_precision<BEVR_PREC_BF16, BEVR_PREC_F16, BEVR_PREC_BF16X3, BEVR_PREC_F32>(d->precision, [&](auto P) {
+    return launch<P()>(*d, Q, Qt, K, V, key_a, key_b, table_pair, dO, dOt, LSE, delta, grad_scale, dK, dV, dkey_a, dkey_b,
+                       slow_list, max_wg, (hipStream_t)stream BEVR_DROP_ARGS);
+  });
 }
 
 }  // namespace
@@ -829,7 +812,7 @@ extern "C" int bevr_attn_bwd_k(const bevr_attn_desc* d, const void* Q, const voi
 extern "C" size_t bevr_attn_bwd_k_ws_bytes(const bevr_attn_desc* d) {
   if (bevr_check_desc(d)) return 0;
   const size_t n_kb = ((size_t)d->Np + KEYS_WG - 1) / KEYS_WG;
-  return (LIST_HEAD + (size_t)d->n_prob * d->heads * n_kb) * sizeof(int);
+  return bevr_list_bytes((size_t)d->n_prob * d->heads * n_kb);
 }
 
 extern "C" int bevr_attn_bwd_k_ws(const bevr_attn_desc* d, const void* Q, const void* Qt, const void* K, const void* V,

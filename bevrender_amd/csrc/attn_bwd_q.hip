@@ -23,6 +23,7 @@
 // Gradient semantics: see include/bevrender_hip.h (log2-domain inputs as handed in).
 #include <type_traits>
 #include "attn_tile.h"
+#include "attn_host.h"
 
 #include "bevr_prof.h"
 
@@ -642,20 +643,9 @@ int launch(const bevr_attn_desc& d, const void* Q, const void* K, const void* Kt
   return (int)hipGetLastError();
 }
 
-}  // namespace
-
-#if BEVR_DROP
-extern "C" int bevr_attn_bwd_q_dropout(const bevr_attn_desc* d, const void* Q, const void* K, const void* Kt, const void* V,
-                                       const void* key_ws, const float* table_pair, const void* dO,
-                                       const float* LSE, const float* delta, const float* grad_scale, float* dQ,
-                                       float* dtable, unsigned drop_thr, unsigned drop_seed, void* stream) {
-  if (drop_thr >= 65536u) return BEVR_E_SHAPE;
-#else
-extern "C" int bevr_attn_bwd_q(const bevr_attn_desc* d, const void* Q, const void* K, const void* Kt, const void* V,
-                               const void* key_ws, const float* table_pair, const void* dO,
-                               const float* LSE, const float* delta, const float* grad_scale, float* dQ,
-                               float* dtable, void* stream) {
-#endif
+int run(const bevr_attn_desc* d, const void* Q, const void* K, const void* Kt, const void* V, const void* key_ws,
+        const float* table_pair, const void* dO, const float* LSE, const float* delta, const float* grad_scale,
+        float* dQ, float* dtable, void* stream BEVR_DROP_PARAMS) {
   int rc = bevr_check_desc(d);
   if (rc) return rc;
   if (!Q || !K || !Kt || !V || !key_ws || !table_pair || !dO || !LSE || !delta || !grad_scale || !dQ ||
@@ -664,13 +654,27 @@ extern "C" int bevr_attn_bwd_q(const bevr_attn_desc* d, const void* Q, const voi
   if (!bevr_aligned16(Q) || !bevr_aligned16(K) || !bevr_aligned16(Kt) || !bevr_aligned16(V) || !bevr_aligned16(dO) ||
       !bevr_aligned16(dQ) || !bevr_aligned16(table_pair))
     return BEVR_E_ALIGN;
-  hipStream_t st = (hipStream_t)stream;
-  if (d->precision == BEVR_PREC_BF16)
-    return launch<BEVR_PREC_BF16>(*d, Q, K, Kt, V, key_ws, table_pair, dO, LSE, delta, grad_scale, dQ, dtable,
-                                  st BEVR_DROP_ARGS);
-  if (d->precision == BEVR_PREC_F16)
-    return launch<BEVR_PREC_F16>(*d, Q, K, Kt, V, key_ws, table_pair, dO, LSE, delta, grad_scale, dQ, dtable, st BEVR_DROP_ARGS);
-  if (d->precision == BEVR_PREC_BF16X3)
-    return launch<BEVR_PREC_BF16X3>(*d, Q, K, Kt, V, key_ws, table_pair, dO, LSE, delta, grad_scale, dQ, dtable, st BEVR_DROP_ARGS);
-  return launch<BEVR_PREC_F32>(*d, Q, K, Kt, V, key_ws, table_pair, dO, LSE, delta, grad_scale, dQ, dtable, st BEVR_DROP_ARGS);
+  return bevr_for_precision<BEVR_PREC_BF16, BEVR_PREC_F16, BEVR_PREC_BF16X3, BEVR_PREC_F32>(d->precision, [&](auto P) {
+    return launch<P()>(*d, Q, K, Kt, V, key_ws, table_pair, dO, LSE, delta, grad_scale, dQ, dtable,
+                       (hipStream_t)stream BEVR_DROP_ARGS);
+  });
 }
+
+}  // namespace
+
+#if BEVR_DROP
+extern "C" int bevr_attn_bwd_q_dropout(const bevr_attn_desc* d, const void* Q, const void* K, const void* Kt, const void* V,
+                                       const void* key_ws, const float* table_pair, const void* dO,
+                                       const float* LSE, const float* delta, const float* grad_scale, float* dQ,
+                                       float* dtable, unsigned drop_thr, unsigned drop_seed, void* stream) {
+  if (drop_thr >= 65536u) return BEVR_E_SHAPE;
+  return run(d, Q, K, Kt, V, key_ws, table_pair, dO, LSE, delta, grad_scale, dQ, dtable, stream, drop_thr, drop_seed);
+}
+#else
+extern "C" int bevr_attn_bwd_q(const bevr_attn_desc* d, const void* Q, const void* K, const void* Kt, const void* V,
+                               const void* key_ws, const float* table_pair, const void* dO,
+                               const float* LSE, const float* delta, const float* grad_scale, float* dQ,
+                               float* dtable, void* stream) {
+  return run(d, Q, K, Kt, V, key_ws, table_pair, dO, LSE, delta, grad_scale, dQ, dtable, stream);
+}
+#endif

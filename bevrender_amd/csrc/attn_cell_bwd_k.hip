@@ -18,6 +18,7 @@
 #include <type_traits>
 #include "attn_cell.h"
 #include "attn_kstage.h"
+#include "attn_host.h"
 
 
 namespace {
@@ -386,14 +387,15 @@ int launch(const bevr_attn_desc& d, const void* Q, const void* Qt, const void* K
   const int n_kb = (d.Np + KEYS_WGC - 1) / KEYS_WGC;
   const int n_ph = d.n_prob * d.heads;
   const int grid = ((n_ph + 7) / 8) * 8 * n_kb;
-  hipLaunchKernelGGL((attn_cell_bwd_k_kernel<PREC, false>), dim3(grid), dim3(TWC), 0, st, d, (const char*)Q,
-                     (const char*)Qt, (const char*)K, (const char*)V, (const char*)key_ws, (const char*)table_pair,
-                     (const char*)dO, (const char*)dOt, LSE, delta, gs, dK, dV, dka, dkb);
+#define BEVR_CELL_LAUNCH(SLOW_)                                                                                        \
+  hipLaunchKernelGGL((attn_cell_bwd_k_kernel<PREC, SLOW_>), dim3(grid), dim3(TWC), 0, st, d, (const char*)Q,          \
+                     (const char*)Qt, (const char*)K, (const char*)V, (const char*)key_ws, (const char*)table_pair,   \
+                     (const char*)dO, (const char*)dOt, LSE, delta, gs, dK, dV, dka, dkb)
+  BEVR_CELL_LAUNCH(false);
   int rc = (int)hipGetLastError();
   if (rc) return rc;
-  hipLaunchKernelGGL((attn_cell_bwd_k_kernel<PREC, true>), dim3(grid), dim3(TWC), 0, st, d, (const char*)Q,
-                     (const char*)Qt, (const char*)K, (const char*)V, (const char*)key_ws, (const char*)table_pair,
-                     (const char*)dO, (const char*)dOt, LSE, delta, gs, dK, dV, dka, dkb);
+  BEVR_CELL_LAUNCH(true);
+#undef BEVR_CELL_LAUNCH
   return (int)hipGetLastError();
 }
 
@@ -413,16 +415,8 @@ extern "C" int bevr_attn_cell_bwd_k(const bevr_attn_desc* d, const void* Q, cons
       !bevr_aligned16(dOt) || !bevr_aligned16(dK) || !bevr_aligned16(dV) || !bevr_aligned16(table_pair) ||
       !bevr_aligned16(key_ws))
     return BEVR_E_ALIGN;
-  hipStream_t st = (hipStream_t)stream;
-  if (d->precision == BEVR_PREC_BF16)
-    return launch<BEVR_PREC_BF16>(*d, Q, Qt, K, V, key_ws, table_pair, dO, dOt, LSE, delta, grad_scale, dK, dV, dkey_a,
-                                  dkey_b, st);
-  if (d->precision == BEVR_PREC_F16)
-    return launch<BEVR_PREC_F16>(*d, Q, Qt, K, V, key_ws, table_pair, dO, dOt, LSE, delta, grad_scale, dK, dV, dkey_a,
-                                 dkey_b, st);
-  if (d->precision == BEVR_PREC_BF16X3)
-    return launch<BEVR_PREC_BF16X3>(*d, Q, Qt, K, V, key_ws, table_pair, dO, dOt, LSE, delta, grad_scale, dK, dV, dkey_a,
-                               dkey_b, st);
-  return launch<BEVR_PREC_F32>(*d, Q, Qt, K, V, key_ws, table_pair, dO, dOt, LSE, delta, grad_scale, dK, dV, dkey_a,
-                               dkey_b, st);
+  return bevr_for_precision<BEVR_PREC_BF16, BEVR_PREC_F16, BEVR_PREC_BF16X3, BEVR_PREC_F32>(d->precision, [&](auto P) {
+    return launch<P()>(*d, Q, Qt, K, V, key_ws, table_pair, dO, dOt, LSE, delta, grad_scale, dK, dV, dkey_a, dkey_b,
+                       (hipStream_t)stream);
+  });
 }

@@ -18,6 +18,7 @@
 // dQ and dtable are ACCUMULATED: the region kernel (attn_bwd_q.hip) may have written the other key segment's share.
 #include <type_traits>
 #include "attn_cell.h"
+#include "attn_host.h"
 
 namespace {
 
@@ -496,24 +497,17 @@ int launch(const bevr_attn_desc& d, const void* Q, const void* K, const void* Kt
   const size_t lds = 2 * L::BUF + (size_t)n_fast * L::QSLOT;
   const size_t lds_slow = 2 * L::BUF + (size_t)n_rb * L::QSLOT + (size_t)(d.Np / 32) * 4;
   if (lds > 160 * 1024 || lds_slow > 160 * 1024) return BEVR_E_SHAPE;
-  if (!is16(PREC) && 64 * n_fast <= 512)
-    hipLaunchKernelGGL((attn_cell_bwd_q_kernel<PREC, false, (is16(PREC) ? 1024 : 512)>), dim3(grid), dim3(64 * n_fast), lds, st,
-                       d, (const char*)Q, (const char*)K, (const char*)Kt, (const char*)V, (const char*)key_ws,
-                       (const char*)table_pair, (const char*)dO, LSE, delta, gs, dQ, dtable);
-  else
-    hipLaunchKernelGGL((attn_cell_bwd_q_kernel<PREC, false, 1024>), dim3(grid), dim3(64 * n_fast), lds, st, d, (const char*)Q,
-                       (const char*)K, (const char*)Kt, (const char*)V, (const char*)key_ws, (const char*)table_pair,
-                       (const char*)dO, LSE, delta, gs, dQ, dtable);
+#define BEVR_CELL_LAUNCH(SLOW_, MAXT_, WAVES_, LDS_)                                                                    \
+  hipLaunchKernelGGL((attn_cell_bwd_q_kernel<PREC, SLOW_, MAXT_>), dim3(grid), dim3(64 * (WAVES_)), LDS_, st, d,       \
+                     (const char*)Q, (const char*)K, (const char*)Kt, (const char*)V, (const char*)key_ws,              \
+                     (const char*)table_pair, (const char*)dO, LSE, delta, gs, dQ, dtable)
+  if (!is16(PREC) && 64 * n_fast <= 512) BEVR_CELL_LAUNCH(false, (is16(PREC) ? 1024 : 512), n_fast, lds);
+  else BEVR_CELL_LAUNCH(false, 1024, n_fast, lds);
   int rc = (int)hipGetLastError();
   if (rc) return rc;
-  if (!is16(PREC) && 64 * n_rb <= 512)
-    hipLaunchKernelGGL((attn_cell_bwd_q_kernel<PREC, true, (is16(PREC) ? 1024 : 512)>), dim3(grid), dim3(64 * n_rb), lds_slow, st,
-                       d, (const char*)Q, (const char*)K, (const char*)Kt, (const char*)V, (const char*)key_ws,
-                       (const char*)table_pair, (const char*)dO, LSE, delta, gs, dQ, dtable);
-  else
-    hipLaunchKernelGGL((attn_cell_bwd_q_kernel<PREC, true, 1024>), dim3(grid), dim3(64 * n_rb), lds_slow, st, d,
-                       (const char*)Q, (const char*)K, (const char*)Kt, (const char*)V, (const char*)key_ws,
-                       (const char*)table_pair, (const char*)dO, LSE, delta, gs, dQ, dtable);
+  if (!is16(PREC) && 64 * n_rb <= 512) BEVR_CELL_LAUNCH(true, (is16(PREC) ? 1024 : 512), n_rb, lds_slow);
+  else BEVR_CELL_LAUNCH(true, 1024, n_rb, lds_slow);
+#undef BEVR_CELL_LAUNCH
   return (int)hipGetLastError();
 }
 
@@ -532,12 +526,7 @@ extern "C" int bevr_attn_cell_bwd_q(const bevr_attn_desc* d, const void* Q, cons
   if (!bevr_aligned16(Q) || !bevr_aligned16(K) || !bevr_aligned16(Kt) || !bevr_aligned16(V) || !bevr_aligned16(dO) ||
       !bevr_aligned16(dQ) || !bevr_aligned16(table_pair) || !bevr_aligned16(key_ws))
     return BEVR_E_ALIGN;
-  hipStream_t st = (hipStream_t)stream;
-  if (d->precision == BEVR_PREC_BF16)
-    return launch<BEVR_PREC_BF16>(*d, Q, K, Kt, V, key_ws, table_pair, dO, LSE, delta, grad_scale, dQ, dtable, st);
-  if (d->precision == BEVR_PREC_F16)
-    return launch<BEVR_PREC_F16>(*d, Q, K, Kt, V, key_ws, table_pair, dO, LSE, delta, grad_scale, dQ, dtable, st);
-  if (d->precision == BEVR_PREC_BF16X3)
-    return launch<BEVR_PREC_BF16X3>(*d, Q, K, Kt, V, key_ws, table_pair, dO, LSE, delta, grad_scale, dQ, dtable, st);
-  return launch<BEVR_PREC_F32>(*d, Q, K, Kt, V, key_ws, table_pair, dO, LSE, delta, grad_scale, dQ, dtable, st);
+  return bevr_for_precision<BEVR_PREC_BF16, BEVR_PREC_F16, BEVR_PREC_BF16X3, BEVR_PREC_F32>(d->precision, [&](auto P) {
+    return launch<P()>(*d, Q, K, Kt, V, key_ws, table_pair, dO, LSE, delta, grad_scale, dQ, dtable, (hipStream_t)stream);
+  });
 }

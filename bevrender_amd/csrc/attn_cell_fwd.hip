@@ -28,6 +28,7 @@
 // softmax over both segments; with O_in == NULL it starts empty.
 #include <type_traits>
 #include "attn_cell.h"
+#include "attn_host.h"
 
 
 namespace {
@@ -654,24 +655,20 @@ int launch(const bevr_attn_desc& d, const void* Q, const void* K, const void* Vt
   // both passes' LDS before anything is launched: the fast pass updates (O, LSE) in place
   const size_t lds_slow = 2 * L::BUF + (size_t)n_rb * L::QSLOT + (size_t)(d.Np / 32) * 4;
   if (lds > 160 * 1024 || lds_slow > 160 * 1024) return BEVR_E_SHAPE;
-  if (!is16(PREC) && 64 * n_fast <= 512)
-    hipLaunchKernelGGL((attn_cell_fwd_kernel<PREC, false, (is16(PREC) ? 1024 : 512)>), dim3(grid), dim3(64 * n_fast), lds, st,
-                       d, (const char*)Q, (const char*)K, (const char*)Vt, (const char*)key_ws, (const char*)table_pair,
-                       O_in, LSE_in, O, LSE);
-  else
-    hipLaunchKernelGGL((attn_cell_fwd_kernel<PREC, false, 1024>), dim3(grid), dim3(64 * n_fast), lds, st, d, (const char*)Q,
-                       (const char*)K, (const char*)Vt, (const char*)key_ws, (const char*)table_pair, O_in, LSE_in, O, LSE);
+  // (O_IN_, LSE_IN_): the state the pass continues from
+#define BEVR_CELL_LAUNCH(SLOW_, MAXT_, WAVES_, LDS_, O_IN_, LSE_IN_)                                                   \
+  hipLaunchKernelGGL((attn_cell_fwd_kernel<PREC, SLOW_, MAXT_>), dim3(grid), dim3(64 * (WAVES_)), LDS_, st, d,        \
+                     (const char*)Q, (const char*)K, (const char*)Vt, (const char*)key_ws, (const char*)table_pair,   \
+                     O_IN_, LSE_IN_, O, LSE)
+  if (!is16(PREC) && 64 * n_fast <= 512) BEVR_CELL_LAUNCH(false, (is16(PREC) ? 1024 : 512), n_fast, lds, O_in, LSE_in);
+  else BEVR_CELL_LAUNCH(false, 1024, n_fast, lds, O_in, LSE_in);
   int rc = (int)hipGetLastError();
   if (rc) return rc;
   // slow pass, in place: continues from the fast pass's state; no producer; its LDS also holds the list of slow tiles
   if (!is16(PREC) && 64 * n_rb <= 512)
-    hipLaunchKernelGGL((attn_cell_fwd_kernel<PREC, true, (is16(PREC) ? 1024 : 512)>), dim3(grid), dim3(64 * n_rb), lds_slow, st,
-                       d, (const char*)Q, (const char*)K, (const char*)Vt, (const char*)key_ws, (const char*)table_pair,
-                       (const float*)O, (const float*)LSE, O, LSE);
-  else
-    hipLaunchKernelGGL((attn_cell_fwd_kernel<PREC, true, 1024>), dim3(grid), dim3(64 * n_rb), lds_slow, st, d,
-                       (const char*)Q, (const char*)K, (const char*)Vt, (const char*)key_ws, (const char*)table_pair,
-                       (const float*)O, (const float*)LSE, O, LSE);
+    BEVR_CELL_LAUNCH(true, (is16(PREC) ? 1024 : 512), n_rb, lds_slow, (const float*)O, (const float*)LSE);
+  else BEVR_CELL_LAUNCH(true, 1024, n_rb, lds_slow, (const float*)O, (const float*)LSE);
+#undef BEVR_CELL_LAUNCH
   return (int)hipGetLastError();
 }
 
@@ -687,12 +684,7 @@ extern "C" int bevr_attn_cell_fwd(const bevr_attn_desc* d, const void* Q, const 
   if (!bevr_aligned16(Q) || !bevr_aligned16(K) || !bevr_aligned16(Vt) || !bevr_aligned16(O) ||
       !bevr_aligned16(table_pair) || !bevr_aligned16(key_ws) || (O_in && !bevr_aligned16(O_in)))
     return BEVR_E_ALIGN;
-  hipStream_t st = (hipStream_t)stream;
-  if (d->precision == BEVR_PREC_BF16)
-    return launch<BEVR_PREC_BF16>(*d, Q, K, Vt, key_ws, table_pair, O_in, LSE_in, O, LSE, st);
-  if (d->precision == BEVR_PREC_F16)
-    return launch<BEVR_PREC_F16>(*d, Q, K, Vt, key_ws, table_pair, O_in, LSE_in, O, LSE, st);
-  if (d->precision == BEVR_PREC_BF16X3)
-    return launch<BEVR_PREC_BF16X3>(*d, Q, K, Vt, key_ws, table_pair, O_in, LSE_in, O, LSE, st);
-  return launch<BEVR_PREC_F32>(*d, Q, K, Vt, key_ws, table_pair, O_in, LSE_in, O, LSE, st);
+  return bevr_for_precision<BEVR_PREC_BF16, BEVR_PREC_F16, BEVR_PREC_BF16X3, BEVR_PREC_F32>(d->precision, [&](auto P) {
+    return launch<P()>(*d, Q, K, Vt, key_ws, table_pair, O_in, LSE_in, O, LSE, (hipStream_t)stream);
+  });
 }

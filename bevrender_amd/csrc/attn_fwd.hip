@@ -20,6 +20,7 @@
 // blockIdx is remapped so that all query tiles of one (problem, head) run on one XCD and stream the same K/V
 // through that XCD's L2.
 #include "attn_tile.h"
+#include "attn_host.h"
 
 #include "bevr_prof.h"
 
@@ -434,6 +435,19 @@ int launch_fwd(const bevr_attn_desc& d, const void* Q, const void* K, const void
   return (int)hipGetLastError();
 }
 
+int run(const bevr_attn_desc* d, const void* Q, const void* K, const void* Vt, const void* key_ws,
+        const float* table_pair, float* O, float* LSE, void* stream BEVR_DROP_PARAMS) {
+  int rc = bevr_check_desc(d);
+  if (rc) return rc;
+  if (!Q || !K || !Vt || !key_ws || !table_pair || !O || !LSE) return BEVR_E_NULL;
+  if (!bevr_aligned16(Q) || !bevr_aligned16(K) || !bevr_aligned16(Vt) || !bevr_aligned16(O) ||
+      !bevr_aligned16(table_pair))
+    return BEVR_E_ALIGN;
+  return bevr_for_precision<BEVR_PREC_BF16, BEVR_PREC_F16, BEVR_PREC_BF16X3, BEVR_PREC_F32>(d->precision, [&](auto P) {
+    return launch_fwd<P()>(*d, Q, K, Vt, key_ws, table_pair, O, LSE, (hipStream_t)stream BEVR_DROP_ARGS);
+  });
+}
+
 }  // namespace
 
 #if BEVR_DROP
@@ -441,21 +455,12 @@ extern "C" int bevr_attn_fwd_dropout(const bevr_attn_desc* d, const void* Q, con
                                      const void* key_ws, const float* table_pair, float* O,
                                      float* LSE, unsigned drop_thr, unsigned drop_seed, void* stream) {
   if (drop_thr >= 65536u) return BEVR_E_SHAPE;
+  return run(d, Q, K, Vt, key_ws, table_pair, O, LSE, stream, drop_thr, drop_seed);
+}
 #else
 extern "C" int bevr_attn_fwd(const bevr_attn_desc* d, const void* Q, const void* K, const void* Vt,
                              const void* key_ws, const float* table_pair, float* O,
                              float* LSE, void* stream) {
-#endif
-  int rc = bevr_check_desc(d);
-  if (rc) return rc;
-  if (!Q || !K || !Vt || !key_ws || !table_pair || !O || !LSE) return BEVR_E_NULL;
-  if (!bevr_aligned16(Q) || !bevr_aligned16(K) || !bevr_aligned16(Vt) || !bevr_aligned16(O) ||
-      !bevr_aligned16(table_pair))
-    return BEVR_E_ALIGN;
-  hipStream_t st = (hipStream_t)stream;
-  if (d->precision == BEVR_PREC_BF16) return launch_fwd<BEVR_PREC_BF16>(*d, Q, K, Vt, key_ws, table_pair, O, LSE, st BEVR_DROP_ARGS);
-  if (d->precision == BEVR_PREC_F16) return launch_fwd<BEVR_PREC_F16>(*d, Q, K, Vt, key_ws, table_pair, O, LSE, st BEVR_DROP_ARGS);
-  if (d->precision == BEVR_PREC_BF16X3)
-    return launch_fwd<BEVR_PREC_BF16X3>(*d, Q, K, Vt, key_ws, table_pair, O, LSE, st BEVR_DROP_ARGS);
-  return launch_fwd<BEVR_PREC_F32>(*d, Q, K, Vt, key_ws, table_pair, O, LSE, st BEVR_DROP_ARGS);
+  return run(d, Q, K, Vt, key_ws, table_pair, O, LSE, stream);
 }
+#endif

@@ -55,6 +55,7 @@
 //             contracts
 // One workgroup per CU (152 KB of LDS), two waves per SIMD: see DESIGN.md "Split-bf16 mode on the gather forward".
 #include "attn_tap.h"
+#include "attn_host.h"
 
 #ifndef BEVR_GATHER_ROWS
 #define BEVR_GATHER_ROWS 0
@@ -688,13 +689,11 @@ int launch(const bevr_attn_desc& d, const void* Q, const void* K, const void* V,
                      (const char*)Q, (const char*)K, (const char*)V, (const char*)key_ws, (const uint32_t*)table_pk, \
                      mref, O, LSE, flags BEVR_GATHER_ROW_ARGS)
 #if BEVR_GATHER_X3
-  // more than 64 KB of dynamic LDS: the limit is raised per kernel AND per device, so on every launch (a "done once" flag
-  // would leave every device but the first at 64 KB)
+  // more than 64 KB of dynamic LDS: the limit is raised per kernel and per device
 #define BEVR_GATHER_LAUNCH(NB_, EX_, DMA_)                                                                           \
   do {                                                                                                               \
-    const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(&BEVR_GATHER_KERNEL<PREC, NB_, EX_, DMA_>), \
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, L::TOTAL);                 \
-    if (ea != hipSuccess) return (int)ea;                                                                            \
+    const int ea = bevr_raise_dynamic_lds<&BEVR_GATHER_KERNEL<PREC, NB_, EX_, DMA_>>(L::TOTAL);                      \
+    if (ea) return ea;                                                                                               \
     BEVR_GATHER_LAUNCH_(NB_, EX_, DMA_);                                                                             \
   } while (0)
 #else
@@ -717,53 +716,41 @@ int launch(const bevr_attn_desc& d, const void* Q, const void* K, const void* V,
   return BEVR_OK;
 }
 
+// The contract of the three gather entry points.  PRECS: the modes this translation unit holds the kernels of.
+template <int... PRECS>
+int run(const bevr_attn_desc* d, const void* Q, const void* K, const void* V, const void* key_ws, const void* table_pk,
+        const float* mref, float* O, float* LSE, int* flags, int row0, int n_rows, void* stream) {
+  int rc = bevr_check_desc(d);
+  if (rc) return rc;
+  if (!Q || !K || !V || !key_ws || !table_pk || !mref || !O || !LSE || !flags) return BEVR_E_NULL;
+  if (!bevr_aligned16(Q) || !bevr_aligned16(K) || !bevr_aligned16(V) || !bevr_aligned16(O) || !bevr_aligned16(key_ws))
+    return BEVR_E_ALIGN;
+  return bevr_for_precision<PRECS...>(d->precision, [&](auto P) {
+    // a row range is checked after the precision: it starts on a row block and fits the column and one launch
+    if (BEVR_GATHER_ROWS && (row0 < 0 || row0 % QB != 0 || n_rows < 1 || n_rows > 14 * QB || n_rows > d->S - row0))
+      return (int)BEVR_E_SHAPE;
+    return launch<P()>(*d, Q, K, V, key_ws, table_pk, mref, O, LSE, flags, row0, n_rows, (hipStream_t)stream);
+  });
+}
+
 }  // namespace
 
 #if BEVR_GATHER_X3
 extern "C" int bevr_attn_gather_fwd_x3(const bevr_attn_desc* d, const void* Q, const void* K, const void* V,
                                        const void* key_ws, const void* table_pk2, const float* mref, float* O,
                                        float* LSE, int* flags, int row0, int n_rows, void* stream) {
-  int rc = bevr_check_desc(d);
-  if (rc) return rc;
-  if (!Q || !K || !V || !key_ws || !table_pk2 || !mref || !O || !LSE || !flags) return BEVR_E_NULL;
-  if (!bevr_aligned16(Q) || !bevr_aligned16(K) || !bevr_aligned16(V) || !bevr_aligned16(O) || !bevr_aligned16(key_ws))
-    return BEVR_E_ALIGN;
-  if (d->precision != BEVR_PREC_BF16X3) return BEVR_E_PRECISION;
-  if (row0 < 0 || row0 % QB != 0 || n_rows < 1 || n_rows > 14 * QB || n_rows > d->S - row0) return BEVR_E_SHAPE;
-  return launch<BEVR_PREC_BF16X3>(*d, Q, K, V, key_ws, table_pk2, mref, O, LSE, flags, row0, n_rows, (hipStream_t)stream);
+  return run<BEVR_PREC_BF16X3>(d, Q, K, V, key_ws, table_pk2, mref, O, LSE, flags, row0, n_rows, stream);
 }
-
-#elif !BEVR_GATHER_ROWS
-extern "C" int bevr_attn_gather_fwd(const bevr_attn_desc* d, const void* Q, const void* K, const void* V,
-                                    const void* key_ws, const void* table_pk, const float* mref, float* O, float* LSE,
-                                    int* flags, void* stream) {
-  int rc = bevr_check_desc(d);
-  if (rc) return rc;
-  if (!Q || !K || !V || !key_ws || !table_pk || !mref || !O || !LSE || !flags) return BEVR_E_NULL;
-  if (!bevr_aligned16(Q) || !bevr_aligned16(K) || !bevr_aligned16(V) || !bevr_aligned16(O) || !bevr_aligned16(key_ws))
-    return BEVR_E_ALIGN;
-  hipStream_t st = (hipStream_t)stream;
-  if (d->precision == BEVR_PREC_BF16)
-    return launch<BEVR_PREC_BF16>(*d, Q, K, V, key_ws, table_pk, mref, O, LSE, flags, 0, 0, st);
-  if (d->precision == BEVR_PREC_F16)
-    return launch<BEVR_PREC_F16>(*d, Q, K, V, key_ws, table_pk, mref, O, LSE, flags, 0, 0, st);
-  return BEVR_E_PRECISION;
-}
-
-#else
+#elif BEVR_GATHER_ROWS
 extern "C" int bevr_attn_gather_fwd_rows(const bevr_attn_desc* d, const void* Q, const void* K, const void* V,
                                          const void* key_ws, const void* table_pk, const float* mref, float* O,
                                          float* LSE, int* flags, int row0, int n_rows, void* stream) {
-  int rc = bevr_check_desc(d);
-  if (rc) return rc;
-  if (!Q || !K || !V || !key_ws || !table_pk || !mref || !O || !LSE || !flags) return BEVR_E_NULL;
-  if (!bevr_aligned16(Q) || !bevr_aligned16(K) || !bevr_aligned16(V) || !bevr_aligned16(O) || !bevr_aligned16(key_ws))
-    return BEVR_E_ALIGN;
-  if (d->precision != BEVR_PREC_BF16 && d->precision != BEVR_PREC_F16) return BEVR_E_PRECISION;
-  if (row0 < 0 || row0 % QB != 0 || n_rows < 1 || n_rows > 14 * QB || n_rows > d->S - row0) return BEVR_E_SHAPE;
-  hipStream_t st = (hipStream_t)stream;
-  if (d->precision == BEVR_PREC_BF16)
-    return launch<BEVR_PREC_BF16>(*d, Q, K, V, key_ws, table_pk, mref, O, LSE, flags, row0, n_rows, st);
-  return launch<BEVR_PREC_F16>(*d, Q, K, V, key_ws, table_pk, mref, O, LSE, flags, row0, n_rows, st);
+  return run<BEVR_PREC_BF16, BEVR_PREC_F16>(d, Q, K, V, key_ws, table_pk, mref, O, LSE, flags, row0, n_rows, stream);
+}
+#else
+extern "C" int bevr_attn_gather_fwd(const bevr_attn_desc* d, const void* Q, const void* K, const void* V,
+                                    const void* key_ws, const void* table_pk, const float* mref, float* O, float* LSE,
+                                    int* flags, void* stream) {
+  return run<BEVR_PREC_BF16, BEVR_PREC_F16>(d, Q, K, V, key_ws, table_pk, mref, O, LSE, flags, 0, 0, stream);
 }
 #endif

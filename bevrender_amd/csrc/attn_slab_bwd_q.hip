@@ -55,6 +55,7 @@
 #endif
 #include "attn_tile.h"
 #include "attn_tap.h"
+#include "attn_host.h"
 
 #include "bevr_prof.h"
 
@@ -728,26 +729,13 @@ int launch(const bevr_attn_desc& d, const void* Q, const void* Ks, const void* V
   int* cnt = reinterpret_cast<int*>(const_cast<char*>(base) + w.off_cnt);
   hipError_t e = hipMemsetAsync(cnt + 1, 0, 4, st);       // the item counter of this launch
   if (e != hipSuccess) return (int)e;
-  // the CU count and the dynamic-LDS attribute belong to a DEVICE, not to the process: both are cached per device
-  constexpr int MAX_DEV = 64;
-  static int n_cu_of[MAX_DEV] = {};
-  static bool attr_set[MAX_DEV][4] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEV) return BEVR_E_SHAPE;
-  if (n_cu_of[dev] == 0) {
-    int n = 0;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) return BEVR_E_SHAPE;
-    n_cu_of[dev] = n;
-  }
-  const int n_cu = n_cu_of[dev];
+  // one workgroup per CU of the current device, with more than 64 KB of dynamic LDS
+  const int n_cu = bevr_cu_count();
+  if (n_cu <= 0) return BEVR_E_SHAPE;
   const int R = slab_rows(d.S);
   const size_t lds = slab_lds_bytes(d.S, w.sw, RP);
-  if (!attr_set[dev][PREC]) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&SLAB_KERNEL(PREC, RP)),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return (int)e;
-    attr_set[dev][PREC] = true;
-  }
+  const int ea = bevr_raise_dynamic_lds<&SLAB_KERNEL(PREC, RP)>(160 * 1024);
+  if (ea) return ea;
   hipLaunchKernelGGL((SLAB_KERNEL(PREC, RP)), dim3(n_cu), dim3(STHREADS), lds, st, d, (const char*)Q,
                      (const char*)Ks, (const char*)Vs, reinterpret_cast<const SlabKey*>(base),
                      reinterpret_cast<const int*>(base + w.off_beg), reinterpret_cast<const int*>(base + w.off_end),
@@ -796,6 +784,39 @@ bool slab_shape_ok(const bevr_attn_desc& d) {
 #define SLAB_PREP bevr_attn_slab_prep
 #endif
 
+// The contract of the three slab bwd_q entry points.  PRECS: the modes this translation unit holds the kernels of;
+// (row0, n_rows): the band of BEVR_SLAB_ROWS, else unused.
+template <int... PRECS>
+int run(const bevr_attn_desc* d, const void* Q, const void* Ks, const void* Vs, const void* slab_ws_,
+        const float* table_pair, const void* dO, const float* LSE, const float* delta, const float* grad_scale, float* dQ,
+        float* dtable, int row0, int n_rows, void* stream) {
+  int rc = bevr_check_desc(d);
+  if (rc) return rc;
+  if (!Q || !Ks || !Vs || !slab_ws_ || !table_pair || !dO || !LSE || !delta || !grad_scale || !dQ || !dtable)
+    return BEVR_E_NULL;
+  // the precision before the shape before the alignment
+  return bevr_for_precision<PRECS...>(d->precision, [&](auto P) {
+    if (!slab_shape_ok(*d)) return (int)BEVR_E_SHAPE;
+#if BEVR_SLAB_ROWS
+    if (!slab_band_ok(*d, row0, n_rows)) return (int)BEVR_E_SHAPE;
+#endif
+    if (!bevr_aligned16(Q) || !bevr_aligned16(Ks) || !bevr_aligned16(Vs) || !bevr_aligned16(dO) || !bevr_aligned16(dQ) ||
+        !bevr_aligned16(table_pair) || !bevr_aligned16(slab_ws_))
+      return (int)BEVR_E_ALIGN;
+    const int nb = (n_rows + SQROWS - 1) / SQROWS;
+    auto go = [&](auto RP) {
+      return launch<decltype(P)::value, decltype(RP)::value>(*d, Q, Ks, Vs, slab_ws_, table_pair, dO, LSE, delta,
+                                                             grad_scale, dQ, dtable, row0, nb, (hipStream_t)stream);
+    };
+#if BEVR_SLAB_ROWS
+    return slab_pitch(d->S) == SLAB_RP_B ? go(std::integral_constant<int, SLAB_RP_B>())
+                                         : go(std::integral_constant<int, SLAB_RP_A>());
+#else
+    return go(std::integral_constant<int, SLAB_RP>());
+#endif
+  });
+}
+
 }  // namespace
 
 extern "C" size_t SLAB_WS_BYTES(const bevr_attn_desc* d) {
@@ -832,41 +853,20 @@ extern "C" int bevr_attn_slab_bwd_q_rows(const bevr_attn_desc* d, const void* Q,
                                          const void* slab_ws_, const float* table_pair, const void* dO, const float* LSE,
                                          const float* delta, const float* grad_scale, float* dQ, float* dtable, int row0,
                                          int n_rows, void* stream) {
+  return run<BEVR_PREC_BF16, BEVR_PREC_F16>(d, Q, Ks, Vs, slab_ws_, table_pair, dO, LSE, delta, grad_scale, dQ, dtable, row0,
+                                            n_rows, stream);
+}
 #elif BEVR_SLAB_X3
 extern "C" int bevr_attn_slab_bwd_q_x3(const bevr_attn_desc* d, const void* Q, const void* Ks, const void* Vs,
                                        const void* slab_ws_, const float* table_pair, const void* dO, const float* LSE,
                                        const float* delta, const float* grad_scale, float* dQ, float* dtable, void* stream) {
+  return run<BEVR_PREC_BF16X3>(d, Q, Ks, Vs, slab_ws_, table_pair, dO, LSE, delta, grad_scale, dQ, dtable, 0, 0, stream);
+}
 #else
 extern "C" int bevr_attn_slab_bwd_q(const bevr_attn_desc* d, const void* Q, const void* Ks, const void* Vs,
                                     const void* slab_ws_, const float* table_pair, const void* dO, const float* LSE,
                                     const float* delta, const float* grad_scale, float* dQ, float* dtable, void* stream) {
-#endif
-  int rc = bevr_check_desc(d);
-  if (rc) return rc;
-  if (!Q || !Ks || !Vs || !slab_ws_ || !table_pair || !dO || !LSE || !delta || !grad_scale || !dQ || !dtable)
-    return BEVR_E_NULL;
-  if (!SLAB_PREC_OK(d->precision)) return BEVR_E_PRECISION;
-  if (!slab_shape_ok(*d)) return BEVR_E_SHAPE;
-#if BEVR_SLAB_ROWS
-  if (!slab_band_ok(*d, row0, n_rows)) return BEVR_E_SHAPE;
-#endif
-  if (!bevr_aligned16(Q) || !bevr_aligned16(Ks) || !bevr_aligned16(Vs) || !bevr_aligned16(dO) || !bevr_aligned16(dQ) ||
-      !bevr_aligned16(table_pair) || !bevr_aligned16(slab_ws_))
-    return BEVR_E_ALIGN;
-  hipStream_t st = (hipStream_t)stream;
-#if BEVR_SLAB_ROWS
-  const int nb = (n_rows + SQROWS - 1) / SQROWS;
-  const bool tall = slab_pitch(d->S) == SLAB_RP_B;
-  if (d->precision == BEVR_PREC_BF16)
-    return tall ? launch<BEVR_PREC_BF16, SLAB_RP_B>(*d, Q, Ks, Vs, slab_ws_, table_pair, dO, LSE, delta, grad_scale, dQ, dtable, row0, nb, st)
-                : launch<BEVR_PREC_BF16, SLAB_RP_A>(*d, Q, Ks, Vs, slab_ws_, table_pair, dO, LSE, delta, grad_scale, dQ, dtable, row0, nb, st);
-  return tall ? launch<BEVR_PREC_F16, SLAB_RP_B>(*d, Q, Ks, Vs, slab_ws_, table_pair, dO, LSE, delta, grad_scale, dQ, dtable, row0, nb, st)
-              : launch<BEVR_PREC_F16, SLAB_RP_A>(*d, Q, Ks, Vs, slab_ws_, table_pair, dO, LSE, delta, grad_scale, dQ, dtable, row0, nb, st);
-#elif BEVR_SLAB_X3
-  return launch<BEVR_PREC_BF16X3>(*d, Q, Ks, Vs, slab_ws_, table_pair, dO, LSE, delta, grad_scale, dQ, dtable, 0, 0, st);
-#else
-  if (d->precision == BEVR_PREC_BF16)
-    return launch<BEVR_PREC_BF16>(*d, Q, Ks, Vs, slab_ws_, table_pair, dO, LSE, delta, grad_scale, dQ, dtable, 0, 0, st);
-  return launch<BEVR_PREC_F16>(*d, Q, Ks, Vs, slab_ws_, table_pair, dO, LSE, delta, grad_scale, dQ, dtable, 0, 0, st);
-#endif
+  return run<BEVR_PREC_BF16, BEVR_PREC_F16>(d, Q, Ks, Vs, slab_ws_, table_pair, dO, LSE, delta, grad_scale, dQ, dtable, 0, 0,
+                                            stream);
 }
+#endif

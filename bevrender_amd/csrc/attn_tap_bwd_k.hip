@@ -20,6 +20,7 @@
 // that column (any key set is handled; a cell-sorted segment never does).
 #include <type_traits>
 #include "attn_tap.h"
+#include "attn_host.h"
 
 namespace {
 
@@ -58,7 +59,7 @@ __device__ __forceinline__ bool tile_fits(const StepBox& sb, float jrx, int a0w,
 // their columns and every wave would wait at the barriers of columns it skips; a wave that stages the 2 KB of G | H rows
 // of its own slab into its own LDS buffer stages exactly what it computes and meets no barrier at all.
 constexpr int MODE_FIT = 0, MODE_SLOW = 1, MODE_LIST = 2;
-constexpr int LIST_HEAD = 4;           // work list: int [0] = count, [LIST_HEAD + i] = ph * (Np / 32) + tile
+// work list (attn_host.h): unit i = ph * (Np / 32) + tile; [1] is the list launch's claim counter
 constexpr int LIST_WAVES = 4;          // waves per workgroup of the list launch (independent of each other)
 // The shortest range of BEV columns of an item.  An item reads its 32 tap records, forms their weights and ends with 128
 // float atomics, a few microseconds; an unfit column is nslab slabs of per-pair gathers at ~3.3 us each (measured on the
@@ -591,17 +592,6 @@ __global__ __launch_bounds__(64 * LIST_WAVES, 3) void attn_tap_bwd_k_list_kernel
                                     tile / NKW, tile % NKW, rng * cols, min(d.S, (rng + 1) * cols), nullptr);
   }
 }
-
-// workgroups the device holds at once: compute units x the kernel's residency (asked once per kernel)
-template <typename Kern>
-int resident_workgroups(Kern kern, int threads, size_t lds) {
-  int dev = 0, cus = 0, per_cu = 0;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, threads, lds) != hipSuccess)
-    return 0;
-  return cus * per_cu;
-}
 #endif
 
 // slow_list: null -- the slow pairs by the main grid launched again; else the work list (cleared here, filled by the
@@ -621,58 +611,37 @@ int launch(const bevr_attn_desc& d, const void* G, const void* H, const void* ta
   if (slow_list) {
     // the list kernel counts items (listed tile, range) in an int
     if ((long long)n_ph * n_tiles * (d.S / LIST_MIN_COLS + 1) > 0x7fffffffLL) return BEVR_E_SHAPE;
-    rc = (int)hipMemsetAsync(slow_list, 0, LIST_HEAD * sizeof(int), st);
+    rc = bevr_list_clear(slow_list, st);
     if (rc) return rc;
   }
-  hipLaunchKernelGGL((attn_tap_bwd_k_kernel<PREC, false>), dim3((unsigned)grid), dim3(64 * (NKW + 1)), lds, st, d, (const char*)G,
-                     (const char*)H, (const char*)tap_ws, table_t, dkey_a, dkey_b, dkey_y, dkey_x, n_wg_ph, slow_list TAP_DROP_ARGS);
+  // the operands the kernels share; each adds its own tail
+#define BEVR_TAP_BWD_K_ARGS \
+  d, (const char*)G, (const char*)H, (const char*)tap_ws, table_t, dkey_a, dkey_b, dkey_y, dkey_x
+#define BEVR_TAP_LAUNCH(SLOW_, LIST_)                                                                                  \
+  hipLaunchKernelGGL((attn_tap_bwd_k_kernel<PREC, SLOW_>), dim3((unsigned)grid), dim3(64 * (NKW + 1)), lds, st,       \
+                     BEVR_TAP_BWD_K_ARGS, n_wg_ph, LIST_ TAP_DROP_ARGS)
+  BEVR_TAP_LAUNCH(false, slow_list);
   rc = (int)hipGetLastError();
   if (rc) return rc;
 #if !BEVR_DROP && !BEVR_TAP_X3
   if (slow_list) {
     const size_t lds_list = LIST_WAVES * (2 * L::SLAB + 32 * sizeof(TapRec));
-    static const int resident = resident_workgroups(attn_tap_bwd_k_list_kernel<PREC>, 64 * LIST_WAVES, lds_list);
-    if (resident <= 0) return (int)hipErrorInvalidDevice;
-    const int n_wg = max_wg > 0 && max_wg < resident ? max_wg : resident;
-    hipLaunchKernelGGL((attn_tap_bwd_k_list_kernel<PREC>), dim3(n_wg), dim3(64 * LIST_WAVES), lds_list, st, d, (const char*)G,
-                       (const char*)H, (const char*)tap_ws, table_t, dkey_a, dkey_b, dkey_y, dkey_x, slow_list);
+    const int n_wg = bevr_list_workgroups<&attn_tap_bwd_k_list_kernel<PREC>>(max_wg, 64 * LIST_WAVES, lds_list);
+    if (n_wg <= 0) return (int)hipErrorInvalidDevice;
+    hipLaunchKernelGGL((attn_tap_bwd_k_list_kernel<PREC>), dim3(n_wg), dim3(64 * LIST_WAVES), lds_list, st,
+                       BEVR_TAP_BWD_K_ARGS, slow_list);
     return (int)hipGetLastError();
   }
 #endif
-  hipLaunchKernelGGL((attn_tap_bwd_k_kernel<PREC, true>), dim3((unsigned)grid), dim3(64 * (NKW + 1)), lds, st, d, (const char*)G,
-                     (const char*)H, (const char*)tap_ws, table_t, dkey_a, dkey_b, dkey_y, dkey_x, n_wg_ph, (int*)nullptr TAP_DROP_ARGS);
+  BEVR_TAP_LAUNCH(true, (int*)nullptr);
+#undef BEVR_TAP_LAUNCH
+#undef BEVR_TAP_BWD_K_ARGS
   return (int)hipGetLastError();
 }
 
-}  // namespace
-
-#if BEVR_TAP_X3 && BEVR_DROP
-// the split-mode instantiations with the keep mask: this translation unit is attn_tap_bwd_k_x3_drop.hip, an entry point
-// of its own (the arguments and checks of bevr_attn_tap_bwd_k_dropout; BEVR_PREC_BF16X3 alone; the slow pairs by the main
-// grid launched again: no work list)
-extern "C" int bevr_attn_tap_bwd_k_x3_dropout(const bevr_attn_desc* d, const void* G, const void* H, const void* tap_ws,
-                                              const float* table_t, float* dkey_a, float* dkey_b, float* dkey_y,
-                                              float* dkey_x, unsigned key0, unsigned drop_thr, unsigned drop_seed,
-                                              void* stream) {
-  if (drop_thr >= 65536u) return BEVR_E_SHAPE;
-  int rc = bevr_check_desc(d);
-  if (rc) return rc;
-  if (!G || !H || !tap_ws || !table_t || !dkey_a || !dkey_b || !dkey_y || !dkey_x) return BEVR_E_NULL;
-  if (d->groups != 1) return BEVR_E_SHAPE;
-  if (!bevr_aligned16(G) || !bevr_aligned16(H) || !bevr_aligned16(tap_ws)) return BEVR_E_ALIGN;
-  if (d->precision != BEVR_PREC_BF16X3) return BEVR_E_PRECISION;
-  return launch<BEVR_PREC_BF16X3>(*d, G, H, tap_ws, table_t, dkey_a, dkey_b, dkey_y, dkey_x, nullptr, 0,
-                                  (hipStream_t)stream TAP_DROP_ARGS);
-}
-#elif BEVR_TAP_X3
-// the split-mode instantiations: this translation unit is attn_tap_bwd_k_x3.hip, entered from bevr_attn_tap_bwd_k
-int bevr_tap_bwd_k_x3(const bevr_attn_desc& d, const void* G, const void* H, const void* tap_ws, const float* table_t,
-                      float* dkey_a, float* dkey_b, float* dkey_y, float* dkey_x, hipStream_t st) {
-  return launch<BEVR_PREC_BF16X3>(d, G, H, tap_ws, table_t, dkey_a, dkey_b, dkey_y, dkey_x, nullptr, 0, st);
-}
-#else
-namespace {
+// The contract of every tap bwd_k entry point.  PRECS: the modes this translation unit holds the kernels of.
 // slow_list: null for the full-grid slow launch (and always in the split mode, which has no list kernel)
+template <int... PRECS>
 int run(const bevr_attn_desc* d, const void* G, const void* H, const void* tap_ws, const float* table_t, float* dkey_a,
         float* dkey_b, float* dkey_y, float* dkey_x, int* slow_list, int max_wg, void* stream TAP_DROP_PARAMS) {
   int rc = bevr_check_desc(d);
@@ -681,36 +650,53 @@ int run(const bevr_attn_desc* d, const void* G, const void* H, const void* tap_w
   if (d->groups != 1) return BEVR_E_SHAPE;
   if (!bevr_aligned16(G) || !bevr_aligned16(H) || !bevr_aligned16(tap_ws)) return BEVR_E_ALIGN;
   hipStream_t st = (hipStream_t)stream;
-  if (d->precision == BEVR_PREC_BF16)
-    return launch<BEVR_PREC_BF16>(*d, G, H, tap_ws, table_t, dkey_a, dkey_b, dkey_y, dkey_x, slow_list, max_wg, st TAP_DROP_ARGS);
-  if (d->precision == BEVR_PREC_F16)
-    return launch<BEVR_PREC_F16>(*d, G, H, tap_ws, table_t, dkey_a, dkey_b, dkey_y, dkey_x, slow_list, max_wg, st TAP_DROP_ARGS);
-#if !BEVR_DROP
+#if !BEVR_DROP && !BEVR_TAP_X3
+  // the split mode's kernels are attn_tap_bwd_k_x3.hip's
   if (d->precision == BEVR_PREC_BF16X3 && !slow_list)
     return bevr_tap_bwd_k_x3(*d, G, H, tap_ws, table_t, dkey_a, dkey_b, dkey_y, dkey_x, st);
 #endif
-  return BEVR_E_PRECISION;
+  return bevr_for_precision<PRECS...>(d->precision, [&](auto P) {
+    return launch<P()>(*d, G, H, tap_ws, table_t, dkey_a, dkey_b, dkey_y, dkey_x, slow_list, max_wg, st TAP_DROP_ARGS);
+  });
 }
+
 }  // namespace
 
-#if BEVR_DROP
+#if BEVR_TAP_X3 && !BEVR_DROP
+// the split-mode instantiations: this translation unit is attn_tap_bwd_k_x3.hip, entered from bevr_attn_tap_bwd_k
+int bevr_tap_bwd_k_x3(const bevr_attn_desc& d, const void* G, const void* H, const void* tap_ws, const float* table_t,
+                      float* dkey_a, float* dkey_b, float* dkey_y, float* dkey_x, hipStream_t st) {
+  return launch<BEVR_PREC_BF16X3>(d, G, H, tap_ws, table_t, dkey_a, dkey_b, dkey_y, dkey_x, nullptr, 0, st);
+}
+#elif BEVR_TAP_X3
+// the split-mode instantiations with the keep mask: this translation unit is attn_tap_bwd_k_x3_drop.hip, an entry point
+// of its own (the slow pairs by the main grid launched again: no work list)
+extern "C" int bevr_attn_tap_bwd_k_x3_dropout(const bevr_attn_desc* d, const void* G, const void* H, const void* tap_ws,
+                                              const float* table_t, float* dkey_a, float* dkey_b, float* dkey_y,
+                                              float* dkey_x, unsigned key0, unsigned drop_thr, unsigned drop_seed,
+                                              void* stream) {
+  if (drop_thr >= 65536u) return BEVR_E_SHAPE;
+  return run<BEVR_PREC_BF16X3>(d, G, H, tap_ws, table_t, dkey_a, dkey_b, dkey_y, dkey_x, nullptr, 0, stream TAP_DROP_ARGS);
+}
+#elif BEVR_DROP
 extern "C" int bevr_attn_tap_bwd_k_dropout(const bevr_attn_desc* d, const void* G, const void* H, const void* tap_ws,
                                            const float* table_t, float* dkey_a, float* dkey_b, float* dkey_y,
                                            float* dkey_x, unsigned key0, unsigned drop_thr, unsigned drop_seed,
                                            void* stream) {
   if (drop_thr >= 65536u) return BEVR_E_SHAPE;
-  return run(d, G, H, tap_ws, table_t, dkey_a, dkey_b, dkey_y, dkey_x, nullptr, 0, stream, key0, drop_thr, drop_seed);
+  return run<BEVR_PREC_BF16, BEVR_PREC_F16>(d, G, H, tap_ws, table_t, dkey_a, dkey_b, dkey_y, dkey_x, nullptr, 0, stream
+                                            TAP_DROP_ARGS);
 }
 #else
 extern "C" int bevr_attn_tap_bwd_k(const bevr_attn_desc* d, const void* G, const void* H, const void* tap_ws,
                                    const float* table_t, float* dkey_a, float* dkey_b, float* dkey_y, float* dkey_x,
                                    void* stream) {
-  return run(d, G, H, tap_ws, table_t, dkey_a, dkey_b, dkey_y, dkey_x, nullptr, 0, stream);
+  return run<BEVR_PREC_BF16, BEVR_PREC_F16>(d, G, H, tap_ws, table_t, dkey_a, dkey_b, dkey_y, dkey_x, nullptr, 0, stream);
 }
 
 extern "C" size_t bevr_attn_tap_bwd_k_ws_bytes(const bevr_attn_desc* d) {
   if (bevr_check_desc(d)) return 0;
-  return (LIST_HEAD + (size_t)d->n_prob * d->heads * (d->Np / 32)) * sizeof(int);
+  return bevr_list_bytes((size_t)d->n_prob * d->heads * (d->Np / 32));
 }
 
 extern "C" int bevr_attn_tap_bwd_k_ws(const bevr_attn_desc* d, const void* G, const void* H, const void* tap_ws,
@@ -719,8 +705,7 @@ extern "C" int bevr_attn_tap_bwd_k_ws(const bevr_attn_desc* d, const void* G, co
   if (!ws) return BEVR_E_NULL;
   if (!bevr_aligned16(ws)) return BEVR_E_ALIGN;
   if (max_workgroups < 0) return BEVR_E_SHAPE;
-  return run(d, G, H, tap_ws, table_t, dkey_a, dkey_b, dkey_y, dkey_x, (int*)ws, max_workgroups, stream);
+  return run<BEVR_PREC_BF16, BEVR_PREC_F16>(d, G, H, tap_ws, table_t, dkey_a, dkey_b, dkey_y, dkey_x, (int*)ws,
+                                            max_workgroups, stream);
 }
 #endif
-#endif  // BEVR_TAP_X3
-

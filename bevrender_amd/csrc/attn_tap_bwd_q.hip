@@ -12,6 +12,7 @@
 // from the images the producer wrote).  The cell half of dG lives in 4 registers per row block while the chunk origin
 // stays and is flushed into the table gradient with float atomics when it changes (~1 tile in 30).
 #include "attn_tap.h"
+#include "attn_host.h"
 
 namespace {
 
@@ -213,40 +214,10 @@ int launch(const bevr_attn_desc& d, const void* G, const void* H, const void* ta
   return (int)hipGetLastError();
 }
 
-}  // namespace
-
-#if BEVR_TAP_X3 && BEVR_DROP
-// the split-mode instantiations with the keep mask: this translation unit is attn_tap_bwd_q_x3_drop.hip, an entry point
-// of its own (the arguments and checks of bevr_attn_tap_bwd_q_dropout; BEVR_PREC_BF16X3 alone)
-extern "C" int bevr_attn_tap_bwd_q_x3_dropout(const bevr_attn_desc* d, const void* G, const void* H, const void* tap_ws,
-                                              const float* table_pair, float* dG, float* dtable, unsigned key0,
-                                              unsigned drop_thr, unsigned drop_seed, void* stream) {
-  if (drop_thr >= 65536u) return BEVR_E_SHAPE;
-  int rc = bevr_check_desc(d);
-  if (rc) return rc;
-  if (!G || !H || !tap_ws || !table_pair || !dG || !dtable) return BEVR_E_NULL;
-  if (d->groups != 1) return BEVR_E_SHAPE;
-  if (!bevr_aligned16(G) || !bevr_aligned16(H) || !bevr_aligned16(tap_ws) || !bevr_aligned16(table_pair) || !bevr_aligned16(dG))
-    return BEVR_E_ALIGN;
-  if (d->precision != BEVR_PREC_BF16X3) return BEVR_E_PRECISION;
-  return launch<BEVR_PREC_BF16X3>(*d, G, H, tap_ws, table_pair, dG, dtable, (hipStream_t)stream TAP_DROP_ARGS);
-}
-#elif BEVR_TAP_X3
-// the split-mode instantiations: this translation unit is attn_tap_bwd_q_x3.hip, entered from bevr_attn_tap_bwd_q
-int bevr_tap_bwd_q_x3(const bevr_attn_desc& d, const void* G, const void* H, const void* tap_ws, const float* table_pair,
-                      float* dG, float* dtable, hipStream_t st) {
-  return launch<BEVR_PREC_BF16X3>(d, G, H, tap_ws, table_pair, dG, dtable, st);
-}
-#else
-#if BEVR_DROP
-extern "C" int bevr_attn_tap_bwd_q_dropout(const bevr_attn_desc* d, const void* G, const void* H, const void* tap_ws,
-                                           const float* table_pair, float* dG, float* dtable, unsigned key0,
-                                           unsigned drop_thr, unsigned drop_seed, void* stream) {
-  if (drop_thr >= 65536u) return BEVR_E_SHAPE;
-#else
-extern "C" int bevr_attn_tap_bwd_q(const bevr_attn_desc* d, const void* G, const void* H, const void* tap_ws,
-                                   const float* table_pair, float* dG, float* dtable, void* stream) {
-#endif
+// The contract of every tap bwd_q entry point.  PRECS: the modes this translation unit holds the kernels of.
+template <int... PRECS>
+int run(const bevr_attn_desc* d, const void* G, const void* H, const void* tap_ws, const float* table_pair, float* dG,
+        float* dtable, void* stream TAP_DROP_PARAMS) {
   int rc = bevr_check_desc(d);
   if (rc) return rc;
   if (!G || !H || !tap_ws || !table_pair || !dG || !dtable) return BEVR_E_NULL;
@@ -254,11 +225,42 @@ extern "C" int bevr_attn_tap_bwd_q(const bevr_attn_desc* d, const void* G, const
   if (!bevr_aligned16(G) || !bevr_aligned16(H) || !bevr_aligned16(tap_ws) || !bevr_aligned16(table_pair) || !bevr_aligned16(dG))
     return BEVR_E_ALIGN;
   hipStream_t st = (hipStream_t)stream;
-  if (d->precision == BEVR_PREC_BF16) return launch<BEVR_PREC_BF16>(*d, G, H, tap_ws, table_pair, dG, dtable, st TAP_DROP_ARGS);
-  if (d->precision == BEVR_PREC_F16) return launch<BEVR_PREC_F16>(*d, G, H, tap_ws, table_pair, dG, dtable, st TAP_DROP_ARGS);
-#if !BEVR_DROP
+#if !BEVR_DROP && !BEVR_TAP_X3
+  // the split mode's kernels are attn_tap_bwd_q_x3.hip's
   if (d->precision == BEVR_PREC_BF16X3) return bevr_tap_bwd_q_x3(*d, G, H, tap_ws, table_pair, dG, dtable, st);
 #endif
-  return BEVR_E_PRECISION;
+  return bevr_for_precision<PRECS...>(d->precision, [&](auto P) {
+    return launch<P()>(*d, G, H, tap_ws, table_pair, dG, dtable, st TAP_DROP_ARGS);
+  });
 }
-#endif  // BEVR_TAP_X3
+
+}  // namespace
+
+#if BEVR_TAP_X3 && !BEVR_DROP
+// the split-mode instantiations: this translation unit is attn_tap_bwd_q_x3.hip, entered from bevr_attn_tap_bwd_q
+int bevr_tap_bwd_q_x3(const bevr_attn_desc& d, const void* G, const void* H, const void* tap_ws, const float* table_pair,
+                      float* dG, float* dtable, hipStream_t st) {
+  return launch<BEVR_PREC_BF16X3>(d, G, H, tap_ws, table_pair, dG, dtable, st);
+}
+#elif BEVR_TAP_X3
+// the split-mode instantiations with the keep mask: this translation unit is attn_tap_bwd_q_x3_drop.hip, an entry point
+// of its own
+extern "C" int bevr_attn_tap_bwd_q_x3_dropout(const bevr_attn_desc* d, const void* G, const void* H, const void* tap_ws,
+                                              const float* table_pair, float* dG, float* dtable, unsigned key0,
+                                              unsigned drop_thr, unsigned drop_seed, void* stream) {
+  if (drop_thr >= 65536u) return BEVR_E_SHAPE;
+  return run<BEVR_PREC_BF16X3>(d, G, H, tap_ws, table_pair, dG, dtable, stream TAP_DROP_ARGS);
+}
+#elif BEVR_DROP
+extern "C" int bevr_attn_tap_bwd_q_dropout(const bevr_attn_desc* d, const void* G, const void* H, const void* tap_ws,
+                                           const float* table_pair, float* dG, float* dtable, unsigned key0,
+                                           unsigned drop_thr, unsigned drop_seed, void* stream) {
+  if (drop_thr >= 65536u) return BEVR_E_SHAPE;
+  return run<BEVR_PREC_BF16, BEVR_PREC_F16>(d, G, H, tap_ws, table_pair, dG, dtable, stream TAP_DROP_ARGS);
+}
+#else
+extern "C" int bevr_attn_tap_bwd_q(const bevr_attn_desc* d, const void* G, const void* H, const void* tap_ws,
+                                   const float* table_pair, float* dG, float* dtable, void* stream) {
+  return run<BEVR_PREC_BF16, BEVR_PREC_F16>(d, G, H, tap_ws, table_pair, dG, dtable, stream);
+}
+#endif

@@ -19,10 +19,13 @@
 // all underflowed against that reference (bound looser than ~190 binades: exploding activations) is flagged per column
 // and recomputed by the EXACT instantiation (online maximum), which overwrites R and mref of the flagged columns.
 #include "attn_tap.h"
+#include "attn_host.h"
 
 #if BEVR_DROP
+#define BEVR_TAP_FWD_DROP_PARAMS , float* lsum TAP_DROP_PARAMS
 #define BEVR_TAP_FWD_DROP_ARGS , lsum TAP_DROP_ARGS
 #else
+#define BEVR_TAP_FWD_DROP_PARAMS
 #define BEVR_TAP_FWD_DROP_ARGS
 #endif
 
@@ -229,11 +232,7 @@ __global__ __launch_bounds__(512, tap_fwd_waves(PREC, NB)) void attn_tap_fwd_ker
 
 template <int PREC>
 int launch(const bevr_attn_desc& d, const void* G, const void* tap_ws, const float* table_pair,
-           float* mref, float* R, int* flags, hipStream_t st
-#if BEVR_DROP
-           , float* lsum TAP_DROP_PARAMS
-#endif
-           ) {
+           float* mref, float* R, int* flags, hipStream_t st BEVR_TAP_FWD_DROP_PARAMS) {
   typedef LdsTp<PREC> L;
   const int n_ph = d.n_prob * d.heads;
   const int grid = ((n_ph + 7) / 8) * 8 * d.S;
@@ -258,52 +257,54 @@ int launch(const bevr_attn_desc& d, const void* G, const void* tap_ws, const flo
   return BEVR_OK;
 }
 
-}  // namespace
-
-#if BEVR_TAP_X3 && BEVR_DROP
-// the split-mode instantiations with the keep mask: this translation unit is attn_tap_fwd_x3_drop.hip, an entry point of
-// its own (the arguments and checks of bevr_attn_tap_fwd_dropout; BEVR_PREC_BF16X3 alone)
-extern "C" int bevr_attn_tap_fwd_x3_dropout(const bevr_attn_desc* d, const void* G, const void* tap_ws,
-                                            const float* table_pair, float* mref, float* R, float* lsum, int* flags,
-                                            unsigned key0, unsigned drop_thr, unsigned drop_seed, void* stream) {
-  if (drop_thr >= 65536u) return BEVR_E_SHAPE;
-  if (!lsum) return BEVR_E_NULL;
-  int rc = bevr_check_desc(d);
-  if (rc) return rc;
-  if (!G || !tap_ws || !table_pair || !mref || !R || !flags) return BEVR_E_NULL;
-  if (d->groups != 1) return BEVR_E_SHAPE;
-  if (!bevr_aligned16(G) || !bevr_aligned16(tap_ws) || !bevr_aligned16(table_pair) || !bevr_aligned16(R)) return BEVR_E_ALIGN;
-  if (d->precision != BEVR_PREC_BF16X3) return BEVR_E_PRECISION;
-  return launch<BEVR_PREC_BF16X3>(*d, G, tap_ws, table_pair, mref, R, flags, (hipStream_t)stream BEVR_TAP_FWD_DROP_ARGS);
-}
-#elif BEVR_TAP_X3
-// the split-mode instantiations: this translation unit is attn_tap_fwd_x3.hip, entered from bevr_attn_tap_fwd
-int bevr_tap_fwd_x3(const bevr_attn_desc& d, const void* G, const void* tap_ws, const float* table_pair, float* mref,
-                    float* R, int* flags, hipStream_t st) {
-  return launch<BEVR_PREC_BF16X3>(d, G, tap_ws, table_pair, mref, R, flags, st);
-}
-#else
-#if BEVR_DROP
-extern "C" int bevr_attn_tap_fwd_dropout(const bevr_attn_desc* d, const void* G, const void* tap_ws,
-                                         const float* table_pair, float* mref, float* R, float* lsum, int* flags,
-                                         unsigned key0, unsigned drop_thr, unsigned drop_seed, void* stream) {
-  if (drop_thr >= 65536u) return BEVR_E_SHAPE;
-  if (!lsum) return BEVR_E_NULL;
-#else
-extern "C" int bevr_attn_tap_fwd(const bevr_attn_desc* d, const void* G, const void* tap_ws,
-                                 const float* table_pair, float* mref, float* R, int* flags, void* stream) {
-#endif
+// The contract of every tap forward entry point.  PRECS: the modes this translation unit holds the kernels of.
+template <int... PRECS>
+int run(const bevr_attn_desc* d, const void* G, const void* tap_ws, const float* table_pair, float* mref, float* R,
+        int* flags, void* stream BEVR_TAP_FWD_DROP_PARAMS) {
   int rc = bevr_check_desc(d);
   if (rc) return rc;
   if (!G || !tap_ws || !table_pair || !mref || !R || !flags) return BEVR_E_NULL;
   if (d->groups != 1) return BEVR_E_SHAPE;
   if (!bevr_aligned16(G) || !bevr_aligned16(tap_ws) || !bevr_aligned16(table_pair) || !bevr_aligned16(R)) return BEVR_E_ALIGN;
   hipStream_t st = (hipStream_t)stream;
-  if (d->precision == BEVR_PREC_BF16) return launch<BEVR_PREC_BF16>(*d, G, tap_ws, table_pair, mref, R, flags, st BEVR_TAP_FWD_DROP_ARGS);
-  if (d->precision == BEVR_PREC_F16) return launch<BEVR_PREC_F16>(*d, G, tap_ws, table_pair, mref, R, flags, st BEVR_TAP_FWD_DROP_ARGS);
-#if !BEVR_DROP
+#if !BEVR_DROP && !BEVR_TAP_X3
+  // the split mode's kernels are attn_tap_fwd_x3.hip's
   if (d->precision == BEVR_PREC_BF16X3) return bevr_tap_fwd_x3(*d, G, tap_ws, table_pair, mref, R, flags, st);
 #endif
-  return BEVR_E_PRECISION;
+  return bevr_for_precision<PRECS...>(d->precision, [&](auto P) {
+    return launch<P()>(*d, G, tap_ws, table_pair, mref, R, flags, st BEVR_TAP_FWD_DROP_ARGS);
+  });
 }
-#endif  // BEVR_TAP_X3
+
+}  // namespace
+
+#if BEVR_TAP_X3 && !BEVR_DROP
+// the split-mode instantiations: this translation unit is attn_tap_fwd_x3.hip, entered from bevr_attn_tap_fwd
+int bevr_tap_fwd_x3(const bevr_attn_desc& d, const void* G, const void* tap_ws, const float* table_pair, float* mref,
+                    float* R, int* flags, hipStream_t st) {
+  return launch<BEVR_PREC_BF16X3>(d, G, tap_ws, table_pair, mref, R, flags, st);
+}
+#elif BEVR_TAP_X3
+// the split-mode instantiations with the keep mask: this translation unit is attn_tap_fwd_x3_drop.hip, an entry point of
+// its own
+extern "C" int bevr_attn_tap_fwd_x3_dropout(const bevr_attn_desc* d, const void* G, const void* tap_ws,
+                                            const float* table_pair, float* mref, float* R, float* lsum, int* flags,
+                                            unsigned key0, unsigned drop_thr, unsigned drop_seed, void* stream) {
+  if (drop_thr >= 65536u) return BEVR_E_SHAPE;
+  if (!lsum) return BEVR_E_NULL;
+  return run<BEVR_PREC_BF16X3>(d, G, tap_ws, table_pair, mref, R, flags, stream BEVR_TAP_FWD_DROP_ARGS);
+}
+#elif BEVR_DROP
+extern "C" int bevr_attn_tap_fwd_dropout(const bevr_attn_desc* d, const void* G, const void* tap_ws,
+                                         const float* table_pair, float* mref, float* R, float* lsum, int* flags,
+                                         unsigned key0, unsigned drop_thr, unsigned drop_seed, void* stream) {
+  if (drop_thr >= 65536u) return BEVR_E_SHAPE;
+  if (!lsum) return BEVR_E_NULL;
+  return run<BEVR_PREC_BF16, BEVR_PREC_F16>(d, G, tap_ws, table_pair, mref, R, flags, stream BEVR_TAP_FWD_DROP_ARGS);
+}
+#else
+extern "C" int bevr_attn_tap_fwd(const bevr_attn_desc* d, const void* G, const void* tap_ws,
+                                 const float* table_pair, float* mref, float* R, int* flags, void* stream) {
+  return run<BEVR_PREC_BF16, BEVR_PREC_F16>(d, G, tap_ws, table_pair, mref, R, flags, stream);
+}
+#endif

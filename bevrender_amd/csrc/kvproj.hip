@@ -16,6 +16,7 @@
 //            (lane = channel: the transposed layout Xt[ch][n], whose in-32 key order IS the accumulator's row order, see
 //            bevr_common.h) -- instead of a transpose through LDS; the matrix work is ~0.1 ms per SCA call either way.
 #include "bevr_common.h"
+#include "attn_host.h"
 
 namespace {
 
@@ -180,15 +181,15 @@ extern "C" int bevr_kv_project(const void* feat, int feat_bf16, const float* pos
   if (nb <= 0 || Hi < 2 || Wi < 2 || N <= 0 || Np < N || Np % KVP_KEYS || heads <= 0 || c <= 0 || c > 32 ||
       C != heads * c || (C & 15) || C > 256 || pos_pstride < N || groups <= 0 || C % groups || ((C / groups) & 3))
     return BEVR_E_SHAPE;
-  if (!is16(precision)) return BEVR_E_PRECISION;   // the f32-layout modes keep the unfused chain
-  if (!bevr_aligned16(feat) || !bevr_aligned16(Wkv) || !bevr_aligned16(Kr) || !bevr_aligned16(Vr) || !bevr_aligned16(Vt) ||
-      (Kt && !bevr_aligned16(Kt)) || (reinterpret_cast<uintptr_t>(pos) & 7))
-    return BEVR_E_ALIGN;
-  const KvGeom g{nb, Hi, Wi, C, N, Np, heads, c, pos_pstride, groups};
-  hipStream_t st = (hipStream_t)stream;
-  if (precision == BEVR_PREC_BF16)
-    return feat_bf16 ? launch<BEVR_PREC_BF16>(g, static_cast<const bf16_bits*>(feat), pos, Wkv, bkv, Kr, Vr, Kt, Vt, vnorm2_max, knorm2_max, st)
-                     : launch<BEVR_PREC_BF16>(g, static_cast<const float*>(feat), pos, Wkv, bkv, Kr, Vr, Kt, Vt, vnorm2_max, knorm2_max, st);
-  return feat_bf16 ? launch<BEVR_PREC_F16>(g, static_cast<const bf16_bits*>(feat), pos, Wkv, bkv, Kr, Vr, Kt, Vt, vnorm2_max, knorm2_max, st)
-                   : launch<BEVR_PREC_F16>(g, static_cast<const float*>(feat), pos, Wkv, bkv, Kr, Vr, Kt, Vt, vnorm2_max, knorm2_max, st);
+  // the f32-layout modes keep the unfused chain
+  return bevr_for_precision<BEVR_PREC_BF16, BEVR_PREC_F16>(precision, [&](auto P) {
+    if (!bevr_aligned16(feat) || !bevr_aligned16(Wkv) || !bevr_aligned16(Kr) || !bevr_aligned16(Vr) || !bevr_aligned16(Vt) ||
+        (Kt && !bevr_aligned16(Kt)) || (reinterpret_cast<uintptr_t>(pos) & 7))
+      return (int)BEVR_E_ALIGN;
+    const KvGeom g{nb, Hi, Wi, C, N, Np, heads, c, pos_pstride, groups};
+    auto go = [&](auto* f) {
+      return launch<decltype(P)::value>(g, f, pos, Wkv, bkv, Kr, Vr, Kt, Vt, vnorm2_max, knorm2_max, (hipStream_t)stream);
+    };
+    return feat_bf16 ? go(static_cast<const bf16_bits*>(feat)) : go(static_cast<const float*>(feat));
+  });
 }
