@@ -105,7 +105,7 @@ extern "C" int bevr_attn_bwd_prep(const float* dO, const float* O, const float* 
   if (!bevr_aligned16(dO) || !bevr_aligned16(O) || !bevr_aligned16(dOe) || !bevr_aligned16(dOt)) return BEVR_E_ALIGN;
   const long long n_blk = (long long)n_ph * (Mp / 32);
   const long long want = (n_blk + BP_WAVES - 1) / BP_WAVES;
-  const int grid = (int)(want < 256 * 8 ? want : 256 * 8);
+  const int grid = (int)(want < 256 * 8 ? want : 256 * 8);      // restated in tests/test_gpu_glue_edges.py test_attn_bwd_prep_past_one_sweep
   hipStream_t st = (hipStream_t)stream;
   if (precision == BEVR_PREC_BF16)
     hipLaunchKernelGGL((attn_bwd_prep_kernel<BEVR_PREC_BF16>), dim3(grid), dim3(64 * BP_WAVES), 0, st, dO, O, scale, dLSE, LSE0,

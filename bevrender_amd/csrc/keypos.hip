@@ -93,7 +93,7 @@ int check(int V, int P, int G, int N, int sca, int S, int D) {
 
 int grid_of(size_t total) {
   size_t g = (total + 255) / 256;
-  return (int)(g > 8192 ? 8192 : g);
+  return (int)(g > 8192 ? 8192 : g);      // restated in tests/test_gpu_glue_edges.py test_key_positions_past_one_sweep
 }
 
 }  // namespace

@@ -95,6 +95,7 @@ int grid_of(long long rows, int C) {
   const long long per = LN_THREADS / (C >> 2);
   long long g = (rows + per - 1) / per;
   if (g > 256 * 8) g = 256 * 8;   // grid-stride the rest: the backward's per-workgroup reduction stays amortised
+                                  // (the cap is restated in tests/test_gpu_glue_edges.py test_layer_norm_past_one_sweep)
   return (int)(g < 1 ? 1 : g);
 }
 

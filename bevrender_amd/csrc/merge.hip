@@ -118,6 +118,7 @@ int merge_check(int n_prob, int views, int heads, int S, int Sp, int c) {
 
 int merge_grid(long long n_thr) {
   const long long want = (n_thr + MG_THREADS - 1) / MG_THREADS;
+  // (the cap is restated in tests/test_gpu_glue_edges.py test_merge_views_past_one_sweep)
   return (int)(want < 256 * 16 ? want : 256 * 16);      // grid-stride above 16 workgroups per CU
 }
 

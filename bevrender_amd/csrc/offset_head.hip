@@ -192,7 +192,7 @@ __global__ __launch_bounds__(OH_THREADS) void offset_head_bwd_kernel(
 int oh_grid(long long P) {
   long long g = (P + (OH_THREADS / 64) * 16 - 1) / ((OH_THREADS / 64) * 16);   // >= 16 pixels per wave: amortises the parameter load
   if (g > 256 * 4) g = 256 * 4;   // 4 workgroups per CU: enough waves to hide the loads, few enough parameter-gradient atomics
-  if (g < 1) g = 1;
+  if (g < 1) g = 1;   // (both figures are restated in tests/test_gpu_glue_edges.py test_offset_head_past_the_grid_cap)
   return (int)g;
 }
 

@@ -283,8 +283,10 @@ __global__ __launch_bounds__(SB_THREADS) void sample_bwd_patch_kernel(const T* _
       xlo = min(xlo, s_box[w][0]); xhi = max(xhi, s_box[w][1]); ylo = min(ylo, s_box[w][2]); yhi = max(yhi, s_box[w][3]);
       gmax = fmaxf(gmax, __builtin_bit_cast(float, s_box[w][4]));
     }
-    // NaN / inf in dout: no finite unit -- every tap of the chunk takes the direct scatter (pw = 0)
-    const bool unit_ok = gmax > 0.f && gmax < 3.0e38f;
+    // NaN / inf in dout: no finite unit; a largest |dout| below 2^-80: the unit gmax * 2^-40 would be a subnormal float
+    // (a few bits of it left below 2^-86, none below 2^-109, and 256 / gmax infinite below 2^-119) -- every tap of the
+    // chunk takes the direct scatter (pw = 0).  tests/test_gpu_glue_edges.py test_sample_backward_under_a_scaled_cotangent
+    const bool unit_ok = gmax >= 0x1p-80f && gmax < 3.0e38f;
     const float to_fix = unit_ok ? 256.0f / gmax : 0.f, from_fix = unit_ok ? gmax * 0x1p-40f : 0.f;
     const int pw = (xhi >= xlo && unit_ok) ? min(xhi - xlo + 1, PCH_WMAX) : 0;
     const int ph = pw > 0 ? min(yhi - ylo + 1, pix_cap / pw) : 0;
@@ -397,7 +399,8 @@ __global__ __launch_bounds__(SB_THREADS) void sample_bwd_patch_kernel(const T* _
 
 int grid_for(long long total) {
   long long g = (total + 255) / 256;
-  if (g > 256 * 16) g = 256 * 16;  // grid-stride the rest
+  if (g > 256 * 16) g = 256 * 16;  // grid-stride the rest (restated in tests/test_gpu_glue_edges.py
+                                   // test_sample_forward_and_scatter_backward_past_one_sweep)
   if (g < 1) g = 1;
   return (int)g;
 }
@@ -433,6 +436,7 @@ int sample_bwd(const T* feat, const float* pos, const float* dout, float* dfeat,
     // chunks of consecutive keys; a workgroup takes several (the hot corner's partials are reduced once per workgroup)
     const int n_chunk = (N + PCH_KEYS - 1) / PCH_KEYS;
     long long gx = n_chunk;
+    // (restated in tests/test_gpu_glue_edges.py test_sample_patch_backward_with_several_chunks_per_workgroup)
     const long long want = (256LL * 12 + nb - 1) / nb;
     if (gx > want) gx = want;
     hipLaunchKernelGGL(sample_bwd_patch_kernel<T>, dim3((unsigned)gx, nb), dim3(SB_THREADS), 0, (hipStream_t)stream,
@@ -441,6 +445,7 @@ int sample_bwd(const T* feat, const float* pos, const float* dout, float* dfeat,
     // one image per workgroup row, grid-stride over its keys, every tap scattered
     const long long per_img = (long long)N * c4n;
     long long gx = (per_img + SB_THREADS - 1) / SB_THREADS;
+    // (restated in tests/test_gpu_glue_edges.py test_sample_forward_and_scatter_backward_past_one_sweep)
     const long long want = (256LL * 16 + nb - 1) / nb;
     if (gx > want) gx = want;
     if (gx < 1) gx = 1;

@@ -17,6 +17,8 @@
 
 namespace {
 
+// both launchers cap the grid at 256 * 32 workgroups of 256 pixels and grid-stride the rest (restated in
+// tests/test_gpu_glue_edges.py test_affine_warp_past_one_sweep)
 struct WarpTaps {
   int x0, y0;
   float w00, w01, w10, w11;   // in-bounds weights (0 for a tap outside the image)
