@@ -54,6 +54,15 @@
 //   P         split in registers after exp2; the row sum is the ones-operand product of BOTH parts -- of the values PV
 //             contracts
 // One workgroup per CU (152 KB of LDS), two waves per SIMD: see DESIGN.md "Split-bf16 mode on the gather forward".
+//
+// BEVR_DROP = 1 (attn_gather_fwd_drop.hip, a translation unit of its own, with BEVR_GATHER_ROWS = 1): attention dropout,
+// the semantics of bevr_attn_fwd_dropout (attn_fwd.hip).  The keep decision of pair (ph, mq = j Sp + ABSOLUTE BEV row,
+// n = the key's index in the caller's order) is bevr_drop_keep's (bevr_common.h); the row part of the hash is formed once
+// per row block, the key part once per emission (the emission's first key index travels in the control word's third
+// dword, free with NT = 1) -- a strip emission and the EXACT pass hash the same index and so decide alike.  Softmax
+// first: the row sum (a ones-operand product, as without a mask), the largest weight and both LSE planes are of ALL the
+// rounded weights; PV contracts the same packed weights with the dropped ones' 16 bits cleared; D = 65536 / (65536 -
+// drop_thr) multiplies O in the epilogue (the fp16 operands stay the unscaled weights).
 #include "attn_tap.h"
 #include "attn_host.h"
 
@@ -137,7 +146,12 @@ __device__ __forceinline__ void glds16(const char* src, char* lds_base) {
   __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)lds_base, 16, 0, 0);
 }
 
-#if BEVR_GATHER_X3
+#if BEVR_DROP
+static_assert(BEVR_GATHER_ROWS && !BEVR_GATHER_X3, "the keep mask: the 16-bit row-range kernels");
+#define BEVR_GATHER_KERNEL attn_gather_fwd_drop_kernel
+#define BEVR_GATHER_ROW_PARAMS , const int row0, const int n_rows, const unsigned drop_thr, const unsigned drop_seed
+#define BEVR_GATHER_WAVES_PER_SIMD 4
+#elif BEVR_GATHER_X3
 #define BEVR_GATHER_KERNEL attn_gather_fwd_x3_kernel
 #define BEVR_GATHER_ROW_PARAMS , const int row0, const int n_rows
 #define BEVR_GATHER_WAVES_PER_SIMD 2      // one workgroup of 8 waves per CU: 256 registers
@@ -366,9 +380,16 @@ __global__ __launch_bounds__(512, BEVR_GATHER_WAVES_PER_SIMD) void BEVR_GATHER_K
         fd[2 * lane] = nxt->fd_xc;
         fd[2 * lane + 1] = nxt->fd_r0;
       }
+#if BEVR_DROP
+      static_assert(NT == 1, "the third dword (live keys 32..63) carries the emission's first key index");
+      if (lane == 0)
+        *reinterpret_cast<u32x4*>(bb + L::OFF_CT) =
+            u32x4{0u, (unsigned)em.sel, (unsigned)(em.step * GT), nxt ? (unsigned)nxt->nfill : 0u};
+#else
       if (lane == 0)
         *reinterpret_cast<u32x4*>(bb + L::OFF_CT) =
             u32x4{0u, (unsigned)em.sel, (unsigned)(em.sel >> 32), nxt ? (unsigned)nxt->nfill : 0u};
+#endif
     };
 
     Em cur, nxt;
@@ -429,6 +450,9 @@ __global__ __launch_bounds__(512, BEVR_GATHER_WAVES_PER_SIMD) void BEVR_GATHER_K
   f32x4 lacc[NB];         // row sum: a product of the ROUNDED weights with a ones operand (every register the same sum):
                           // O / l is then exact where one key dominates -- the backward's delta = dO . O relies on it
   float pmx[NB];          // the largest weight
+#if BEVR_DROP
+  uint32_t hrow[NB];      // the row part of the keep hash, out of the emission loop
+#endif
   // byte offset of the lane's BEV row (first block) in ITS window column: k-groups 0, 2 read a key's column x, k-groups
   // 1, 3 column x + 1.  The second block's rows are QB dwords further: one ds_read2_b32 serves both blocks.
   const unsigned qoff0 = (unsigned)(blk0 * QB + li) * 4u + (unsigned)(kg & 1) * (PITCH * 4u);
@@ -446,6 +470,9 @@ __global__ __launch_bounds__(512, BEVR_GATHER_WAVES_PER_SIMD) void BEVR_GATHER_K
     negm[nb] = f32x4{-mr, -mr, -mr, -mr};
     lacc[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
     pmx[nb] = 0.f;
+#if BEVR_DROP
+    hrow[nb] = bevr_drop_row(drop_seed, (uint32_t)ph, (uint32_t)mcol);      // mq = j Sp + the absolute BEV row
+#endif
   }
   const uint32_t one2 = H16::pack2(1.0f, 1.0f);
   const bf16x8 ones = __builtin_bit_cast(bf16x8, u32x4{one2, one2, one2, one2});
@@ -490,6 +517,11 @@ __global__ __launch_bounds__(512, BEVR_GATHER_WAVES_PER_SIMD) void BEVR_GATHER_K
       const TapOp<NP> vlo = tap_ld_tr<NP>(bb + L::OFF_VLO + t * 1024 + t_off, 512, L::V_IMG);
       const TapOp<NP> vhi = tap_ld_tr<NP>(bb + L::OFF_VHI + t * 1024 + t_off, 512, L::V_IMG);
       u32x4 pw[NB][NP];      // the tile's weights, packed: the B operand of PV
+#if BEVR_DROP
+      u32x4 km[NB];          // 0xffff over every kept weight of pw: PV contracts pw & km, the row sum all of pw
+      // the key part of the hash: key n = the emission's first key + 16 s2 + 4 kg + r
+      const uint32_t kh0 = ((uint32_t)__builtin_amdgcn_readfirstlane((int)ct[2]) + 4u * (uint32_t)kg) * 0xC2B2AE3Du;
+#endif
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2) {
         const int kb = 32 * t + 16 * s2;                 // first key of the sub-tile
@@ -590,14 +622,31 @@ __global__ __launch_bounds__(512, BEVR_GATHER_WAVES_PER_SIMD) void BEVR_GATHER_K
             pw[nb][0][2 * s2 + 1] = H16::pack2(pb2[0], pb2[1]);
           }
           pmx[nb] = fmaxf(fmaxf(fmaxf(pmx[nb], pa[0]), pa[1]), fmaxf(pb2[0], pb2[1]));
+#if BEVR_DROP
+#pragma unroll
+          for (int k = 0; k < 2; ++k) {
+            // (n 0xC2B2AE3D is additive in n: the two keys of dword k are 16 s2 + 4 kg + 2 k + {0, 1})
+            const uint32_t kn = kh0 + (uint32_t)(16 * s2 + 2 * k) * 0xC2B2AE3Du;
+            const bool k0 = (bevr_drop_mix(hrow[nb] ^ kn) >> 16) >= drop_thr;
+            const bool k1 = (bevr_drop_mix(hrow[nb] ^ (kn + 0xC2B2AE3Du)) >> 16) >= drop_thr;
+            km[nb][2 * s2 + k] = (k0 ? 0xffffu : 0u) | (k1 ? 0xffff0000u : 0u);
+          }
+#endif
         }
         if constexpr (EXACT) first = false;
       }
 #pragma unroll
       for (int nb = 0; nb < NBX; ++nb) {
         const TapOp<NP> pb = tap_op(pw[nb]);
+#if BEVR_DROP
+        const u32x4 pk[NP] = {pw[nb][0] & km[nb]};      // the kept weights (the EXACT pass rescales pw: masked after it)
+        const TapOp<NP> pkb = tap_op(pk);
+        o_lo[nb] = tap_mm<PREC>(vlo, pkb, o_lo[nb]);
+        o_hi[nb] = tap_mm<PREC>(vhi, pkb, o_hi[nb]);
+#else
         o_lo[nb] = tap_mm<PREC>(vlo, pb, o_lo[nb]);
         o_hi[nb] = tap_mm<PREC>(vhi, pb, o_hi[nb]);
+#endif
         // (split mode: ones . lo + ones . hi, the f32 sum of exactly the values PV contracts)
 #pragma unroll
         for (int pl = NP - 1; pl >= 0; --pl) lacc[nb] = mfma16<PREC>(ones, pb.p[pl], lacc[nb]);
@@ -634,7 +683,11 @@ __global__ __launch_bounds__(512, BEVR_GATHER_WAVES_PER_SIMD) void BEVR_GATHER_K
     if (BAND && !to_end && row >= row_end) continue;      // rows of the next band (no shuffles below)
     // rows past the grid (zero Q rows of the last block) get their O and LSE like any other: the key-side backward
     // walks all Sp rows of a column and needs a finite LSE there; the rows no block covers take the last block's
+#if BEVR_DROP
+    const float inv = (65536.0f / (65536.0f - (float)drop_thr)) / l;      // the kept weights' 1 / (1 - p)
+#else
     const float inv = 1.0f / l;
+#endif
     const size_t mq = (size_t)ph * Mp + (size_t)j * d.Sp + row;
     float* orow = O + mq * 32;
     *reinterpret_cast<f32x4*>(orow + 4 * kg) = o_lo[nb] * inv;
@@ -669,7 +722,7 @@ __global__ __launch_bounds__(512, BEVR_GATHER_WAVES_PER_SIMD) void BEVR_GATHER_K
 template <int PREC>
 int launch(const bevr_attn_desc& d, const void* Q, const void* K, const void* V, const void* key_ws,
            const void* table_pk, const float* mref, float* O, float* LSE, int* flags, int row0, int n_rows,
-           hipStream_t st) {
+           hipStream_t st BEVR_DROP_PARAMS) {
   typedef LdsG L;
   const int n_ph = d.n_prob * d.heads;
   const int grid = ((n_ph + 7) / 8) * 8 * d.S;
@@ -679,7 +732,9 @@ int launch(const bevr_attn_desc& d, const void* Q, const void* K, const void* V,
   const int nb = nblk <= 7 ? 1 : 2;      // row blocks per wave: at most 7 row-block waves + the producer
   const int n_cw = (nblk + nb - 1) / nb;
   const dim3 block(64 * (n_cw + 1));
-#if BEVR_GATHER_ROWS
+#if BEVR_DROP
+#define BEVR_GATHER_ROW_ARGS , row0, n_rows, drop_thr, drop_seed
+#elif BEVR_GATHER_ROWS
 #define BEVR_GATHER_ROW_ARGS , row0, n_rows
 #else
 #define BEVR_GATHER_ROW_ARGS
@@ -719,7 +774,7 @@ int launch(const bevr_attn_desc& d, const void* Q, const void* K, const void* V,
 // The contract of the three gather entry points.  PRECS: the modes this translation unit holds the kernels of.
 template <int... PRECS>
 int run(const bevr_attn_desc* d, const void* Q, const void* K, const void* V, const void* key_ws, const void* table_pk,
-        const float* mref, float* O, float* LSE, int* flags, int row0, int n_rows, void* stream) {
+        const float* mref, float* O, float* LSE, int* flags, int row0, int n_rows, void* stream BEVR_DROP_PARAMS) {
   int rc = bevr_check_desc(d);
   if (rc) return rc;
   if (!Q || !K || !V || !key_ws || !table_pk || !mref || !O || !LSE || !flags) return BEVR_E_NULL;
@@ -729,13 +784,22 @@ int run(const bevr_attn_desc* d, const void* Q, const void* K, const void* V, co
     // a row range is checked after the precision: it starts on a row block and fits the column and one launch
     if (BEVR_GATHER_ROWS && (row0 < 0 || row0 % QB != 0 || n_rows < 1 || n_rows > 14 * QB || n_rows > d->S - row0))
       return (int)BEVR_E_SHAPE;
-    return launch<P()>(*d, Q, K, V, key_ws, table_pk, mref, O, LSE, flags, row0, n_rows, (hipStream_t)stream);
+    return launch<P()>(*d, Q, K, V, key_ws, table_pk, mref, O, LSE, flags, row0, n_rows, (hipStream_t)stream BEVR_DROP_ARGS);
   });
 }
 
 }  // namespace
 
-#if BEVR_GATHER_X3
+#if BEVR_DROP
+extern "C" int bevr_attn_gather_fwd_dropout(const bevr_attn_desc* d, const void* Q, const void* K, const void* V,
+                                            const void* key_ws, const void* table_pk, const float* mref, float* O,
+                                            float* LSE, int* flags, int row0, int n_rows, unsigned drop_thr,
+                                            unsigned drop_seed, void* stream) {
+  if (drop_thr >= 65536u) return BEVR_E_SHAPE;
+  return run<BEVR_PREC_BF16, BEVR_PREC_F16>(d, Q, K, V, key_ws, table_pk, mref, O, LSE, flags, row0, n_rows, stream,
+                                            drop_thr, drop_seed);
+}
+#elif BEVR_GATHER_X3
 extern "C" int bevr_attn_gather_fwd_x3(const bevr_attn_desc* d, const void* Q, const void* K, const void* V,
                                        const void* key_ws, const void* table_pk2, const float* mref, float* O,
                                        float* LSE, int* flags, int row0, int n_rows, void* stream) {

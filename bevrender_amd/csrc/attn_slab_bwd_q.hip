@@ -47,6 +47,13 @@
 // BEVR_SLAB_X3 = 1 (attn_slab_bwd_q_x3.hip, a translation unit of its own for the same reason): BEVR_PREC_BF16X3, S <= 211.
 // This file gives it the constants, the workspace, the preparation kernels, the launch and the entry points
 // (bevr_attn_slab_x3_ws_bytes / _slab_x3_prep / bevr_attn_slab_bwd_q_x3); the kernel body is that file's own.
+//
+// BEVR_DROP = 1 (attn_slab_bwd_q_drop.hip, a translation unit of its own again): attention dropout on the one-band 16-bit
+// kernel, the arithmetic of bevr_attn_bwd_q_dropout: dS = P (keep ? D dP - delta : -delta), one FMA per pair on the dP
+// accumulator (which starts at -delta).  The keys arrive SORTED by b and the mask is a function of the key's index in the
+// caller's order: this unit's preparation (bevr_attn_slab_drop_prep) writes that index into SlabKey::pad, the producer
+// stages index x 0xC2B2AE3D per emission beside the constants, and the key-row loops take it by DPP as they take those.
+// The entry points are bevr_attn_slab_drop_ws_bytes / _slab_drop_prep / bevr_attn_slab_bwd_q_dropout.
 #ifndef BEVR_SLAB_ROWS
 #define BEVR_SLAB_ROWS 0
 #endif
@@ -114,7 +121,12 @@ struct SlabLds {
   static constexpr int OFF_V = K_BYTES;
   static constexpr int OFF_CK = 2 * K_BYTES;
   static constexpr int OFF_CT = OFF_CK + SEK * (int)sizeof(SlabCK);     // 2 x u32x4: {flags, j, amin0, amax0}, {amin1, amax1, 0, 0}
+#if BEVR_DROP
+  static constexpr int OFF_KN = OFF_CT + 32;      // [SEK] u32: the key part of the keep hash, (ORIGINAL key index) 0xC2B2AE3D
+  static constexpr int BUF = OFF_KN + SEK * 4;
+#else
   static constexpr int BUF = OFF_CT + 32;
+#endif
 };
 enum { SF_DONE = 1, SF_FIRST = 2, SF_LAST = 4 };
 
@@ -139,6 +151,11 @@ constexpr int SLAB_BAND_ROWS = SNRB * SQROWS;      // 217
 __host__ __device__ inline int slab_pitch(int S) { return slab_rows(S) <= SLAB_RP_A ? SLAB_RP_A : SLAB_RP_B; }
 #else
 __host__ __device__ inline int slab_pitch(int S) { return SLAB_RP; }
+#endif
+#if BEVR_DROP
+static_assert(!BEVR_SLAB_ROWS && !BEVR_SLAB_X3, "the keep mask: the 16-bit one-band kernel");
+// the widest slab with the staged hash words beside OFF_CK: the workgroup is still the CU's 160 KB
+static_assert((SLAB_W_MAX + 2) * SLAB_RP * SLAB_CELL + 2 * SlabLds::BUF + 64 <= 160 * 1024, "160 KB of LDS");
 #endif
 // first table column any slab has to cover and the number of slabs: X = floor(j rx + b), b clamped as the key prep does
 __host__ __device__ inline int slab_xmin(const bevr_attn_desc& d) { return -(d.Wt / 2 + 2) - 1; }
@@ -190,7 +207,11 @@ __global__ __launch_bounds__(256) void slab_keys_kernel(bevr_attn_desc d, const 
   k.A = (int)c.af;
   k.fy = c.a - c.af;
   k.b = c.b;
+#if BEVR_DROP
+  k.pad = n;      // the key's index in the caller's order: what the keep mask hashes
+#else
   k.pad = 0;
+#endif
   out[t] = k;
 }
 
@@ -262,6 +283,7 @@ __global__ __launch_bounds__(STHREADS, 1) void attn_slab_bwd_q_kernel(
     const int4* __restrict__ items, int* __restrict__ cnt, const char* __restrict__ table_pair,
     const char* __restrict__ dO, const float* __restrict__ LSE, const float* __restrict__ delta,
     const float* __restrict__ grad_scale, float* __restrict__ dQ, float* __restrict__ dtable, int n_slab, int sw, int R
+    BEVR_DROP_PARAMS
 #if BEVR_SLAB_ROWS
     , int row0, int n_rb_band
 #endif
@@ -297,6 +319,11 @@ __global__ __launch_bounds__(STHREADS, 1) void attn_slab_bwd_q_kernel(
   const float kp16 = PREC == BEVR_PREC_F16 ? grad_scale[2] : 0.f, c2_16 = PREC == BEVR_PREC_F16 ? grad_scale[3] : 1.f;
   const float cfix = PREC == BEVR_PREC_F16 ? grad_scale[0] * grad_scale[4] : 1.f;
   const float dq_scale = PREC == BEVR_PREC_F16 ? grad_scale[4] * BEVR_LN2 : ginv;
+#if BEVR_DROP
+  // D: a kept pair's dP is D dP (uniform: kept in a scalar register)
+  const float ksc = __builtin_bit_cast(
+      float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, 65536.0f / (65536.0f - (float)drop_thr))));
+#endif
   PROF_ACC(16);
 
   for (;;) {
@@ -420,6 +447,10 @@ __global__ __launch_bounds__(STHREADS, 1) void attn_slab_bwd_q_kernel(
             ck.cell = 0;
           }
           *reinterpret_cast<SlabCK*>(bb + L::OFF_CK + lane * 16) = ck;
+#if BEVR_DROP
+          // the keys arrive sorted by b: the mask is of the ORIGINAL index (SlabKey::pad, this unit's prep)
+          *reinterpret_cast<unsigned*>(bb + L::OFF_KN + lane * 4) = (unsigned)sk_e.pad * 0xC2B2AE3Du;
+#endif
           // per half: any live key; any live key whose rows leave the window for some row block (the clamped body)
           const bool far = live && (sk_e.A + SLAB_ROW0 < 0 || sk_e.A > d.S - 1 + SLAB_PADR);
           const unsigned long long lm = __ballot(live), fm = __ballot(far);
@@ -469,6 +500,9 @@ __global__ __launch_bounds__(STHREADS, 1) void attn_slab_bwd_q_kernel(
       Frag<PREC> qf, dof;
       float nl = 0.f, nd = 0.f, lse_r = 0.f, dlt_r = 0.f;
       int jcur = -1, jpend = -1;
+#if BEVR_DROP
+      uint32_t hrow = 0u;      // the row part of the keep hash: per column, out of the key-row loops
+#endif
       f32x16 dq;
 #pragma unroll
       for (int r = 0; r < 16; ++r) dq[r] = 0.f;
@@ -505,6 +539,9 @@ __global__ __launch_bounds__(STHREADS, 1) void attn_slab_bwd_q_kernel(
         }
         nl = kp16 - lse_r;
         nd = -dlt;
+#if BEVR_DROP
+        hrow = bevr_drop_row(drop_seed, (uint32_t)ph, (uint32_t)(jpend * d.Sp + qrow));
+#endif
         jcur = jpend;
       };
       // one flush per (slab, column): this wave saw every key of the column's run
@@ -593,6 +630,19 @@ __global__ __launch_bounds__(STHREADS, 1) void attn_slab_bwd_q_kernel(
         };
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
+#if BEVR_DROP
+          // dS = P (keep ? D dP - delta : -delta); dp holds dP - delta, nd = -delta (attn_bwd_q.hip).  Ahead of the half's
+          // key-row loop, which needs dp at once anyway: inside it the hashes of two chains cost more registers than a
+          // wave has (40 bytes of scratch per lane)
+          // (the hash words of the keys bcast_key(lane), taken by DPP like the constants)
+          const unsigned kn = *reinterpret_cast<const unsigned*>(bb + L::OFF_KN + (h * 32 + bcast_key(lane)) * 4);
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const bool keep = (bevr_drop_mix(hrow ^ row_bcast(kn, r)) >> 16) >= drop_thr;
+            dp[h][r] = keep ? fmaf(ksc, dp[h][r] - nd, nd) : nd;
+            if ((r & 3) == 3) __builtin_amdgcn_sched_barrier(0);      // four hashes in flight, not sixteen: registers
+          }
+#endif
           // chain c walks the key rows c * 8 + 0 .. 7 of the accumulator tile
           const u32x4 k = ck[h];
           int o0[2];
@@ -723,7 +773,7 @@ template <int PREC, int RP = SLAB_RP>
 #endif
 int launch(const bevr_attn_desc& d, const void* Q, const void* Ks, const void* Vs, const void* ws, const float* table_pair,
            const void* dO, const float* LSE, const float* delta, const float* grad_scale, float* dQ, float* dtable,
-           int row0, int n_rb_band, hipStream_t st) {
+           int row0, int n_rb_band, hipStream_t st BEVR_DROP_PARAMS) {
   const SlabWs w = slab_ws(d);
   const char* base = static_cast<const char*>(ws);
   int* cnt = reinterpret_cast<int*>(const_cast<char*>(base) + w.off_cnt);
@@ -740,7 +790,7 @@ int launch(const bevr_attn_desc& d, const void* Q, const void* Ks, const void* V
                      (const char*)Ks, (const char*)Vs, reinterpret_cast<const SlabKey*>(base),
                      reinterpret_cast<const int*>(base + w.off_beg), reinterpret_cast<const int*>(base + w.off_end),
                      reinterpret_cast<const int4*>(base + w.off_items), cnt, (const char*)table_pair, (const char*)dO,
-                     LSE, delta, grad_scale, dQ, dtable, w.n_slab, w.sw, R
+                     LSE, delta, grad_scale, dQ, dtable, w.n_slab, w.sw, R BEVR_DROP_ARGS
 #if BEVR_SLAB_ROWS
                      , row0, n_rb_band
 #endif
@@ -780,8 +830,14 @@ bool slab_shape_ok(const bevr_attn_desc& d) {
   return is16(d.precision) && slab_n_rb(d.S) <= SNRB && slab_rows(d.S) <= SLAB_RP && SLAB_CH <= 64 &&
          slab_lds_bytes(d.S, slab_width(d.S)) <= 160 * 1024;
 }
+#if BEVR_DROP
+// a preparation of this unit's own: it writes SlabKey::pad, and bevr_attn_slab_prep's code stays what it is
+#define SLAB_WS_BYTES bevr_attn_slab_drop_ws_bytes
+#define SLAB_PREP bevr_attn_slab_drop_prep
+#else
 #define SLAB_WS_BYTES bevr_attn_slab_ws_bytes
 #define SLAB_PREP bevr_attn_slab_prep
+#endif
 #endif
 
 // The contract of the three slab bwd_q entry points.  PRECS: the modes this translation unit holds the kernels of;
@@ -789,7 +845,7 @@ bool slab_shape_ok(const bevr_attn_desc& d) {
 template <int... PRECS>
 int run(const bevr_attn_desc* d, const void* Q, const void* Ks, const void* Vs, const void* slab_ws_,
         const float* table_pair, const void* dO, const float* LSE, const float* delta, const float* grad_scale, float* dQ,
-        float* dtable, int row0, int n_rows, void* stream) {
+        float* dtable, int row0, int n_rows, void* stream BEVR_DROP_PARAMS) {
   int rc = bevr_check_desc(d);
   if (rc) return rc;
   if (!Q || !Ks || !Vs || !slab_ws_ || !table_pair || !dO || !LSE || !delta || !grad_scale || !dQ || !dtable)
@@ -806,7 +862,8 @@ int run(const bevr_attn_desc* d, const void* Q, const void* Ks, const void* Vs, 
     const int nb = (n_rows + SQROWS - 1) / SQROWS;
     auto go = [&](auto RP) {
       return launch<decltype(P)::value, decltype(RP)::value>(*d, Q, Ks, Vs, slab_ws_, table_pair, dO, LSE, delta,
-                                                             grad_scale, dQ, dtable, row0, nb, (hipStream_t)stream);
+                                                             grad_scale, dQ, dtable, row0, nb, (hipStream_t)stream
+                                                             BEVR_DROP_ARGS);
     };
 #if BEVR_SLAB_ROWS
     return slab_pitch(d->S) == SLAB_RP_B ? go(std::integral_constant<int, SLAB_RP_B>())
@@ -861,6 +918,15 @@ extern "C" int bevr_attn_slab_bwd_q_x3(const bevr_attn_desc* d, const void* Q, c
                                        const void* slab_ws_, const float* table_pair, const void* dO, const float* LSE,
                                        const float* delta, const float* grad_scale, float* dQ, float* dtable, void* stream) {
   return run<BEVR_PREC_BF16X3>(d, Q, Ks, Vs, slab_ws_, table_pair, dO, LSE, delta, grad_scale, dQ, dtable, 0, 0, stream);
+}
+#elif BEVR_DROP
+extern "C" int bevr_attn_slab_bwd_q_dropout(const bevr_attn_desc* d, const void* Q, const void* Ks, const void* Vs,
+                                            const void* slab_ws_, const float* table_pair, const void* dO,
+                                            const float* LSE, const float* delta, const float* grad_scale, float* dQ,
+                                            float* dtable, unsigned drop_thr, unsigned drop_seed, void* stream) {
+  if (drop_thr >= 65536u) return BEVR_E_SHAPE;
+  return run<BEVR_PREC_BF16, BEVR_PREC_F16>(d, Q, Ks, Vs, slab_ws_, table_pair, dO, LSE, delta, grad_scale, dQ, dtable, 0, 0,
+                                            stream, drop_thr, drop_seed);
 }
 #else
 extern "C" int bevr_attn_slab_bwd_q(const bevr_attn_desc* d, const void* Q, const void* Ks, const void* Vs,

@@ -1,0 +1,5 @@
+// Slab query-side backward with attention dropout: the same source as attn_slab_bwd_q.hip, compiled with the keep-mask
+// blocks in (bevr_common.h: bevr_drop_keep) -- a separate translation unit so that the kernels and the preparation
+// without dropout are unchanged.
+#define BEVR_DROP 1
+#include "attn_slab_bwd_q.hip"

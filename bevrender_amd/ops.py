@@ -538,9 +538,11 @@ class K:
     FWD, FWD_DROP = "bevr_attn_fwd", "bevr_attn_fwd_dropout"
     GATHER, GATHER_ROWS = "bevr_attn_gather_fwd", "bevr_attn_gather_fwd_rows"
     GATHER_X3 = "bevr_attn_gather_fwd_x3"
+    GATHER_DROP = "bevr_attn_gather_fwd_dropout"
     BWD_Q, BWD_Q_DROP, SLAB_BWD_Q = "bevr_attn_bwd_q", "bevr_attn_bwd_q_dropout", "bevr_attn_slab_bwd_q"
     SLAB_BWD_Q_ROWS = "bevr_attn_slab_bwd_q_rows"
     SLAB_BWD_Q_X3 = "bevr_attn_slab_bwd_q_x3"
+    SLAB_BWD_Q_DROP = "bevr_attn_slab_bwd_q_dropout"
     BWD_K, BWD_K_DROP = "bevr_attn_bwd_k", "bevr_attn_bwd_k_dropout"
     CELL_FWD, CELL_BWD_Q, CELL_BWD_K = "bevr_attn_cell_fwd", "bevr_attn_cell_bwd_q", "bevr_attn_cell_bwd_k"
     TAP_FWD, TAP_FWD_DROP = "bevr_attn_tap_fwd", "bevr_attn_tap_fwd_dropout"
@@ -591,8 +593,12 @@ def attention_route(precision: int, groups: int, S: int, Wt: int, N: int, cell_s
     C, heads: the channels.  keys_in_tap_grid(split) -> bool: the ONE data-dependent input, "do the keys [split, N) all
     sample inside the tap grid?" (a reduction and a host sync at the caller): called at most once, and only for
     tap_source=True with dropout and a split that would otherwise be kept.  Raises attention_core's routing ValueErrors.
-    Reads the A/B switches itself (BEVR_KNORM, BEVR_MERGE_TAP) or through gather_supported, slab_supported,
-    slab_rows_supported, tap_supported and kv_source_supported."""
+    Reads the A/B switches itself (BEVR_KNORM, BEVR_MERGE_TAP, BEVR_SCATTER_DROP) or through gather_supported,
+    slab_supported, slab_rows_supported, tap_supported and kv_source_supported.
+    BEVR_SCATTER_DROP (default SCATTER_DROP_DEFAULT: off; tests/test_scatter_dropout_routes_cpu.py): with a keep mask, in
+    the 16-bit modes, the region segment's forward is the gather kernel with the mask (K.GATHER_DROP) where
+    gather_supported holds and its bwd_q the slab kernel with the mask (K.SLAB_BWD_Q_DROP) where slab_supported holds;
+    the key-side backward stays K.BWD_K_DROP.  Unset or 0: the region dropout kernels, as before these two had a mask."""
     # tap_pix with a keep mask (the split-bf16 mode behind BEVR_TAP_X3_DROP) follows kv_source's rules below, but where
     # those would drop the split it has no projected rows of the pinned keys to fall back to: ValueError
     # (the split mode alone: tap_pix is its route -- the 16-bit modes have the fused K | V source and keep refusing)
@@ -636,8 +642,16 @@ def attention_route(precision: int, groups: int, S: int, Wt: int, N: int, cell_s
         n_region = N
     segs, gather = [], None
     if n_region > 0:
-        if dropout:     # the keep mask lives in the query-tile kernels: no gather forward, no slab backward
-            segs.append(KeySegment("region", 0, n_region, K.FWD_DROP, K.BWD_Q_DROP, K.BWD_K_DROP))
+        if dropout:     # the keep mask lives in the query-tile kernels: no gather forward, no slab backward ...
+            fwd, bwd_q = K.FWD_DROP, K.BWD_Q_DROP
+            # ... unless BEVR_SCATTER_DROP asks for the masked gather / slab kernels (16-bit modes, the one-band slab)
+            if scatter_drop() and precision in (_lib.PREC_BF16, _lib.PREC_F16):
+                if gather_supported(precision, S):
+                    gather = "whole" if len(gather_bands(S)) == 1 else "bands"
+                    fwd = K.GATHER_DROP             # one entry point, whole columns as the range (0, S)
+                if slab_supported(precision, S, Wt):
+                    bwd_q = K.SLAB_BWD_Q_DROP
+            segs.append(KeySegment("region", 0, n_region, fwd, bwd_q, K.BWD_K_DROP))
         else:
             if gather_supported(precision, S):
                 gather = "whole" if len(gather_bands(S)) == 1 else "bands"
@@ -683,6 +697,15 @@ def gather_supported(precision, S) -> bool:
     return precision in (_lib.PREC_BF16, _lib.PREC_F16)
 
 
+def scatter_drop() -> bool:
+    """With a keep mask, do the scattered keys of the 16-bit modes run on the gather forward and the slab bwd_q with the
+    mask (csrc/attn_gather_fwd_drop.hip, csrc/attn_slab_bwd_q_drop.hip) where gather_supported / slab_supported hold?
+    BEVR_SCATTER_DROP, default SCATTER_DROP_DEFAULT: off -- the region dropout kernels, the routing before these kernels
+    had a mask -- until the pinned route table changes with it.  Same mask, same results up to the kernels' rounding."""
+    return os.environ.get("BEVR_SCATTER_DROP", SCATTER_DROP_DEFAULT) != "0"
+
+
+SCATTER_DROP_DEFAULT = "0"                        # BEVR_SCATTER_DROP when unset (scatter_drop)
 GATHER_MAX_S, GATHER_BAND_ROWS = 448, 224
 GATHER_X3_DEFAULT = "0"                           # BEVR_GATHER_X3 when unset (gather_supported)
 
@@ -789,7 +812,7 @@ def _fwd_cell(name, o):
             _ptr(o.LSE), _stream(), flops=_attn_flops(o.g, 2), tag=_call_tag(o.g))
 
 
-def _fwd_gather(name, o):
+def _fwd_gather(name, o, drop=(), timer=K.GATHER):
     g, Ttc = o.g, o.Ttc
     x3 = name == K.GATHER_X3
     # (h, Wp, Hp, 2) 16-bit: one dword per (column, row) entry; split mode: a plane of hi parts and one of lo parts
@@ -809,13 +832,19 @@ def _fwd_gather(name, o):
         kmx = torch.linalg.vector_norm(o.Ke[:, :, :g.N], dim=-1, dtype=torch.float32).amax(-1)    # (B', h)
     ub = 1.01 * (qn.repeat_interleave(g.q_div, 0) * kmx[..., None] + tmax[None, :, None]) + 0.01
     mref = (ub - tap_headroom(g.precision)).contiguous()
-    bands = gather_bands(g.S) if name in (K.GATHER_ROWS, K.GATHER_X3) else [()]
+    bands = gather_bands(g.S) if name in (K.GATHER_ROWS, K.GATHER_X3, K.GATHER_DROP) else [()]
     # scratch of one call's two passes: zeroed per call (per band)
     gflags = torch.zeros(len(bands), g.n_prob * g.heads * g.S, device=o.O.device, dtype=torch.int32)
     for bi, rows in enumerate(bands):       # rows = (row0, n_rows); (the timer's name is the route's, whichever entry point runs it)
         flops = _attn_flops(g, 2) * rows[1] / g.S if rows else _attn_flops(g, 2)
         _launch(name, C.byref(o.desc), _ptr(o.Qe), _ptr(o.Ke), _ptr(o.Ve), _ptr(o.key_ws), _ptr(pair_pk), _ptr(mref),
-                _ptr(o.O), _ptr(o.LSE), _ptr(gflags[bi]), *rows, _stream(), flops=flops, tag=_call_tag(g), timer=K.GATHER)
+                _ptr(o.O), _ptr(o.LSE), _ptr(gflags[bi]), *rows, *drop, _stream(), flops=flops, tag=_call_tag(g),
+                timer=timer)
+
+
+def _fwd_gather_drop(name, o):
+    """the gather forward with the keep mask: _fwd_gather's operands and bands, then (thr16, seed)"""
+    _fwd_gather(name, o, drop=o.drop, timer=name)
 
 
 def _bwd_q_tile(name, o):
@@ -850,6 +879,16 @@ def _bwd_q_slab(name, o):
     _launch(name, C.byref(o.desc), _ptr(o.Qe), _ptr(Ks), _ptr(Vs), _ptr(sws), _ptr(o.pair), _ptr(o.dOe), _ptr(o.LSE),
             _ptr(o.delta), _ptr(o.gscale), _ptr(o.dQ), _ptr(o.dT), _stream(), flops=_attn_flops(g, 3), tag=_call_tag(g),
             timer=K.SLAB_BWD_Q)
+
+
+def _bwd_q_slab_drop(name, o):
+    """the slab bwd_q with the keep mask: the workspace of its own prep carries the keys' indices in the caller's order
+    (what the mask hashes); the cotangent is the unscaled one, D enters in the kernel"""
+    g = o.g
+    Ks, Vs, sws = _slab_operands(o, "bevr_attn_slab_drop_ws_bytes", "bevr_attn_slab_drop_prep")
+    _launch(name, C.byref(o.desc), _ptr(o.Qe), _ptr(Ks), _ptr(Vs), _ptr(sws), _ptr(o.pair), _ptr(o.dOe), _ptr(o.LSE),
+            _ptr(o.delta), _ptr(o.gscale), _ptr(o.dQ), _ptr(o.dT), *o.drop, _stream(), flops=_attn_flops(g, 3),
+            tag=_call_tag(g))
 
 
 def _bwd_q_slab_rows(name, o):
@@ -918,9 +957,9 @@ def _tap_bwd_k(name, o):
 
 
 _RUN = {K.FWD: _fwd_tile, K.FWD_DROP: _fwd_tile, K.GATHER: _fwd_gather, K.GATHER_ROWS: _fwd_gather,
-        K.GATHER_X3: _fwd_gather, K.CELL_FWD: _fwd_cell,
+        K.GATHER_X3: _fwd_gather, K.GATHER_DROP: _fwd_gather_drop, K.CELL_FWD: _fwd_cell,
         K.BWD_Q: _bwd_q_tile, K.BWD_Q_DROP: _bwd_q_tile, K.CELL_BWD_Q: _bwd_q_tile, K.SLAB_BWD_Q: _bwd_q_slab,
-        K.SLAB_BWD_Q_ROWS: _bwd_q_slab_rows, K.SLAB_BWD_Q_X3: _bwd_q_slab,
+        K.SLAB_BWD_Q_ROWS: _bwd_q_slab_rows, K.SLAB_BWD_Q_X3: _bwd_q_slab, K.SLAB_BWD_Q_DROP: _bwd_q_slab_drop,
         K.BWD_K: _bwd_k_tile, K.BWD_K_DROP: _bwd_k_tile, K.CELL_BWD_K: _bwd_k_cell,
         K.TAP_FWD: _tap_fwd, K.TAP_FWD_DROP: _tap_fwd, K.TAP_BWD_Q: _tap_bwd_q, K.TAP_BWD_Q_DROP: _tap_bwd_q,
         K.TAP_BWD_K: _tap_bwd_k, K.TAP_BWD_K_DROP: _tap_bwd_k,

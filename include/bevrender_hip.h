@@ -69,7 +69,10 @@ extern "C" {
  *    BEVR_PREC_BF16X3, S <= 211; the 16-bit slab entry points keep returning BEVR_E_PRECISION for that mode);
  *    bevr_attn_tap_fwd_x3_dropout, bevr_attn_tap_bwd_q_x3_dropout, bevr_attn_tap_bwd_k_x3_dropout (attention dropout on
  *    the tap entry points in BEVR_PREC_BF16X3; the three _dropout entry points keep returning BEVR_E_PRECISION for that
- *    mode). */
+ *    mode);
+ *    bevr_attn_gather_fwd_dropout (the gather forward with the keep mask, over a row range) and
+ *    bevr_attn_slab_drop_ws_bytes / _slab_drop_prep / bevr_attn_slab_bwd_q_dropout (the slab query-side backward with
+ *    the keep mask, S <= 211), both in the 16-bit modes; every other gather and slab entry point keeps its contract. */
 #define BEVR_ABI_VERSION 6
 
 enum {
@@ -229,8 +232,11 @@ int bevr_attn_bwd_k_ws(const bevr_attn_desc* d, const void* Q, const void* Qt, c
  * D = 65536 / (65536 - drop_thr): s D Pmax bound <= 2^30; fp16: D Pmax 2^kp <= 2^14 and D Pmax bound 2^kp c2 <= 2^14
  * (|D dP - delta| <= D bound: the fixed-point contributions and the fp16 operands D P', P' (D dP - delta) c2 stay in
  * range).  The forward applies D after the normalisation, to the output (its fp16 operands are the unscaled weights).
- * bevrender_amd/ops.py:dropout_keep_mask is the host twin.  The cell, gather and slab entry points have no mask: a
- * caller with dropout keeps their keys on these entry points; the tap entry points have dropout variants of their own
+ * bevrender_amd/ops.py:dropout_keep_mask is the host twin.  The cell entry points have no mask: a caller with dropout
+ * keeps their keys on these entry points.  The gather forward and the one-band slab bwd_q have dropout variants in the
+ * 16-bit modes (bevr_attn_gather_fwd_dropout, bevr_attn_slab_bwd_q_dropout below: the same mask over the same key
+ * numbering, so either may stand in for its region counterpart beside the other two); the split-bf16 gather, the
+ * row-band and the split-bf16 slab entry points have none.  The tap entry points have dropout variants of their own
  * (bevr_attn_tap_*_dropout below), which hash the same function with an offset into the caller's key order. */
 int bevr_attn_fwd_dropout(const bevr_attn_desc* d, const void* Q, const void* K, const void* Vt,
                           const void* key_ws, const float* table_pair, float* O, float* LSE,
@@ -479,6 +485,19 @@ int bevr_attn_gather_fwd_rows(const bevr_attn_desc* d, const void* Q, const void
 int bevr_attn_gather_fwd_x3(const bevr_attn_desc* d, const void* Q, const void* K, const void* V,
                             const void* key_ws, const void* table_pk2, const float* mref, float* O, float* LSE,
                             int* flags, int row0, int n_rows, void* stream);
+/* bevr_attn_gather_fwd_rows with the keep mask of bevr_attn_fwd_dropout (csrc/attn_gather_fwd_drop.hip), over the BEV rows
+ * [row0, row0 + n_rows) of every column; a whole column of S <= 224 rows is the range (0, S).  Operands, the order of the
+ * checks, the row-range contract, flags and the padding rows as bevr_attn_gather_fwd_rows (BEVR_PREC_BF16 and
+ * BEVR_PREC_F16; else BEVR_E_PRECISION); drop_thr = round(p * 65536) < 65536, else BEVR_E_SHAPE (checked first).  Pair
+ * (ph, mq, n) is kept iff the hash of "Attention dropout" above says so, with n the key's index in the caller's key order
+ * (K's row) and mq = j * Sp + i of the ABSOLUTE BEV row i, whichever band the call computes: the bands of a column, the
+ * masked strip emissions of a wide key tile and the second pass over flagged columns all evaluate one mask.  Semantics of
+ * bevr_attn_fwd_dropout: softmax first -- both LSE planes and the row sum are of ALL the (rounded) weights and equal
+ * those of bevr_attn_gather_fwd_rows --, the product with V contracts the kept weights, and D = 65536 / (65536 - drop_thr)
+ * multiplies O after the normalisation (the fp16 operands stay the unscaled weights). */
+int bevr_attn_gather_fwd_dropout(const bevr_attn_desc* d, const void* Q, const void* K, const void* V,
+                                 const void* key_ws, const void* table_pk, const float* mref, float* O, float* LSE,
+                                 int* flags, int row0, int n_rows, unsigned drop_thr, unsigned drop_seed, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * SLAB entry points (csrc/attn_slab_bwd_q.hip): bevr_attn_bwd_q -- dQ and the rpe-table gradient of a key segment, same
@@ -540,6 +559,25 @@ int bevr_attn_slab_x3_prep(const bevr_attn_desc* d, const float* key_a, const fl
 int bevr_attn_slab_bwd_q_x3(const bevr_attn_desc* d, const void* Q, const void* Ks, const void* Vs, const void* slab_ws,
                             const float* table_pair, const void* dO, const float* LSE, const float* delta,
                             const float* grad_scale, float* dQ, float* dtable, void* stream);
+/* bevr_attn_slab_bwd_q with the keep mask of bevr_attn_bwd_q_dropout (csrc/attn_slab_bwd_q_drop.hip), 16-bit modes,
+ * S <= 211.  The keys arrive sorted by b, and the mask is of the key's index in the CALLER's order, n = order[pg][t] for
+ * sorted position t: the workspace carries that index, so it has entry points of its own.
+ *   bevr_attn_slab_drop_ws_bytes / _slab_drop_prep: as bevr_attn_slab_ws_bytes / _slab_prep (same checks and results);
+ *           not interchangeable with the other slab workspaces.
+ *   bevr_attn_slab_bwd_q_dropout: operands and checks of bevr_attn_slab_bwd_q, in its order, after drop_thr < 65536
+ *           (else BEVR_E_SHAPE).  Per pair dS = P (keep ? D dP - delta : -delta), D = 65536 / (65536 - drop_thr), applied
+ *           by the kernel to the dP accumulator: dO is the UNSCALED cotangent (the operand bevr_attn_bwd_k_dropout takes)
+ *           and delta = rowsum(dO * O) of it; grad_scale as for bevr_attn_bwd_q_dropout, every Pmax of the contract read
+ *           as D Pmax (fp16: the c2 and headroom rules of "Attention dropout" above).  The result is that of
+ *           bevr_attn_bwd_q_dropout on the same keys in the caller's order, up to the order of the float atomics and one
+ *           rounding of the tap weights. */
+size_t bevr_attn_slab_drop_ws_bytes(const bevr_attn_desc* d);
+int bevr_attn_slab_drop_prep(const bevr_attn_desc* d, const float* key_a, const float* key_b, const int32_t* order,
+                             void* slab_ws, void* stream);
+int bevr_attn_slab_bwd_q_dropout(const bevr_attn_desc* d, const void* Q, const void* Ks, const void* Vs,
+                                 const void* slab_ws, const float* table_pair, const void* dO, const float* LSE,
+                                 const float* delta, const float* grad_scale, float* dQ, float* dtable,
+                                 unsigned drop_thr, unsigned drop_seed, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Bilinear feature sampling, align_corners=True, zero padding (grid_sample semantics).

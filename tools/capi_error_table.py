@@ -1,4 +1,5 @@
-"""The error contract of the attention entry points, as a table: tests/golden/capi_error_codes.json.
+"""The error contract of the attention entry points, as a table: tests/golden/capi_error_codes.json (and, for entry
+points added after it was recorded, a table per group beside it: LATER).
 
 `python tools/capi_error_table.py` calls every attention entry point that takes a descriptor with one defect and with
 every pair of defects of different classes, and records the code each call returns.  The pairs pin the ORDER of the
@@ -38,15 +39,31 @@ SIZE_LIMITS = {
 }
 
 
-def entry_points(L):
-    """Every bevr_attn_* symbol whose first argument is the descriptor and whose result is an int code."""
+# Entry points added AFTER capi_error_codes.json was recorded.  That table is a record of the library at one point and stays
+# what it is; a later group's rows -- the same cases, built by the same functions -- go into a table of its own, beside the
+# test file that came with the group: {group: (table file under tests/golden, its entry points)}.
+LATER = {
+    "scatter_dropout": ("scatter_dropout_error_codes.json",
+                        ("bevr_attn_gather_fwd_dropout", "bevr_attn_slab_drop_prep", "bevr_attn_slab_bwd_q_dropout")),
+}
+
+
+def later_table(group):
+    return os.path.join(os.path.dirname(TABLE), LATER[group][0])
+
+
+def entry_points(L, group=None):
+    """Every bevr_attn_* symbol whose first argument is the descriptor and whose result is an int code: those of the
+    recorded table (group None: all but the LATER groups), or those of one LATER group."""
     dp = C.POINTER(_lib.AttnDesc)
+    later = {n for _, names in LATER.values() for n in names}
     out = []
     for name in _lib.SYMBOLS:
         fn = getattr(L, name)
         if (name.startswith("bevr_attn_") and name != "bevr_attn_table_dims" and fn.restype is C.c_int
                 and fn.argtypes and fn.argtypes[0] is dp):
-            out.append(name)
+            if (name in LATER[group][1]) if group else (name not in later):
+                out.append(name)
     return out
 
 
@@ -139,9 +156,9 @@ def cases(L, name):
     return out
 
 
-def table(L):
+def table(L, group=None):
     entries = {}
-    for name in entry_points(L):
+    for name in entry_points(L, group):
         cs = cases(L, name)
         entries[name] = {
             "cases": len(cs),
@@ -156,12 +173,13 @@ def main():
     import torch
     if torch.cuda.is_available():
         sys.exit("run this without a GPU: the accepted cases reach a launch with made-up pointers")
-    t = table(_lib.lib())
-    with open(TABLE, "w") as f:
-        json.dump(t, f, indent=1)
-        f.write("\n")
-    n = sum(e["cases"] for e in t["entry_points"].values())
-    print(f"{len(t['entry_points'])} entry points, {n} cases -> {TABLE}")
+    for group, path in [(None, TABLE)] + [(g, later_table(g)) for g in LATER]:
+        t = table(_lib.lib(), group)
+        with open(path, "w") as f:
+            json.dump(t, f, indent=1)
+            f.write("\n")
+        n = sum(e["cases"] for e in t["entry_points"].values())
+        print(f"{len(t['entry_points'])} entry points, {n} cases -> {path}")
 
 
 if __name__ == "__main__":
