@@ -33,6 +33,7 @@ SYMBOLS = [
     "bevr_attn_tap_fwd_x3_dropout", "bevr_attn_tap_bwd_q_x3_dropout", "bevr_attn_tap_bwd_k_x3_dropout",
     "bevr_attn_gather_fwd_dropout", "bevr_attn_slab_drop_ws_bytes", "bevr_attn_slab_drop_prep",
     "bevr_attn_slab_bwd_q_dropout",
+    "bevr_kv_project_w2",
     "bevr_offset_head_fwd", "bevr_offset_head_bwd", "bevr_key_positions_fwd", "bevr_key_positions_bwd", "bevr_kv_project", "bevr_layernorm_fwd", "bevr_layernorm_bwd", "bevr_merge_views_fwd", "bevr_merge_views_bwd", "bevr_merge_tap_fwd", "bevr_merge_tap_bwd", "bevr_attn_bwd_prep", "bevr_pack_kv", "bevr_unpack_dkv",
 ]
 
@@ -145,6 +146,7 @@ def lib() -> C.CDLL:
         L.bevr_layernorm_fwd.argtypes = [fp] * 6 + [C.c_longlong, ip, C.c_float, vp]
         L.bevr_layernorm_bwd.argtypes = [fp] * 8 + [C.c_longlong, ip, vp]
         L.bevr_kv_project.argtypes = [vp, ip, fp, C.c_longlong, vp, fp] + [ip] * 9 + [vp] * 6 + [ip, vp]
+        L.bevr_kv_project_w2.argtypes = [vp, ip, fp, C.c_longlong, vp, ip, fp] + [ip] * 9 + [vp] * 6 + [ip, vp]
         L.bevr_key_positions_fwd.argtypes = [fp, fp, vp, fp] + [ip] * 8 + [C.c_float, C.c_float, vp]
         L.bevr_key_positions_bwd.argtypes = [fp, fp, vp, fp, fp] + [ip] * 8 + [C.c_float, C.c_float, vp]
         L.bevr_pack_kv.argtypes = [fp, fp, C.c_longlong, C.c_longlong] + [ip] * 6 + [vp] * 5

@@ -573,6 +573,7 @@ class AttnRoute:
     gather: Optional[str]   # the gather forward of the region segment: "whole", "bands" (gather_bands) or None
     kn2: bool               # bevr_kv_project emits the largest squared K row norm (the gather forward's reference)
     merge: str              # "merge_tap" (region + tap halves, the tap half's O formed on the way) or "merge_views"
+    wsplit: bool = False    # the fused K | V source takes its weights as two E planes (bevr_kv_project_w2, kv_wsplit)
 
     @property
     def tap(self) -> bool:
@@ -594,7 +595,8 @@ def attention_route(precision: int, groups: int, S: int, Wt: int, N: int, cell_s
     sample inside the tap grid?" (a reduction and a host sync at the caller): called at most once, and only for
     tap_source=True with dropout and a split that would otherwise be kept.  Raises attention_core's routing ValueErrors.
     Reads the A/B switches itself (BEVR_KNORM, BEVR_MERGE_TAP, BEVR_SCATTER_DROP) or through gather_supported,
-    slab_supported, slab_rows_supported, tap_supported and kv_source_supported.
+    slab_supported, slab_rows_supported, tap_supported, kv_source_supported and kv_wsplit (BEVR_KV_WSPLIT: `wsplit`, the
+    one field it changes, and only for source == "kv_source").
     BEVR_SCATTER_DROP (default SCATTER_DROP_DEFAULT: off; tests/test_scatter_dropout_routes_cpu.py): with a keep mask, in
     the 16-bit modes, the region segment's forward is the gather kernel with the mask (K.GATHER_DROP) where
     gather_supported holds and its bwd_q the slab kernel with the mask (K.SLAB_BWD_Q_DROP) where slab_supported holds;
@@ -679,7 +681,9 @@ def attention_route(precision: int, groups: int, S: int, Wt: int, N: int, cell_s
     # (the fused merge_tap assumes a kept mass of 1: no mask)
     fused_merge = (tap and split > 0 and not dropout and (C // heads) % 4 == 0
                    and os.environ.get("BEVR_MERGE_TAP", "1") != "0")
-    return AttnRoute(tuple(segs), split, gather, kn2, "merge_tap" if fused_merge else "merge_views")
+    # split (hi + lo) projection weights for the fused source: off unless BEVR_KV_WSPLIT asks for them
+    wsplit = source == "kv_source" and kv_wsplit()
+    return AttnRoute(tuple(segs), split, gather, kn2, "merge_tap" if fused_merge else "merge_views", wsplit)
 
 
 def gather_supported(precision, S) -> bool:
@@ -1020,7 +1024,10 @@ class _AttnCore(torch.autograd.Function):
         if fused:
             feat, spos = feat.contiguous(), spos.float().contiguous()
             N, C2 = spos.shape[1], 2 * feat.shape[-1]
-            W_e = Wkv.detach().to(ed).contiguous()
+            if route.wsplit:        # two E planes, hi | lo (bevr_kv_project_w2)
+                W_e, lo_exp = kv_split_weights(Wkv, geom.precision)
+            else:
+                W_e = Wkv.detach().to(ed).contiguous()
             vn2 = torch.zeros(1, device=Qp.device, dtype=torch.float32)   # largest squared V row norm (kv_project)
             b_f = None if bkv is None else bkv.detach().float().contiguous()
         else:
@@ -1054,10 +1061,14 @@ class _AttnCore(torch.autograd.Function):
                 # reference of the gather forward needs it (a pass over K otherwise)
                 if route.kn2 and sg.kind == "region":
                     kn2 = torch.zeros(g.n_prob, g.heads, device=dev, dtype=torch.float32)
-                _launch("bevr_kv_project", _ptr(feat), int(feat.dtype == torch.bfloat16),
-                        C.c_void_p(spos.data_ptr() + sg.n0 * 8), N, _ptr(W_e), _ptr(b_f), nb, Hi, Wi, Cc, g.N, g.Np, g.heads, c,
+                # the split-weight form: its own library symbol and one more argument, the plain form's timer name
+                # (bench.py --full and the profile tooling find the projection's time under it)
+                entry = "bevr_kv_project_w2" if route.wsplit else "bevr_kv_project"
+                _launch(entry, _ptr(feat), int(feat.dtype == torch.bfloat16),
+                        C.c_void_p(spos.data_ptr() + sg.n0 * 8), N, _ptr(W_e), *((lo_exp,) if route.wsplit else ()),
+                        _ptr(b_f), nb, Hi, Wi, Cc, g.N, g.Np, g.heads, c,
                         g.precision, _ptr(Ke), _ptr(Ve), _ptr(Kt), _ptr(Vt), _ptr(vn2) if need_bwd else None, _ptr(kn2),
-                        g.groups, _stream(), flops=0.0,
+                        g.groups, _stream(), flops=0.0, timer="bevr_kv_project",
                         nbytes=float(feat.numel() * feat.element_size() + 8 * nb * g.N + (4 if need_bwd else 3) * Ke.numel() * 2))
             else:
                 kp = kv.data_ptr() + sg.n0 * C2 * 4
@@ -1557,6 +1568,34 @@ def kv_source_supported(C: int, heads: int, groups: int, precision: int) -> bool
     return (groups >= 1 and C % groups == 0 and (C // groups) % 4 == 0 and precision in (_lib.PREC_BF16, _lib.PREC_F16)
             and C % 16 == 0 and C <= 256 and C % heads == 0 and C // heads <= 32
             and os.environ.get("BEVR_FUSED_KV", "1") != "0")
+
+
+def kv_wsplit() -> bool:
+    """Does the fused K | V source take its weights as two E planes (bevr_kv_project_w2: hi + lo, kv_split_weights)?
+    A weight rounded to E is an error common to all keys, which the attention's average over the keys does not shrink
+    (DESIGN.md 3.1); the split removes it at twice the projection's matrix work.  BEVR_KV_WSPLIT, default
+    KV_WSPLIT_DEFAULT: off -- the rounded weights of bevr_kv_project, the routing before the split form -- until the
+    pinned tables change with it.  Only attention_route reads it."""
+    return os.environ.get("BEVR_KV_WSPLIT", KV_WSPLIT_DEFAULT) != "0"
+
+
+KV_WSPLIT_DEFAULT = "0"                           # BEVR_KV_WSPLIT when unset (kv_wsplit)
+KV_WSPLIT_LO_EXP = {_lib.PREC_BF16: 0, _lib.PREC_F16: 11}
+
+
+def kv_split_weights(Wkv: torch.Tensor, precision: int):
+    """The weight operand of bevr_kv_project_w2 (include/bevrender_hip.h: Wkv2) from the float weights (2C, C):
+    (planes, lo_exp) with planes (2, 2C, C) E, plane 0 = hi = E(w), plane 1 = E((w - hi) 2^lo_exp).  lo_exp is 0 for
+    bf16 (float's exponent range) and 11 for fp16: the residual of a weight around 1e-3 is subnormal or zero as a plain
+    fp16 value, eleven binades up it is as well placed as hi.  hi + plane 1 * 2^-lo_exp reproduces w to 2^-16 (bf16) /
+    2^-21 (fp16) relative.  Any device."""
+    if precision not in KV_WSPLIT_LO_EXP:
+        raise ValueError("kv_split_weights needs a 16-bit operand mode")
+    ed, lo_exp = _edtype(precision), KV_WSPLIT_LO_EXP[precision]
+    w = Wkv.detach().float()
+    hi = w.to(ed)
+    lo = ((w - hi.float()) * 2.0 ** lo_exp).to(ed)
+    return torch.stack((hi, lo)).contiguous(), lo_exp
 
 
 class _Sample(torch.autograd.Function):

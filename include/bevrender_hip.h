@@ -72,7 +72,9 @@ extern "C" {
  *    mode);
  *    bevr_attn_gather_fwd_dropout (the gather forward with the keep mask, over a row range) and
  *    bevr_attn_slab_drop_ws_bytes / _slab_drop_prep / bevr_attn_slab_bwd_q_dropout (the slab query-side backward with
- *    the keep mask, S <= 211), both in the 16-bit modes; every other gather and slab entry point keeps its contract. */
+ *    the keep mask, S <= 211), both in the 16-bit modes; every other gather and slab entry point keeps its contract;
+ *    bevr_kv_project_w2 (bevr_kv_project with the weights as two E planes, hi + lo; bevr_kv_project keeps its
+ *    contract). */
 #define BEVR_ABI_VERSION 6
 
 enum {
@@ -755,6 +757,27 @@ int bevr_kv_project(const void* feat, int feat_bf16, const float* pos, long long
                     const float* bkv, int nb, int Hi, int Wi, int C, int N, int Np, int heads, int c, int precision,
                     void* Kr, void* Vr, void* Kt, void* Vt, float* vnorm2_max, float* knorm2_max, int groups,
                     void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * bevr_kv_project with SPLIT WEIGHTS (additive in ABI 6): the same pass, the weight operand as two E planes.  A rounded
+ * weight is an error common to all keys, which the attention's average over the keys does not shrink; the samples'
+ * rounding is per key and does, so the samples stay rounded once to E.
+ *   Wkv2   [2][2C][C] E, 16-byte aligned, plane 1 exactly 2C * C elements behind plane 0:
+ *            plane 0  hi  = E(w)
+ *            plane 1  lo' = E((w - hi) * 2^lo_exp)
+ *   lo_exp 0 .. 24 (BEVR_E_SHAPE otherwise).  0: lo' is the plain residual (bf16: its exponent range is float's).  fp16:
+ *          the residual of a small weight is subnormal or zero as a plain fp16 value; ops.kv_split_weights passes 11.
+ * Summation order: per k-step (16 input channels) the lo' products are issued before the hi products into the same f32
+ * accumulators; with lo_exp != 0 every lo' k-step runs first, the accumulators are multiplied once by 2^-lo_exp
+ * (exact) and the hi k-steps follow:   row = (sum lo' x) 2^-lo_exp + sum hi x + bias,  x = E(sample).
+ * Everything else is bevr_kv_project's contract: the other arguments, the checks and their order (NULL pointers, shapes
+ * with lo_exp, the f32-layout modes: BEVR_E_PRECISION, alignment), the outputs, and both norms, which are still of the
+ * UNROUNDED rows.  The adjoint is unchanged: it already uses the float weights.
+ * ---------------------------------------------------------------------------------------------- */
+int bevr_kv_project_w2(const void* feat, int feat_bf16, const float* pos, long long pos_pstride, const void* Wkv2,
+                       int lo_exp, const float* bkv, int nb, int Hi, int Wi, int C, int N, int Np, int heads, int c,
+                       int precision, void* Kr, void* Vr, void* Kt, void* Vt, float* vnorm2_max, float* knorm2_max,
+                       int groups, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Key positions from the offset heads' outputs, in the attention's key order, and the adjoint (one launch each).

@@ -1,0 +1,333 @@
+"""The fused K | V source with split (hi + lo) weights: bevr_kv_project_w2 (csrc/kvproj.hip, W2) and BEVR_KV_WSPLIT.
+
+1. layout: with an all-zero lo plane the entry point returns what bevr_kv_project returns, bit for bit;
+2. exactness: against float64 products of the E-rounded samples with hi + lo 2^-lo_exp;
+3. the point: the error COMMON to all keys (the mean over the keys of K | V minus a float64 reference) drops to what the
+   contract's torch emulation has, while bevr_kv_project's stays 10 x above it;
+4. attention_core(kv_source=...) with the switch on against the unfused chain;
+5. the whole model on the fixture whose proj_k / proj_v weights are not on the bf16 grid
+   (tests/golden/full_bevrender_cond_w.npz), with the limits of test_full_bevrender_conditioned."""
+import ctypes as C
+import importlib.util
+import logging
+import os
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from bevrender_amd import _lib, ops
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+HERE = os.path.dirname(os.path.abspath(__file__))
+BF16, F16 = _lib.PREC_BF16, _lib.PREC_F16
+SHAPES = [(2, 64, 2, 12, 20, 300), (1, 64, 4, 9, 7, 129), (1, 48, 2, 8, 8, 70)]     # (Bp, C, heads, Hi, Wi, N)
+
+
+def rel_err(got, want):
+    return (got - want).abs().max().item() / (want.abs().max().item() + 1e-12)
+
+
+def _ptr(t):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _project(feat, pos, n0, W, lo_exp, bias, heads, prec, groups=1, kt=True, norms=True):
+    """One launch on the key segment [n0, N): W (2C, C) E -> bevr_kv_project, W (2, 2C, C) E -> bevr_kv_project_w2.
+    Returns Kr, Vr, Kt (or None), Vt, vn2, kn2; the outputs start as 7.0 everywhere (every element must be written)."""
+    Bp, Hi, Wi, Cc = feat.shape
+    N = pos.shape[1]
+    Ns = N - n0
+    Np = 64 * ((Ns + 63) // 64)
+    ed = ops._edtype(prec)
+    mk = lambda *s: torch.full(s, 7.0, device=DEV, dtype=ed)      # noqa: E731
+    Kr, Vr, Vt = mk(Bp, heads, Np, 32), mk(Bp, heads, Np, 32), mk(Bp, heads, 32, Np)
+    Kt = mk(Bp, heads, 32, Np) if kt else None
+    vn2 = torch.zeros(1, device=DEV) if norms else None
+    kn2 = torch.zeros(Bp, heads, device=DEV) if norms else None
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    head = (_ptr(feat), int(feat.dtype == torch.bfloat16), C.c_void_p(pos.data_ptr() + n0 * 8), N, _ptr(W))
+    tail = (_ptr(bias), Bp, Hi, Wi, Cc, Ns, Np, heads, Cc // heads, prec, _ptr(Kr), _ptr(Vr), _ptr(Kt), _ptr(Vt), _ptr(vn2),
+            _ptr(kn2), groups, st)
+    assert W.is_contiguous() and W.dtype == ed
+    if W.dim() == 3:
+        rc = _lib.lib().bevr_kv_project_w2(*head, lo_exp, *tail)
+    else:
+        rc = _lib.lib().bevr_kv_project(*head, *tail)
+    assert rc == 0
+    return Kr, Vr, Kt, Vt, vn2, kn2
+
+
+def _inputs(shape, feat_bf16, groups, seed=0):
+    Bp, Cc, h, Hi, Wi, N = shape
+    gen = torch.Generator().manual_seed(N + Cc + seed)
+    feat = torch.randn(Bp, Hi, Wi, Cc, generator=gen)
+    feat = (feat.to(torch.bfloat16) if feat_bf16 else feat).to(DEV)
+    pos = (torch.rand(Bp * groups, N, 2, generator=gen) * 2.4 - 1.2).to(DEV)
+    W = (torch.randn(2 * Cc, Cc, generator=gen) / Cc ** 0.5).to(DEV)
+    bias = torch.randn(2 * Cc, generator=gen).to(DEV)
+    return feat, pos, W, bias
+
+
+@pytest.mark.parametrize("groups", [1, 2])
+@pytest.mark.parametrize("prec", [BF16, F16])
+@pytest.mark.parametrize("feat_bf16", [False, True])
+@pytest.mark.parametrize("shape", SHAPES)
+def test_zero_lo_plane_is_bevr_kv_project(shape, feat_bf16, prec, groups):
+    """hi = the rounded weights, lo = 0: the second MFMA adds zeros and, with lo_exp != 0, the scaling multiplies zeros --
+    every output and both norms equal bevr_kv_project's, bit for bit, on a key segment, with and without Kt."""
+    feat, pos, W, bias = _inputs(shape, feat_bf16, groups)
+    ed = ops._edtype(prec)
+    We = W.to(ed).contiguous()
+    W2 = torch.stack((We, torch.zeros_like(We))).contiguous()
+    want = _project(feat, pos, 5, We, None, bias, shape[2], prec, groups)
+    for lo_exp in (0, 11):                                  # the one-sweep and the two-sweep path of the kernel
+        got = _project(feat, pos, 5, W2, lo_exp, bias, shape[2], prec, groups)
+        for name, g, w in zip(("Kr", "Vr", "Kt", "Vt", "vnorm2_max", "knorm2_max"), got, want):
+            assert torch.equal(g, w), (name, lo_exp)
+    assert not (want[0] == 7.0).any() and not (want[3] == 7.0).any()
+    # forward-only call: no transposed K, no norms
+    w_f = _project(feat, pos, 5, We, None, bias, shape[2], prec, groups, kt=False, norms=False)
+    g_f = _project(feat, pos, 5, W2, ops.KV_WSPLIT_LO_EXP[prec], bias, shape[2], prec, groups, kt=False, norms=False)
+    for i in (0, 1, 3):
+        assert torch.equal(g_f[i], w_f[i]) and torch.equal(g_f[i], want[i])
+
+
+@pytest.mark.parametrize("prec", [BF16, F16])
+@pytest.mark.parametrize("feat_bf16", [False, True])
+@pytest.mark.parametrize("shape", SHAPES)
+def test_kv_project_w2_equals_sample_gemm_pack_with_hi_plus_lo(shape, feat_bf16, prec):
+    """As test_kv_project_equals_sample_gemm_pack (tests/test_gpu_ops.py): bevr_sample_fwd -> the GEMM in float64 on the
+    E-rounded samples and hi + lo 2^-lo_exp (weights that are NOT representable in E) -> rounding to E -> bevr_pack_kv's
+    layouts.  The kernel accumulates the same products in f32: 2 ulp of E on the largest entry; padded keys and padded
+    head channels exactly zero."""
+    Bp, Cc, h, Hi, Wi, N = shape
+    c = Cc // h
+    feat, pos, W, bias = _inputs(shape, feat_bf16, 1, seed=1)
+    ed = ops._edtype(prec)
+    assert (W.to(ed).float() != W).float().mean().item() > 0.9
+    W2, lo_exp = ops.kv_split_weights(W, prec)
+    assert lo_exp == {BF16: 0, F16: 11}[prec]
+    n0 = 5
+    Ns = N - n0
+    Kr, Vr, Kt, Vt, vn2, kn2 = _project(feat, pos, n0, W2, lo_exp, bias, h, prec)
+    xs = ops._Sample.sample(feat, pos)[:, n0:]                                           # float samples, the unfused kernel
+    Wd = W2[0].double() + W2[1].double() * 2.0 ** -lo_exp
+    kv = (xs.to(ed).double() @ Wd.t() + bias.double()).float()
+    Kw = ops.pack_keys(kv[..., :Cc].contiguous(), h).to(ed)
+    Vw = ops.pack_keys(kv[..., Cc:].contiguous(), h).to(ed)
+    ulp = 2.0 ** -8 if prec == BF16 else 2.0 ** -11
+    for name, got, want in (("Kr", Kr, Kw), ("Vr", Vr, Vw), ("Kt", Kt, ops._perm_t(Kw)), ("Vt", Vt, ops._perm_t(Vw))):
+        g, w = got.float(), want.float()
+        err = (g - w).abs().max().item()
+        print(f"[w2 exact {shape} bf16 map {feat_bf16} prec {prec}] {name}: max err {err:.3e}, "
+              f"2 ulp {2.0 * ulp * max(w.abs().max().item(), 1.0):.3e}")
+        assert err <= 2.0 * ulp * max(w.abs().max().item(), 1.0)
+        assert torch.equal(g == 0, w == 0) or ((g - w).abs()[(g == 0) != (w == 0)] < 1e-3).all()
+    assert (Kr[:, :, Ns:] == 0).all() and (Vr[:, :, Ns:] == 0).all()
+    assert (Kt[..., 32 * ((Ns + 31) // 32):] == 0).all() and (Vt[..., 32 * ((Ns + 31) // 32):] == 0).all()
+    if c < 32:
+        assert (Kr[..., c:] == 0).all() and (Vr[..., c:] == 0).all() and (Kt[:, :, c:] == 0).all() and (Vt[:, :, c:] == 0).all()
+    # the norms are of the unrounded rows
+    want_n2 = Vw.float().pow(2).sum(-1).max().item()
+    assert abs(vn2.item() - want_n2) <= 0.02 * want_n2
+    want_k2 = Kw.float().pow(2).sum(-1).amax(-1)
+    assert ((kn2 - want_k2).abs() <= 0.02 * want_k2).all()
+
+
+def _unpack(Xr, N, c):
+    """(Bp, h, Np, 32) packed rows -> (Bp, N, h c) float64 on the CPU"""
+    Bp, h = Xr.shape[:2]
+    return Xr[:, :, :N, :c].permute(0, 2, 1, 3).reshape(Bp, N, h * c).double().cpu()
+
+
+def _sys(got, ref):
+    """per problem: || mean over keys of (got - ref) ||_2 / || mean over keys of ref ||_2"""
+    return ((got - ref).mean(1).norm(dim=-1) / ref.mean(1).norm(dim=-1)).tolist()
+
+
+@pytest.mark.parametrize("wscale", [1.0, 2.0 ** -7])
+@pytest.mark.parametrize("prec", [BF16, F16])
+def test_the_error_common_to_all_keys_is_gone(prec, wscale):
+    """N = 4133 keys per problem (the per-key roundings average down to 1 / 40 of the rounded weights' effect), C = 64,
+    features uniform in [0, 1) -- a zero-mean map would hide a common weight error --, a float and a bf16 map.  The
+    reference samples and projects in float64 on the CPU; the emulation is the kernel's contract in torch on the same
+    inputs (float32 samples rounded to E, float64 products with hi + lo 2^-lo_exp, one rounding to E).
+    sys(w2) <= 3 x sys(emulation): the emulation itself moved by 1.4 x over seeds and map types, the GPU sums in
+    another order; rounded weights sit 35-45 x above it, fp16 with a plain or flushed residual at wscale 2^-7 4-40 x.
+    sys(bevr_kv_project) >= 10 x sys(w2): the error is there without the feature, on the same inputs."""
+    Bp, Cc, h, Hi, Wi, N = 2, 64, 2, 12, 20, 4133
+    c = Cc // h
+    ed = ops._edtype(prec)
+    for feat_bf16 in (False, True):
+        gen = torch.Generator().manual_seed(11 + int(feat_bf16))
+        feat = torch.rand(Bp, Hi, Wi, Cc, generator=gen)
+        feat = feat.to(torch.bfloat16) if feat_bf16 else feat
+        pos = torch.rand(Bp, N, 2, generator=gen) * 2.0 - 1.0
+        W = torch.randn(2 * Cc, Cc, generator=gen) / Cc ** 0.5 * wscale
+        bias = 0.1 * torch.randn(2 * Cc, generator=gen) * wscale
+        W2, lo_exp = ops.kv_split_weights(W, prec)
+
+        def sample(dt):     # grid_sample takes (x, y); pos is (y, x)
+            return F.grid_sample(feat.to(dt).permute(0, 3, 1, 2), pos.flip(-1).to(dt)[:, :, None], mode="bilinear",
+                                 padding_mode="zeros", align_corners=True)[..., 0].transpose(1, 2)     # (Bp, N, C)
+        ref = sample(torch.float64) @ W.double().t() + bias.double()
+        Wd = W2[0].double() + W2[1].double() * 2.0 ** -lo_exp
+        emu = (sample(torch.float32).to(ed).double() @ Wd.t() + bias.double()).float().to(ed).double()
+        args = (feat.to(DEV), pos.to(DEV), 0)
+        out2 = _project(*args, W2.to(DEV), lo_exp, bias.to(DEV), h, prec)
+        out1 = _project(*args, W.to(ed).to(DEV), None, bias.to(DEV), h, prec)
+        got2 = torch.cat((_unpack(out2[0], N, c), _unpack(out2[1], N, c)), -1)
+        got1 = torch.cat((_unpack(out1[0], N, c), _unpack(out1[1], N, c)), -1)
+        s_emu, s_w2, s_plain = _sys(emu, ref), _sys(got2, ref), _sys(got1, ref)
+        for b in range(Bp):
+            print(f"[kv wsplit sys] prec {prec} wscale {wscale:.4g} bf16 map {feat_bf16} problem {b}: emulation {s_emu[b]:.3e} "
+                  f"w2 {s_w2[b]:.3e} bevr_kv_project {s_plain[b]:.3e}")
+        for b in range(Bp):
+            assert s_w2[b] <= 3.0 * s_emu[b], (feat_bf16, b, s_w2[b], s_emu[b])
+            assert s_plain[b] >= 10.0 * s_w2[b], (feat_bf16, b, s_plain[b], s_w2[b])
+
+
+@pytest.mark.parametrize("prec", [BF16, F16])
+def test_attention_core_with_split_weights_matches_the_unfused_chain(prec, monkeypatch):
+    """test_attention_core_with_fused_kv_source_matches_the_unfused_chain (tests/test_gpu_ops.py) with BEVR_KV_WSPLIT=1:
+    the same shapes and limits on the output and every gradient; the switch-off distance is printed beside it."""
+    B, V, Cc, h, S, D, Hi, Wi = 1, 2, 64, 2, 10, 3, 12, 20
+    N = (S // 2) * S * D
+    gen = torch.Generator().manual_seed(77)
+    query = torch.randn(B, Cc, S, S, generator=gen)
+    feat = torch.randn(B * V, Hi, Wi, Cc, generator=gen)
+    pos = torch.rand(B * V, N, 2, generator=gen) * 2.2 - 1.1
+    W = torch.randn(2 * Cc, Cc, generator=gen) / Cc ** 0.5
+    bias = torch.randn(2 * Cc, generator=gen) * 0.1
+    table = torch.randn(h, 2 * S - 1, 2 * S * D - 1, generator=gen) * 0.3
+    cot = torch.randn(B * V, S * S, Cc, generator=gen).to(DEV)
+    launched = set()
+    run_timed = ops.KERNEL_TIMER.run
+
+    def recorder(name, flops, fn, *args, **kw):
+        launched.update((name, getattr(fn, "__name__", repr(fn))))
+        return run_timed(name, flops, fn, *args, **kw)
+    monkeypatch.setattr(ops.KERNEL_TIMER, "run", recorder)
+    res = {}
+    for how in ("split", "rounded", "unfused"):
+        monkeypatch.setenv("BEVR_KV_WSPLIT", "1" if how == "split" else "0")
+        ins = [t.clone().to(DEV).requires_grad_(True) for t in (query, feat, pos, W, bias, table)]
+        q, f, p_, w, b_, t = ins
+        if how == "unfused":
+            xs = ops._Sample.apply(f, p_)
+            out = ops.attention_core(q, None, None, p_, t, heads=h, groups=1, views=V, precision=prec,
+                                     kv=F.linear(xs, w, b_), cell_split=N // 2)
+        else:
+            out = ops.attention_core(q, None, None, p_, t, heads=h, groups=1, views=V, precision=prec,
+                                     kv_source=(f, w, b_), cell_split=N // 2)
+        out.backward(cot)
+        res[how] = (out.detach(), [x.grad for x in ins])
+        assert "bevr_kv_project" in launched or how == "unfused"                             # the timer name
+        assert ("bevr_kv_project_w2" in launched) == (how == "split")                        # the library symbol
+        launched.clear()
+    (of, gf), (o0, _), (ou, gu) = res["split"], res["rounded"], res["unfused"]
+    lim = 2e-2 if prec == BF16 else 3e-3
+    e_on, e_off = rel_err(of.cpu(), ou.cpu()), rel_err(o0.cpu(), ou.cpu())
+    print(f"[kv wsplit core prec={prec}] output against the unfused chain: switch on {e_on:.3e}, switch off {e_off:.3e} (limit {lim:.1e})")
+    assert e_on < lim
+    for n, a, b in zip(("query", "feat", "pos", "W", "bias", "table"), gf, gu):
+        e = rel_err(a.cpu(), b.cpu())
+        print(f"[kv wsplit core prec={prec}] grad {n} rel diff {e:.2e}")
+        assert e < 2.5 * lim, f"grad {n}: {e:.3e}"
+
+
+# ---- the whole model on the fixture whose projection weights are not on the bf16 grid ----
+REGION_16 = {"bevr_attn_gather_fwd", "bevr_attn_slab_bwd_q", "bevr_attn_bwd_k"}
+TAP = {"bevr_attn_tap_fwd", "bevr_attn_tap_bwd_q", "bevr_attn_tap_bwd_k"}
+CELL = {"bevr_attn_cell_fwd", "bevr_attn_cell_bwd_q", "bevr_attn_cell_bwd_k"}
+_GEN = []
+
+
+def _gen():
+    if not _GEN:
+        spec = importlib.util.spec_from_file_location("mgfw", os.path.join(HERE, "golden", "make_golden_full_w.py"))
+        m = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(m)
+        _GEN.append((m, m.load_cond_w()))
+    return _GEN[0]
+
+
+def _whole_model(mode, monkeypatch, wsplit):
+    """test_full_bevrender_conditioned's procedure (tests/test_gpu_full_model.py) on the new fixture.  Returns
+    (launched, e_out, lim_out, rows) with rows = (ok, line, err, lim) per parameter in backward order."""
+    from bevrender_amd.model.bevrender import BEVRender
+    gw, z = _gen()
+    g = gw.mgf
+    monkeypatch.setenv("BEVR_KV_WSPLIT", "1" if wsplit else "0")
+    launched = set()
+
+    def recorder(name, flops, fn, *args, nbytes=0.0, tag=""):
+        launched.update((name, getattr(fn, "__name__", repr(fn))))
+        return fn(*args)
+    monkeypatch.setattr(ops.KERNEL_TIMER, "run", recorder)
+    cfg = g.cond_config()
+    cfg["PRECISION"], cfg["STAGE_DTYPE"] = mode, None
+    torch.manual_seed(int(z["seed"]))
+    model = BEVRender(cfg, logging.getLogger("t"), "train")
+    gw.condition_w_(model.state_dict())
+    assert len(model.state_dict()) == int(z["n_state"])
+    model = model.to("cuda")
+    img, pose, vtype = g.full_inputs()
+    out, _ = model(img.cuda(), pose.cuda(), vtype.cuda(), {}, False)
+    assert tuple(out.shape) == tuple(z["out_shape"])
+    (out.float() * g.cond_cotangent(out.shape).cuda()).sum().backward()
+    torch.cuda.synchronize()
+    got = out.detach().float().flatten().cpu()[torch.tensor(z["out_idx"])].numpy()
+    assert np.isfinite(got).all()
+    e_out = g.rel2(got, z["out_val"])
+    lim_out = max(2e-3, 3.0 * float(z["s_out_" + mode]))
+    params = dict(model.named_parameters())
+    missing = [n for n in z["names"] if n not in params or params[n].grad is None]
+    assert not missing, missing
+    nonfinite = [n for n, p in params.items() if p.grad is not None and not torch.isfinite(p.grad).all()]
+    assert not nonfinite, nonfinite
+    rows = []
+    for i, n in enumerate(z["names"]):
+        v = params[n].grad.detach().float().flatten().cpu()[torch.tensor(z["idx"][i])].numpy()
+        if z["null"][i]:
+            err, lim, what = float(np.linalg.norm(v.astype(np.float64))), 10.0 * float(z["null_bound"][i]), "null |g|"
+        else:
+            err, lim, what = g.rel2(v, z["val"][i]), max(2e-2, 3.0 * float(z["s_" + mode][i])), "rel"
+        line = f"  {i:3d} {n:90s} {what:8s} {err:.3e} limit {lim:.3e}{'' if err <= lim else '  FAIL'}"
+        rows.append((err <= lim, line, err, lim))
+    return launched, e_out, lim_out, rows
+
+
+@pytest.mark.parametrize("mode", ["bf16", "f16"])
+def test_full_bevrender_with_split_weights(mode, monkeypatch):
+    """The whole model with BEVR_KV_WSPLIT=1 against the reference's on full_bevrender_cond_w.npz (seeded proj_k / proj_v
+    weights, not representable in bf16): output within max(2e-3, 3 s_out), every non-null gradient within
+    max(2e-2, 3 s), s from the fixture (the reference's own sensitivity to what the split-weight kernel rounds).  The
+    projection must have run as bevr_kv_project_w2 under the plain form's timer name, beside the mode's usual routes.
+    The switch-off run is a control: printed, not asserted (rounded weights alone move the reference's output by
+    2.8e-3 on this model, beyond the 2e-3 limit)."""
+    _, z = _gen()
+    names = z["names"]
+    i_emb = names.index("bev_embedding.weight")
+    launched, e_out, lim_out, rows = _whole_model(mode, monkeypatch, True)
+    ctl_launched, c_out, _, c_rows = _whole_model(mode, monkeypatch, False)
+    live = [i for i in range(len(names)) if not z["null"][i]]
+    med = lambda rs: float(np.median([rs[i][2] for i in live]))      # noqa: E731
+    print(f"[wsplit {mode}] launched: {sorted(launched)}")
+    print(f"[wsplit {mode}] per-parameter gradient errors in backward order (switch on):")
+    print("\n".join(r[1] for r in rows))
+    print(f"[wsplit {mode}] summary, switch on : out {e_out:.3e} limit {lim_out:.3e}; grad(embedding) {rows[i_emb][2]:.3e} "
+          f"limit {rows[i_emb][3]:.3e}; median over parameters {med(rows):.3e}; beyond their limit {sum(not r[0] for r in rows)}")
+    print(f"[wsplit {mode}] control, switch off: out {c_out:.3e} limit {lim_out:.3e}; grad(embedding) {c_rows[i_emb][2]:.3e} "
+          f"limit {c_rows[i_emb][3]:.3e}; median over parameters {med(c_rows):.3e}; beyond their limit {sum(not r[0] for r in c_rows)}")
+    assert "bevr_kv_project_w2" in launched and "bevr_kv_project" in launched
+    assert "bevr_kv_project_w2" not in ctl_launched and "bevr_kv_project" in ctl_launched
+    assert REGION_16 | TAP <= launched, sorted((REGION_16 | TAP) - launched)
+    assert not (CELL & launched), sorted(CELL & launched)
+    assert launched - {"bevr_kv_project_w2"} == ctl_launched            # the mode's usual routes, nothing else moved
+    assert e_out <= lim_out, (mode, e_out, lim_out)
+    bad = [r[1] for r in rows if not r[0]]
+    assert not bad, f"{mode}: {len(bad)} gradients beyond their limit, in backward order:\n" + "\n".join(bad)
