@@ -54,6 +54,9 @@
 // caller's order: this unit's preparation (bevr_attn_slab_drop_prep) writes that index into SlabKey::pad, the producer
 // stages index x 0xC2B2AE3D per emission beside the constants, and the key-row loops take it by DPP as they take those.
 // The entry points are bevr_attn_slab_drop_ws_bytes / _slab_drop_prep / bevr_attn_slab_bwd_q_dropout.
+//
+// BEVR_SLAB_X3 = 1 and BEVR_DROP = 1 (attn_slab_bwd_q_x3_drop.hip): the same mask on the split-bf16 body, staged and taken
+// the same way; bevr_attn_slab_x3_drop_ws_bytes / _slab_x3_drop_prep / bevr_attn_slab_bwd_q_x3_dropout.
 #ifndef BEVR_SLAB_ROWS
 #define BEVR_SLAB_ROWS 0
 #endif
@@ -153,9 +156,16 @@ __host__ __device__ inline int slab_pitch(int S) { return slab_rows(S) <= SLAB_R
 __host__ __device__ inline int slab_pitch(int S) { return SLAB_RP; }
 #endif
 #if BEVR_DROP
-static_assert(!BEVR_SLAB_ROWS && !BEVR_SLAB_X3, "the keep mask: the 16-bit one-band kernel");
+static_assert(!BEVR_SLAB_ROWS, "the keep mask: the one-band kernels, 16-bit and split-bf16");
+#if BEVR_SLAB_X3
+// split-bf16: the hash words leave the slab its 15 owned columns (17 x 448 x 16 + 2 x 18 720 + 64 = 159 360 bytes; a 16th
+// would need 166 528) -- the slab width, the workspace and the work list are bevr_attn_slab_bwd_q_x3's
+static_assert((15 + 2) * SLAB_RP * SLAB_CELL + 2 * SlabLds::BUF + 64 <= 160 * 1024 &&
+              (16 + 2) * SLAB_RP * SLAB_CELL + 2 * (SlabLds::BUF - SEK * 4) + 64 > 160 * 1024, "15 columns with and without the mask");
+#else
 // the widest slab with the staged hash words beside OFF_CK: the workgroup is still the CU's 160 KB
 static_assert((SLAB_W_MAX + 2) * SLAB_RP * SLAB_CELL + 2 * SlabLds::BUF + 64 <= 160 * 1024, "160 KB of LDS");
+#endif
 #endif
 // first table column any slab has to cover and the number of slabs: X = floor(j rx + b), b clamped as the key prep does
 __host__ __device__ inline int slab_xmin(const bevr_attn_desc& d) { return -(d.Wt / 2 + 2) - 1; }
@@ -268,7 +278,8 @@ __global__ __launch_bounds__(STHREADS, 1) void attn_slab_bwd_q_kernel(
     const SlabKey* __restrict__ skeys, const int* __restrict__ kbeg, const int* __restrict__ kend,
     const int4* __restrict__ items, int* __restrict__ cnt, const char* __restrict__ table_pair,
     const char* __restrict__ dO, const float* __restrict__ LSE, const float* __restrict__ delta,
-    const float* __restrict__ grad_scale, float* __restrict__ dQ, float* __restrict__ dtable, int n_slab, int sw, int R);
+    const float* __restrict__ grad_scale, float* __restrict__ dQ, float* __restrict__ dtable, int n_slab, int sw, int R
+    BEVR_DROP_PARAMS);
 #else
 // BEVR_SLAB_ROWS: RP the row pitch, row0 (a multiple of SQROWS) the first BEV row of the launch's band, n_rb_band <= SNRB its
 // row blocks: worker wave w owns row block row0 / SQROWS + w of the column
@@ -821,8 +832,14 @@ bool slab_shape_ok(const bevr_attn_desc& d) {
   return slab_prec_x3(d.precision) && slab_n_rb(d.S) <= SNRB && slab_rows(d.S) <= SLAB_RP && SLAB_CH <= 64 &&
          slab_lds_bytes(d.S, slab_width(d.S)) <= 160 * 1024;
 }
+#if BEVR_DROP
+// a preparation of this unit's own, as the 16-bit masked unit's: it writes SlabKey::pad
+#define SLAB_WS_BYTES bevr_attn_slab_x3_drop_ws_bytes
+#define SLAB_PREP bevr_attn_slab_x3_drop_prep
+#else
 #define SLAB_WS_BYTES bevr_attn_slab_x3_ws_bytes
 #define SLAB_PREP bevr_attn_slab_x3_prep
+#endif
 #define SLAB_PREC_OK slab_prec_x3
 #else
 #define SLAB_PREC_OK is16
@@ -912,6 +929,15 @@ extern "C" int bevr_attn_slab_bwd_q_rows(const bevr_attn_desc* d, const void* Q,
                                          int n_rows, void* stream) {
   return run<BEVR_PREC_BF16, BEVR_PREC_F16>(d, Q, Ks, Vs, slab_ws_, table_pair, dO, LSE, delta, grad_scale, dQ, dtable, row0,
                                             n_rows, stream);
+}
+#elif BEVR_SLAB_X3 && BEVR_DROP
+extern "C" int bevr_attn_slab_bwd_q_x3_dropout(const bevr_attn_desc* d, const void* Q, const void* Ks, const void* Vs,
+                                               const void* slab_ws_, const float* table_pair, const void* dO,
+                                               const float* LSE, const float* delta, const float* grad_scale, float* dQ,
+                                               float* dtable, unsigned drop_thr, unsigned drop_seed, void* stream) {
+  if (drop_thr >= 65536u) return BEVR_E_SHAPE;
+  return run<BEVR_PREC_BF16X3>(d, Q, Ks, Vs, slab_ws_, table_pair, dO, LSE, delta, grad_scale, dQ, dtable, 0, 0, stream,
+                               drop_thr, drop_seed);
 }
 #elif BEVR_SLAB_X3
 extern "C" int bevr_attn_slab_bwd_q_x3(const bevr_attn_desc* d, const void* Q, const void* Ks, const void* Vs,

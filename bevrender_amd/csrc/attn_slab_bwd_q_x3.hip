@@ -30,6 +30,11 @@
 //     (bit 0 of (r >> 1) is bit 1 of f), so the rows read positions C ^ F, C ^ F, C ^ F ^ 2, C ^ F ^ 2 at bank offsets 0, 32, 0,
 //     32: C ^ 2 is the other plane's chunk set, disjoint from C -- 32 lanes x 2 dwords cover the 64 banks once;
 //   - the producer's stores: 8 contiguous lanes write the 8 chunks of ONE row, a permutation of its 128 bytes: 32 banks once.
+// BEVR_DROP = 1 (attn_slab_bwd_q_x3_drop.hip, a translation unit of its own again): the keep mask of
+// bevr_attn_bwd_q_dropout, as the 16-bit slab kernel has it (attn_slab_bwd_q.hip) -- the original key index from
+// SlabKey::pad staged as a hash word per emission (2 x 256 bytes more LDS: 159 360, still 15 columns), the row part of the
+// hash per column, one FMA per pair on the dP accumulator ahead of a half's key-row loop: bevr_attn_slab_bwd_q_x3_dropout.
+//
 // No padding of a uniform row stride can do the same: a stride of 4 m dwords needs m odd for the fragment reads and the
 // eight 8-dword blocks of a transposed read tile the banks only if every row starts on a multiple of 8 dwords.
 #define BEVR_SLAB_X3 1
@@ -49,7 +54,8 @@ __global__ __launch_bounds__(STHREADS, 1) void attn_slab_bwd_q_kernel(
     const SlabKey* __restrict__ skeys, const int* __restrict__ kbeg, const int* __restrict__ kend,
     const int4* __restrict__ items, int* __restrict__ cnt, const char* __restrict__ table_pair,
     const char* __restrict__ dO, const float* __restrict__ LSE, const float* __restrict__ delta,
-    const float* __restrict__ grad_scale, float* __restrict__ dQ, float* __restrict__ dtable, int n_slab, int sw, int R) {
+    const float* __restrict__ grad_scale, float* __restrict__ dQ, float* __restrict__ dtable, int n_slab, int sw, int R
+    BEVR_DROP_PARAMS) {
   static_assert(PREC == BEVR_PREC_BF16X3, "the split-bf16 body");
   typedef SlabLds L;
   extern __shared__ __attribute__((aligned(256))) char lds[];
@@ -77,6 +83,11 @@ __global__ __launch_bounds__(STHREADS, 1) void attn_slab_bwd_q_kernel(
 
   // dS = ln2 P (dP - delta); the fixed-point scale of the cells (a power of two: exact) rides in dO and delta
   const float gscale = grad_scale[0], ginv = grad_scale[1] * BEVR_LN2;
+#if BEVR_DROP
+  // D: a kept pair's dP is D dP (uniform: kept in a scalar register)
+  const float ksc = __builtin_bit_cast(
+      float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, 65536.0f / (65536.0f - (float)drop_thr))));
+#endif
   PROF_ACC(16);
 
   for (;;) {
@@ -221,6 +232,10 @@ __global__ __launch_bounds__(STHREADS, 1) void attn_slab_bwd_q_kernel(
           }
           ck.pad0 = ck.pad1 = 0;
           *reinterpret_cast<SlabCK*>(bb + L::OFF_CK + lane * (int)sizeof(SlabCK)) = ck;
+#if BEVR_DROP
+          // the keys arrive sorted by b: the mask is of the ORIGINAL index (SlabKey::pad, this unit's prep)
+          *reinterpret_cast<unsigned*>(bb + L::OFF_KN + lane * 4) = (unsigned)sk_e.pad * 0xC2B2AE3Du;
+#endif
           // per half: any live key; any live key whose rows leave the window for some row block (the clamped body)
           const bool far = live && (sk_e.A + SLAB_ROW0 < 0 || sk_e.A > d.S - 1 + SLAB_PADR);
           const unsigned long long lm = __ballot(live), fm = __ballot(far);
@@ -269,6 +284,9 @@ __global__ __launch_bounds__(STHREADS, 1) void attn_slab_bwd_q_kernel(
       for (int k = 0; k < 16; ++k) qf.v[k] = dof.v[k] = 0.f;      // (initialised: as the producer's load registers)
       float nl = 0.f, nd = 0.f, lse_r = 0.f, dlt_r = 0.f;
       int jcur = -1;
+#if BEVR_DROP
+      uint32_t hrow = 0u;      // the row part of the keep hash: per column, out of the key-row loops
+#endif
       f32x16 dq;
 #pragma unroll
       for (int r = 0; r < 16; ++r) dq[r] = 0.f;
@@ -280,6 +298,9 @@ __global__ __launch_bounds__(STHREADS, 1) void attn_slab_bwd_q_kernel(
         dof.load(dOh + mq * ROWB, hi);
         lse_r = LSE[(size_t)ph * Mp + mq];
         dlt_r = delta[(size_t)ph * Mp + mq];
+#if BEVR_DROP
+        hrow = bevr_drop_row(drop_seed, (uint32_t)ph, (uint32_t)(j * d.Sp + qrow));
+#endif
         jcur = j;
       };
       // ... and made ready: lanes without a query compute on a copy of a real one with dO = delta = 0 (their dS is exactly
@@ -398,6 +419,20 @@ __global__ __launch_bounds__(STHREADS, 1) void attn_slab_bwd_q_kernel(
             products(1);
             __builtin_amdgcn_sched_barrier(0);
           }
+#if BEVR_DROP
+          // dS = P (keep ? D dP - delta : -delta); dp holds dP - delta, nd = -delta, both in cell units (attn_bwd_q.hip).
+          // The hash words of the keys bcast_key(lane), taken by DPP like the constants.  Ahead of the half's key-row
+          // loop, four hashes in flight between scheduling fences: no scratch in any of the three placements tried, and
+          // this one the fastest per launch (66.8 ms against 67.8 with all sixteen at once and 67.6 with the hashes inside
+          // the two-chain loop: DESIGN.md section 5)
+          const unsigned kn = *reinterpret_cast<const unsigned*>(bb + L::OFF_KN + (h * 32 + bcast_key(lane)) * 4);
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const bool keep = (bevr_drop_mix(hrow ^ row_bcast(kn, r)) >> 16) >= drop_thr;
+            dp[h][r] = keep ? fmaf(ksc, dp[h][r] - nd, nd) : nd;
+            if ((r & 3) == 3) __builtin_amdgcn_sched_barrier(0);
+          }
+#endif
           // chain c walks the key rows c * 8 + 0 .. 7 of the accumulator tile
           int o0[2];
           f32x2 ta[2], tb[2];

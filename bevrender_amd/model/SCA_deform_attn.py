@@ -152,8 +152,9 @@ class SCADeformableAttention(nn.Module):
         dropout kernels, one mask); any other split is dropped and every key runs on the region kernels.  The split-bf16
         mode keeps the split with a mask when BEVR_TAP_X3=1 and BEVR_TAP_X3_DROP=1 (ops.tap_supported(..., dropout=True)):
         the pinned keys are then neither sampled nor projected in training with dropout either.  With BEVR_SCATTER_DROP=1
-        the scattered keys of the 16-bit modes take the gather forward and the slab bwd_q with the same mask
-        (ops.attention_route; nothing here depends on it)."""
+        the scattered keys of the 16-bit modes take the gather forward and the slab bwd_q with the same mask, and those of
+        the split-bf16 mode, with BEVR_SLAB_X3=1 as well, the split slab bwd_q with it (bevr_attn_slab_bwd_q_x3_dropout;
+        their forward stays the region dropout kernel) (ops.attention_route; nothing here depends on it)."""
         B, V, C, Hi, Wi = x.shape
         S = query.shape[-1]
         if V != self.n_views:

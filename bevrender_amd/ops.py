@@ -543,6 +543,7 @@ class K:
     SLAB_BWD_Q_ROWS = "bevr_attn_slab_bwd_q_rows"
     SLAB_BWD_Q_X3 = "bevr_attn_slab_bwd_q_x3"
     SLAB_BWD_Q_DROP = "bevr_attn_slab_bwd_q_dropout"
+    SLAB_BWD_Q_X3_DROP = "bevr_attn_slab_bwd_q_x3_dropout"
     BWD_K, BWD_K_DROP = "bevr_attn_bwd_k", "bevr_attn_bwd_k_dropout"
     CELL_FWD, CELL_BWD_Q, CELL_BWD_K = "bevr_attn_cell_fwd", "bevr_attn_cell_bwd_q", "bevr_attn_cell_bwd_k"
     TAP_FWD, TAP_FWD_DROP = "bevr_attn_tap_fwd", "bevr_attn_tap_fwd_dropout"
@@ -600,7 +601,10 @@ def attention_route(precision: int, groups: int, S: int, Wt: int, N: int, cell_s
     BEVR_SCATTER_DROP (default SCATTER_DROP_DEFAULT: off; tests/test_scatter_dropout_routes_cpu.py): with a keep mask, in
     the 16-bit modes, the region segment's forward is the gather kernel with the mask (K.GATHER_DROP) where
     gather_supported holds and its bwd_q the slab kernel with the mask (K.SLAB_BWD_Q_DROP) where slab_supported holds;
-    the key-side backward stays K.BWD_K_DROP.  Unset or 0: the region dropout kernels, as before these two had a mask."""
+    the key-side backward stays K.BWD_K_DROP.  In the split-bf16 mode it is the bwd_q alone: the split slab kernel with
+    the mask (K.SLAB_BWD_Q_X3_DROP) where slab_supported holds, which there needs BEVR_SLAB_X3 as well
+    (tests/test_slab_x3_dropout_routes_cpu.py); the forward stays K.FWD_DROP whatever BEVR_GATHER_X3 is.  Unset or 0: the
+    region dropout kernels, as before these had a mask."""
     # tap_pix with a keep mask (the split-bf16 mode behind BEVR_TAP_X3_DROP) follows kv_source's rules below, but where
     # those would drop the split it has no projected rows of the pinned keys to fall back to: ValueError
     # (the split mode alone: tap_pix is its route -- the 16-bit modes have the fused K | V source and keep refusing)
@@ -653,6 +657,10 @@ def attention_route(precision: int, groups: int, S: int, Wt: int, N: int, cell_s
                     fwd = K.GATHER_DROP             # one entry point, whole columns as the range (0, S)
                 if slab_supported(precision, S, Wt):
                     bwd_q = K.SLAB_BWD_Q_DROP
+            # ... and, in the split-bf16 mode, the masked split slab kernel: BEVR_SLAB_X3 and BEVR_SCATTER_DROP together
+            # (no masked split gather forward: the unmasked one is no faster than the region forward)
+            elif scatter_drop() and precision == _lib.PREC_BF16X3 and slab_supported(precision, S, Wt):
+                bwd_q = K.SLAB_BWD_Q_X3_DROP
             segs.append(KeySegment("region", 0, n_region, fwd, bwd_q, K.BWD_K_DROP))
         else:
             if gather_supported(precision, S):
@@ -703,7 +711,9 @@ def gather_supported(precision, S) -> bool:
 
 def scatter_drop() -> bool:
     """With a keep mask, do the scattered keys of the 16-bit modes run on the gather forward and the slab bwd_q with the
-    mask (csrc/attn_gather_fwd_drop.hip, csrc/attn_slab_bwd_q_drop.hip) where gather_supported / slab_supported hold?
+    mask (csrc/attn_gather_fwd_drop.hip, csrc/attn_slab_bwd_q_drop.hip) where gather_supported / slab_supported hold --
+    and those of the split-bf16 mode on its slab bwd_q with the mask (csrc/attn_slab_bwd_q_x3_drop.hip) where
+    slab_supported holds, i.e. with BEVR_SLAB_X3 on as well (their forward stays the region dropout kernel)?
     BEVR_SCATTER_DROP, default SCATTER_DROP_DEFAULT: off -- the region dropout kernels, the routing before these kernels
     had a mask -- until the pinned route table changes with it.  Same mask, same results up to the kernels' rounding."""
     return os.environ.get("BEVR_SCATTER_DROP", SCATTER_DROP_DEFAULT) != "0"
@@ -740,7 +750,9 @@ def slab_supported(precision, S, Wt=None) -> bool:
     (A/B timing, tests).  Same results up to the order of the float atomics and one rounding of the tap weights.
     The split-bf16 mode (BEVR_PREC_BF16X3: csrc/attn_slab_bwd_q_x3.hip, bevr_attn_slab_bwd_q_x3) under the same rules when
     BEVR_SLAB_X3 is set and not 0; the switch's default is SLAB_X3_DEFAULT: off, that mode's earlier routing (the
-    query-tile kernel), until the pinned route table changes with it."""
+    query-tile kernel), until the pinned route table changes with it.  With a keep mask the same answer decides, together
+    with scatter_drop, between bevr_attn_slab_bwd_q_dropout / bevr_attn_slab_bwd_q_x3_dropout and the query-tile kernel
+    with the mask (attention_route)."""
     mode = os.environ.get("BEVR_SLAB", "1")
     if mode == "0" or S > 211:
         return False
@@ -889,7 +901,10 @@ def _bwd_q_slab_drop(name, o):
     """the slab bwd_q with the keep mask: the workspace of its own prep carries the keys' indices in the caller's order
     (what the mask hashes); the cotangent is the unscaled one, D enters in the kernel"""
     g = o.g
-    Ks, Vs, sws = _slab_operands(o, "bevr_attn_slab_drop_ws_bytes", "bevr_attn_slab_drop_prep")
+    if name == K.SLAB_BWD_Q_X3_DROP:     # split rows in float containers, the split kernel's slab width
+        Ks, Vs, sws = _slab_operands(o, "bevr_attn_slab_x3_drop_ws_bytes", "bevr_attn_slab_x3_drop_prep")
+    else:
+        Ks, Vs, sws = _slab_operands(o, "bevr_attn_slab_drop_ws_bytes", "bevr_attn_slab_drop_prep")
     _launch(name, C.byref(o.desc), _ptr(o.Qe), _ptr(Ks), _ptr(Vs), _ptr(sws), _ptr(o.pair), _ptr(o.dOe), _ptr(o.LSE),
             _ptr(o.delta), _ptr(o.gscale), _ptr(o.dQ), _ptr(o.dT), *o.drop, _stream(), flops=_attn_flops(g, 3),
             tag=_call_tag(g))
@@ -964,6 +979,7 @@ _RUN = {K.FWD: _fwd_tile, K.FWD_DROP: _fwd_tile, K.GATHER: _fwd_gather, K.GATHER
         K.GATHER_X3: _fwd_gather, K.GATHER_DROP: _fwd_gather_drop, K.CELL_FWD: _fwd_cell,
         K.BWD_Q: _bwd_q_tile, K.BWD_Q_DROP: _bwd_q_tile, K.CELL_BWD_Q: _bwd_q_tile, K.SLAB_BWD_Q: _bwd_q_slab,
         K.SLAB_BWD_Q_ROWS: _bwd_q_slab_rows, K.SLAB_BWD_Q_X3: _bwd_q_slab, K.SLAB_BWD_Q_DROP: _bwd_q_slab_drop,
+        K.SLAB_BWD_Q_X3_DROP: _bwd_q_slab_drop,
         K.BWD_K: _bwd_k_tile, K.BWD_K_DROP: _bwd_k_tile, K.CELL_BWD_K: _bwd_k_cell,
         K.TAP_FWD: _tap_fwd, K.TAP_FWD_DROP: _tap_fwd, K.TAP_BWD_Q: _tap_bwd_q, K.TAP_BWD_Q_DROP: _tap_bwd_q,
         K.TAP_BWD_K: _tap_bwd_k, K.TAP_BWD_K_DROP: _tap_bwd_k,

@@ -74,7 +74,9 @@ extern "C" {
  *    bevr_attn_slab_drop_ws_bytes / _slab_drop_prep / bevr_attn_slab_bwd_q_dropout (the slab query-side backward with
  *    the keep mask, S <= 211), both in the 16-bit modes; every other gather and slab entry point keeps its contract;
  *    bevr_kv_project_w2 (bevr_kv_project with the weights as two E planes, hi + lo; bevr_kv_project keeps its
- *    contract). */
+ *    contract);
+ *    bevr_attn_slab_x3_drop_ws_bytes / _slab_x3_drop_prep / bevr_attn_slab_bwd_q_x3_dropout (the slab query-side backward
+ *    with the keep mask in BEVR_PREC_BF16X3, S <= 211; every other slab entry point keeps its contract). */
 #define BEVR_ABI_VERSION 6
 
 enum {
@@ -580,6 +582,26 @@ int bevr_attn_slab_bwd_q_dropout(const bevr_attn_desc* d, const void* Q, const v
                                  const void* slab_ws, const float* table_pair, const void* dO, const float* LSE,
                                  const float* delta, const float* grad_scale, float* dQ, float* dtable,
                                  unsigned drop_thr, unsigned drop_seed, void* stream);
+/* bevr_attn_slab_bwd_q_x3 with the same keep mask (csrc/attn_slab_bwd_q_x3_drop.hip), BEVR_PREC_BF16X3, S <= 211.  The
+ * mask is again of the key's index in the CALLER's order, carried by a workspace of this kernel's own.
+ *   bevr_attn_slab_x3_drop_ws_bytes / _slab_x3_drop_prep: as bevr_attn_slab_x3_ws_bytes / _slab_x3_prep (same checks,
+ *           same size, slab width and work list: the staged hash words leave the slab its 15 columns; 0 / BEVR_E_SHAPE
+ *           for S > 211, 0 / BEVR_E_PRECISION for any mode but BEVR_PREC_BF16X3); not interchangeable with the other
+ *           slab workspaces.
+ *   bevr_attn_slab_bwd_q_x3_dropout: operands and checks of bevr_attn_slab_bwd_q_x3, in its order (NULL, precision,
+ *           shape, alignment), after drop_thr < 65536 (else BEVR_E_SHAPE).  Per pair dS = P (keep ? D dP - delta :
+ *           -delta), D = 65536 / (65536 - drop_thr), applied by the kernel to the dP accumulator: dO is the UNSCALED
+ *           cotangent in the mode's split rows and delta = rowsum(dO * O) of the masked forward, grad_scale as for
+ *           bevr_attn_bwd_q_dropout (every Pmax of the contract read as D Pmax) -- the operands bevr_attn_bwd_q_dropout
+ *           takes in this mode.  The result is that kernel's on the same keys in the caller's order, up to the order of
+ *           the float atomics.  BEVR_E_PRECISION for any mode but BEVR_PREC_BF16X3. */
+size_t bevr_attn_slab_x3_drop_ws_bytes(const bevr_attn_desc* d);
+int bevr_attn_slab_x3_drop_prep(const bevr_attn_desc* d, const float* key_a, const float* key_b, const int32_t* order,
+                                void* slab_ws, void* stream);
+int bevr_attn_slab_bwd_q_x3_dropout(const bevr_attn_desc* d, const void* Q, const void* Ks, const void* Vs,
+                                    const void* slab_ws, const float* table_pair, const void* dO, const float* LSE,
+                                    const float* delta, const float* grad_scale, float* dQ, float* dtable,
+                                    unsigned drop_thr, unsigned drop_seed, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Bilinear feature sampling, align_corners=True, zero padding (grid_sample semantics).

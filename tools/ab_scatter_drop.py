@@ -10,7 +10,12 @@ B samples) in training mode with attn_drop_rate = 0.1, this route (BEVR_SCATTER_
 switch UNSET: the scattered keys on the region dropout kernels) alternating in ONE process, HIP events around each step,
 one warm-up step per route; medians of 5 with min and max, and the per-kernel times of one more step of each.
 
-    B=8 python tools/ab_scatter_drop.py [out.json]"""
+--x3: the same two measurements in the split-bf16 mode (bf16x3), where the switch moves the scattered keys' bwd_q alone
+(bevr_attn_slab_bwd_q_x3_dropout against bevr_attn_bwd_q_dropout, and against its no-mask version bevr_attn_slab_bwd_q_x3,
+which runs under the slab route's timer name).  Every route of that mode runs with BEVR_TAP_X3=1 BEVR_TAP_X3_DROP=1
+BEVR_SLAB_X3=1; BEVR_SCATTER_DROP is the one difference.  --kernel-only: the per-kernel part alone.
+
+    B=8 python tools/ab_scatter_drop.py [--x3] [--kernel-only] [out.json]"""
 import json
 import math
 import os
@@ -34,6 +39,9 @@ ROUTES = (("scatter_drop", {"BEVR_SCATTER_DROP": "1"}, True), ("region_drop", {"
 K = ops.K
 PAIRS = {"forward": {"scatter_drop": K.GATHER_DROP, "region_drop": K.FWD_DROP, "no_mask": K.GATHER},
          "bwd_q": {"scatter_drop": K.SLAB_BWD_Q_DROP, "region_drop": K.BWD_Q_DROP, "no_mask": K.SLAB_BWD_Q}}
+# the split-bf16 mode: its switches on every route; the no-mask slab kernel is timed under the slab route's name
+X3_BASE = {"BEVR_TAP_X3": "1", "BEVR_TAP_X3_DROP": "1", "BEVR_SLAB_X3": "1"}
+X3_PAIRS = {"bwd_q": {"scatter_drop": K.SLAB_BWD_Q_X3_DROP, "region_drop": K.BWD_Q_DROP, "no_mask": K.SLAB_BWD_Q}}
 
 
 def switches(sw):
@@ -48,7 +56,8 @@ def stats(v):
     return {"median_ms": round(statistics.median(v), 2), "min_ms": round(min(v), 2), "max_ms": round(max(v), 2)}
 
 
-def per_kernel(iters=7):
+def per_kernel(iters=7, x3=False):
+    prec, pairs = (_lib.PREC_BF16X3, X3_PAIRS) if x3 else (_lib.PREC_BF16, PAIRS)
     S, D, C, h, n_prob, N = 200, 5, 64, 2, 12, 36000
     Wt = 2 * S * D - 1
     gen = torch.Generator().manual_seed(5)
@@ -62,20 +71,20 @@ def per_kernel(iters=7):
     ms = {tag: {} for tag, _, _ in ROUTES}
     for it in range(iters + 1):
         for tag, sw, drop in ROUTES:
-            switches(sw)
+            switches(dict(X3_BASE, **sw) if x3 else sw)
             for t in (query, kv, table):
                 t.grad = None
             ops.KERNEL_TIMER.start()
-            out = ops.attention_core(query, None, None, pos, table, heads=h, groups=1, views=1, precision=_lib.PREC_BF16,
+            out = ops.attention_core(query, None, None, pos, table, heads=h, groups=1, views=1, precision=prec,
                                      kv=kv, attn_drop=(P, 1000 + it) if drop else None)
             out.backward(cot)
             rec = ops.KERNEL_TIMER.stop()
             if it > 0:
                 for k_, v_ in rec.items():
                     ms[tag].setdefault(k_, []).append(v_["ms"])
-    res = {"what": "scattered segment alone: S=200, D=5, %d problems x %d heads, N=%d, bf16, p=%g; per-kernel HIP events, "
-                   "medians of %d" % (n_prob, h, N, P, iters)}
-    for what, names in PAIRS.items():
+    res = {"what": "scattered segment alone: S=200, D=5, %d problems x %d heads, N=%d, %s, p=%g; per-kernel HIP events, "
+                   "medians of %d" % (n_prob, h, N, "bf16x3" if x3 else "bf16", P, iters)}
+    for what, names in pairs.items():
         row = {tag: dict(kernel=name, **stats(ms[tag][name])) for tag, name in names.items()}
         row["new_over_region_dropout"] = round(row["scatter_drop"]["median_ms"] / row["region_drop"]["median_ms"], 3)
         row["new_over_no_mask"] = round(row["scatter_drop"]["median_ms"] / row["no_mask"]["median_ms"], 3)
@@ -83,14 +92,14 @@ def per_kernel(iters=7):
     return res
 
 
-def per_block(B, iters=5):
+def per_block(B, iters=5, x3=False):
     S, D, V, C, h, img_w, img_h = 200, 5, 6, 64, 2, 704, 256
     Hi, Wi = img_h // 4, img_w // 4
     T, Kc = ring_rig(V, img_w, img_h)
     proj = BEV2CameraProjector(imu_to_rgb={0: T}, K={0: Kc}, vehicle_type_code=0, img_width=img_w, img_height=img_h,
                                ori_img_width=img_w, ori_img_height=img_h, device=DEV)
     sca = SpatialCrossAttn({"X": 50, "Y": 50, "Z": 2}, proj, S, D, -1.0, C, h, 1, 1, 3, B, True, n_views=V,
-                           attn_drop_rate=P, precision=_lib.PREC_BF16)
+                           attn_drop_rate=P, precision=_lib.PREC_BF16X3 if x3 else _lib.PREC_BF16)
     gen = torch.Generator().manual_seed(11)
     with torch.no_grad():
         for prm in sca.parameters():
@@ -100,6 +109,8 @@ def per_block(B, iters=5):
     x = torch.randn(B * V, C, Hi, Wi, generator=gen).to(DEV).requires_grad_(True)
     cot = torch.randn(B, C, S, S, generator=gen).to(DEV)
     routes = (("scatter_drop", {"BEVR_SCATTER_DROP": "1"}), ("parent_route", {"BEVR_SCATTER_DROP": None}))
+    if x3:
+        routes = tuple((tag, dict(X3_BASE, **sw)) for tag, sw in routes)
     times, kernels = {tag: [] for tag, _ in routes}, {}
 
     def step(tag, sw, record):
@@ -125,8 +136,8 @@ def per_block(B, iters=5):
                 times[tag].append(t_ms)
     for tag, sw in routes:
         step(tag, sw, True)
-    res = {"what": "SCA block forward + backward, bf16, S=200, 6 views, B=%d, training mode, attention dropout p=%g; routes "
-                   "alternating in one process, medians of %d" % (B, P, iters),
+    res = {"what": "SCA block forward + backward, %s, S=200, 6 views, B=%d, training mode, attention dropout p=%g; routes "
+                   "alternating in one process, medians of %d" % ("bf16x3" if x3 else "bf16", B, P, iters),
            "routes": {tag: sw for tag, sw in routes}}
     for tag, v in times.items():
         res[tag] = dict(stats(v), all_ms=[round(t, 1) for t in v])
@@ -136,10 +147,14 @@ def per_block(B, iters=5):
 
 
 def main():
-    res = {"per_kernel": per_kernel(), "per_block": per_block(int(os.environ.get("B", "8")))}
+    args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    x3 = "--x3" in sys.argv
+    res = {"per_kernel": per_kernel(x3=x3)}
+    if "--kernel-only" not in sys.argv:
+        res["per_block"] = per_block(int(os.environ.get("B", "8")), x3=x3)
     print(json.dumps(res, indent=1))
-    if sys.argv[1:]:
-        with open(sys.argv[1], "w") as f:
+    if args:
+        with open(args[0], "w") as f:
             json.dump(res, f, indent=1)
 
 

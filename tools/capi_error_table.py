@@ -45,6 +45,8 @@ SIZE_LIMITS = {
 LATER = {
     "scatter_dropout": ("scatter_dropout_error_codes.json",
                         ("bevr_attn_gather_fwd_dropout", "bevr_attn_slab_drop_prep", "bevr_attn_slab_bwd_q_dropout")),
+    "slab_x3_dropout": ("slab_x3_dropout_error_codes.json",
+                        ("bevr_attn_slab_x3_drop_prep", "bevr_attn_slab_bwd_q_x3_dropout")),
 }
 
 
