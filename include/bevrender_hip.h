@@ -643,7 +643,15 @@ int bevr_project_bev_grid_masked(const float* points_3d, const float* cam_inv, c
  * L2-normalised rows.   cam [n][E], map [m][E] float; D [n][m] float.
  *   normalize != 0: rows are L2-normalised first (the LpDistance(normalize_embeddings=True) of the
  *   retrieval losses); inv_norm_cam [n], inv_norm_map [m] receive 1/||row|| for the backward.
- * backward: dcam [n][E], dmap [m][E] written from dD [n][m].
+ *   n, m and E are any positive numbers, n != m included; D, the inverse norms and dD have no alignment contract.
+ *   normalize == 0: inv_norm_cam and inv_norm_map are not looked at and may be NULL (in the backward D too).
+ *   forward, E % 4 == 0: the rows are read as 16-byte vectors, so cam and map must be 16-byte aligned (BEVR_E_ALIGN
+ *   otherwise, nothing is written); E % 4 != 0: no alignment contract.
+ * backward: dcam [n][E], dmap [m][E] written from dD [n][m]; D, inv_norm_cam, inv_norm_map are the forward's (read only when
+ *   normalize != 0).  No pointer has an alignment contract and no call returns BEVR_E_ALIGN: with cam, map, dcam or dmap
+ *   off the 16-byte grid the backward runs on its scalar kernels and computes the same.
+ * errors, in this order: a NULL pointer that the call needs BEVR_E_NULL; n, m or E <= 0 BEVR_E_SHAPE; then the forward's
+ *   alignment rule.
  *   Aliased operands, cam == map (the same pointer) and n == m: dcam receives the SUM of both sides' gradients (the
  *   gradient of the one matrix both arguments are) and dmap is neither read nor written -- the same for every n, m, E
  *   and alignment.  A caller that wants the two sides apart passes two buffers (a copy of one side).
@@ -653,7 +661,10 @@ int bevr_corr_fwd(const float* cam, const float* map, float* D, float* inv_norm_
 int bevr_corr_bwd(const float* cam, const float* map, const float* D, const float* dD,
                   const float* inv_norm_cam, const float* inv_norm_map, float* dcam, float* dmap,
                   int n, int m, int E, int normalize, void* stream);
-/* Rank of the diagonal within its column (train.py:559-563): rank[k] = #{ i : D[i][k] < D[k][k] }. */
+/* Rank of the diagonal within its column (train.py:559-563): rank[k] = #{ i : D[i][k] < D[k][k] }.
+ *   D [n][n] float, rank [n] int32, any n > 0 (BEVR_E_SHAPE otherwise; a NULL pointer BEVR_E_NULL); no alignment contract.
+ *   The comparison is the float one: an entry equal to the diagonal is not counted, and a NaN counts on neither side
+ *   (a NaN diagonal has rank 0). */
 int bevr_recall_rank(const float* D, int32_t* rank, int n, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
