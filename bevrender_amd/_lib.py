@@ -34,6 +34,8 @@ SYMBOLS = [
     "bevr_attn_gather_fwd_dropout", "bevr_attn_slab_drop_ws_bytes", "bevr_attn_slab_drop_prep",
     "bevr_attn_slab_bwd_q_dropout",
     "bevr_kv_project_w2",
+    "bevr_attn_tap_g2_ws_bytes", "bevr_attn_tap_g2_prep", "bevr_attn_tap_g2_fwd", "bevr_attn_tap_g2_bwd_q",
+    "bevr_attn_tap_g2_bwd_k",
     "bevr_attn_slab_x3_drop_ws_bytes", "bevr_attn_slab_x3_drop_prep", "bevr_attn_slab_bwd_q_x3_dropout",
     "bevr_offset_head_fwd", "bevr_offset_head_bwd", "bevr_key_positions_fwd", "bevr_key_positions_bwd", "bevr_kv_project", "bevr_layernorm_fwd", "bevr_layernorm_bwd", "bevr_merge_views_fwd", "bevr_merge_views_bwd", "bevr_merge_tap_fwd", "bevr_merge_tap_bwd", "bevr_attn_bwd_prep", "bevr_pack_kv", "bevr_unpack_dkv",
 ]
@@ -106,6 +108,11 @@ def lib() -> C.CDLL:
         L.bevr_attn_tap_fwd.argtypes = [dp, vp, vp, fp, fp, fp, vp, vp]
         L.bevr_attn_tap_bwd_q.argtypes = [dp, vp, vp, vp, fp, fp, fp, vp]
         L.bevr_attn_tap_bwd_k.argtypes = [dp, vp, vp, vp, fp, fp, fp, fp, fp, vp]
+        L.bevr_attn_tap_g2_ws_bytes.argtypes = [dp]
+        L.bevr_attn_tap_g2_prep.argtypes = L.bevr_attn_tap_prep.argtypes
+        L.bevr_attn_tap_g2_fwd.argtypes = L.bevr_attn_tap_fwd.argtypes
+        L.bevr_attn_tap_g2_bwd_q.argtypes = L.bevr_attn_tap_bwd_q.argtypes
+        L.bevr_attn_tap_g2_bwd_k.argtypes = L.bevr_attn_tap_bwd_k.argtypes
         L.bevr_attn_tap_fwd_dropout.argtypes = [dp, vp, vp, fp, fp, fp, fp, vp, u32, u32, u32, vp]
         L.bevr_attn_tap_bwd_q_dropout.argtypes = [dp, vp, vp, vp, fp, fp, fp, u32, u32, u32, vp]
         L.bevr_attn_tap_bwd_k_dropout.argtypes = [dp, vp, vp, vp, fp, fp, fp, fp, fp, u32, u32, u32, vp]
@@ -162,7 +169,7 @@ def lib() -> C.CDLL:
         L.bevr_unpack_dkv.argtypes = [fp] * 4 + [C.c_longlong, C.c_longlong] + [ip] * 5 + [vp]
         for name in SYMBOLS:
             fn = getattr(L, name)
-            if name in ("bevr_attn_key_ws_bytes", "bevr_attn_tap_ws_bytes", "bevr_attn_slab_ws_bytes",
+            if name in ("bevr_attn_key_ws_bytes", "bevr_attn_tap_ws_bytes", "bevr_attn_tap_g2_ws_bytes", "bevr_attn_slab_ws_bytes",
                         "bevr_attn_slab_rows_ws_bytes", "bevr_attn_slab_x3_ws_bytes", "bevr_attn_slab_drop_ws_bytes",
                         "bevr_attn_slab_x3_drop_ws_bytes",
                         "bevr_attn_bwd_k_ws_bytes", "bevr_attn_tap_bwd_k_ws_bytes"):

@@ -37,14 +37,40 @@ constexpr int QB = 16;          // BEV rows per matrix tile
 
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 
+// TWO CHANNEL GROUPS (attn_tap_*_g2.hip: #define BEVR_TAP_G2 1 and #include the kernel's source; 16-bit modes).  Group g'
+// samples its C / 2 channels at its own position, proj_k / proj_v mix all channels and a head's bias follows its own
+// group g, so for a head of group g
+//     S[n][q] = sum_g' sum_t w_t^g'(n) G^g'[t][q] + Gb[q] + bias^g[n][q],     R^g'[t][q] = sum_n w_t^g'(n) P[n][q]
+// 12 tap slots per group: G, H, R, dG are TAP_ROW = 32 slots wide, block 0 (slots 0..15) as with one group and group 0's
+// taps, block 1 group 1's taps in its slots 0..11 and zeros behind them.  Softmax does not care about key order and a
+// head needs (a, b) of its own group only, so every (problem, group) ROW p * 2 + g has its own key order (cell-sorted
+// by group g's table coordinates): its records hold (a, b) of group g and the sampling positions of BOTH groups for the
+// key at that index.  The second logit product is one more depth-32 matrix product, [w^1 | 0] against [G^1 ; 0]: the
+// group's weights are a third LDS image of the first's shape, read plainly for S / dP and transposed for R / dG.
+#ifndef BEVR_TAP_G2
+#define BEVR_TAP_G2 0
+#endif
+constexpr int TAP_NG = BEVR_TAP_G2 ? 2 : 1;          // channel groups of this translation unit
+constexpr int TAP_ROW = TAP_SLOTS * TAP_NG;         // slots of a row of G, H, R, dG
+// sampling position of group 1 for the key of a record (group 0's is the record's)
+struct TapPos1 { float ys, xs; };
+
 // per key, written by bevr_attn_tap_prep: clamped table coordinates and the sampling position in feature pixels
 // (a masked key: ys = TAP_YS_DEAD, every tap weight 0)
 struct TapRec { float a, b, ys, xs; };
 #define TAP_YS_DEAD (-100.0f)
 
-// workspace layout: TapRec[n_prob][Np] | StepBox[n_prob][Np / 32]
+// workspace layout: TapRec[rows][Np] | StepBox[rows][Np / 32] (| two groups: TapPos1[rows][Np]), rows = n_prob * TAP_NG
+__host__ __device__ __forceinline__ size_t tap_ws_rows(const bevr_attn_desc& d) { return (size_t)d.n_prob * TAP_NG; }
 __host__ __device__ __forceinline__ size_t tap_ws_box_offset(const bevr_attn_desc& d) {
-  return (size_t)d.n_prob * d.Np * sizeof(TapRec);
+  return tap_ws_rows(d) * d.Np * sizeof(TapRec);
+}
+__host__ __device__ __forceinline__ size_t tap_ws_pos1_offset(const bevr_attn_desc& d) {
+  return tap_ws_box_offset(d) + tap_ws_rows(d) * (d.Np / 32) * sizeof(StepBox);
+}
+// the record row of (problem, head): with two groups the head's group picks it
+__device__ __forceinline__ int tap_key_row(const bevr_attn_desc& d, int prob, int hd) {
+  return BEVR_TAP_G2 ? prob * 2 + hd / (d.heads >> 1) : prob;
 }
 
 // BEVR_PREC_BF16X3 (bevr_common.h: split-bf16 products at f32 tolerance) on the tap kernels.  Every matrix operand is two
@@ -184,6 +210,25 @@ template <int PREC> __device__ __forceinline__ void tap_weights(float ys, float 
   t[1] = tap_pack8<PREC>(w[1]);
 }
 
+#if BEVR_TAP_G2
+// the slot weights of group 1 for one key: the 12 taps alone (the constant slots ride in group 0's image)
+template <int PREC> __device__ __forceinline__ void tap_weights1(float ys, float xs, TapOpP<PREC> (&t)[2]) {
+  float wy[TAP_R], wx[TAP_C], w[2][8];
+#pragma unroll
+  for (int r = 0; r < TAP_R; ++r) wy[r] = hat((float)r - ys);
+#pragma unroll
+  for (int c = 0; c < TAP_C; ++c) wx[c] = hat((float)c - xs);
+#pragma unroll
+  for (int r = 0; r < TAP_R; ++r)
+#pragma unroll
+    for (int c = 0; c < TAP_C; ++c) w[(r * TAP_C + c) >> 3][(r * TAP_C + c) & 7] = wy[r] * wx[c];
+#pragma unroll
+  for (int k = TAP_N; k < TAP_SLOTS; ++k) w[1][k - 8] = 0.f;
+  t[0] = tap_pack8<PREC>(w[0]);
+  t[1] = tap_pack8<PREC>(w[1]);
+}
+#endif
+
 // cells 8 hf .. 8 hf + 7 of the bias chunk for one key, the arithmetic and the order of cell_weights (attn_cell.h):
 // element e = column 2 hf + (e >> 2), row e & 3
 template <int PREC> __device__ __forceinline__ TapOpP<PREC> tap_cell_half(float tcol, float trow, int hf) {
@@ -246,10 +291,12 @@ template <int NP> struct LdsTn {
   static constexpr int OFF_TAPS = 0;            // [64 keys][16 slots] 16-bit
   static constexpr int OFF_CELLS = 2048;        // [64 keys][16 cells] 16-bit
   static constexpr int OFF_LO = 4096;
-  static constexpr int OFF_CT = 4096 * NP;      // u32x4: flags (bit 0 / 1: tile 0 / 1 live, bit 2: done), alloc0, alloc1, 0
+  static constexpr int OFF_TAPS1 = 4096 * NP;   // two groups: [64 keys][16 slots] 16-bit, group 1's weights
+  static constexpr int G2B = BEVR_TAP_G2 ? 2048 : 0;
+  static constexpr int OFF_CT = 4096 * NP + G2B;   // u32x4: flags (bit 0 / 1: tile 0 / 1 live, bit 2: done), alloc0, alloc1, 0
                                                 //        (dropout build: the 4th dword = record index of tile 0's first key)
-  static constexpr int OFF_ORG = 4096 * NP + 16;   // i32x4: chunk origin of tile 0 (x0, a0), of tile 1 (x0, a0)
-  static constexpr int BUF = 4096 * NP + 32;
+  static constexpr int OFF_ORG = 4096 * NP + G2B + 16;   // i32x4: chunk origin of tile 0 (x0, a0), of tile 1 (x0, a0)
+  static constexpr int BUF = 4096 * NP + G2B + 32;
   static constexpr int RING = 4;
 };
 typedef LdsTn<1> LdsT;
@@ -266,6 +313,9 @@ __device__ __forceinline__ bool box_fits(const StepBox& sb, float jrx) {
 template <int PREC>
 __device__ __forceinline__ void tap_producer(const bevr_attn_desc& d, char* smem, char* ring, int img_bytes, int rows_img,
                                              const TapRec* __restrict__ recs, const StepBox* __restrict__ box,
+#if BEVR_TAP_G2
+                                             const TapPos1* __restrict__ pos1,
+#endif
                                              const char* __restrict__ tbl, float jrx, int lane) {
   typedef LdsTp<PREC> L;
   const int hi = lane >> 5;
@@ -302,9 +352,16 @@ __device__ __forceinline__ void tap_producer(const bevr_attn_desc& d, char* smem
   for (int o = lane * 16; o < img_bytes; o += 64 * 16) *reinterpret_cast<u32x4*>(ring + o) = u32x4{0u, 0u, 0u, 0u};
   TapRec rc_n = recs[lane];
   StepBox sb_n = box[hi];
+#if BEVR_TAP_G2
+  TapPos1 p1_n = pos1[lane];
+#endif
   for (int step = 0; step < n_step; ++step) {
     const TapRec rc = rc_n;
     const StepBox sb = sb_n;
+#if BEVR_TAP_G2
+    const TapPos1 p1 = p1_n;
+    if (step + 1 < n_step) p1_n = pos1[(size_t)(step + 1) * KT + lane];
+#endif
     if (step + 1 < n_step) {   // the next step's records are in flight while this one is emitted
       rc_n = recs[(size_t)(step + 1) * KT + lane];
       sb_n = box[2 * (step + 1) + hi];
@@ -343,6 +400,11 @@ __device__ __forceinline__ void tap_producer(const bevr_attn_desc& d, char* smem
         tap_st(bb + L::OFF_TAPS + lane * 32 + 16 * k, L::OFF_LO, t[k]);
         tap_st(bb + L::OFF_CELLS + lane * 32 + 16 * k, L::OFF_LO, tap_cell_half<PREC>(tcol, rc.a - (float)a0, k));
       }
+#if BEVR_TAP_G2
+      tap_weights1<PREC>(sel ? p1.ys : TAP_YS_DEAD, p1.xs, t);
+#pragma unroll
+      for (int k = 0; k < 2; ++k) tap_st(bb + L::OFF_TAPS1 + lane * 32 + 16 * k, L::OFF_LO, t[k]);
+#endif
       int al0 = alloc, al1 = alloc, ox0 = tag_x, oa0 = tag_a;
       if (ok0) {
         const int x = __builtin_amdgcn_readlane(x0, 0), a = __builtin_amdgcn_readlane(a0, 0);

@@ -33,13 +33,15 @@ template <int NP> struct LdsKn {
   static constexpr int OFF_G = 0;      // [32 rows][16 slots] 16-bit
   static constexpr int OFF_H = 1024;
   static constexpr int OFF_LO = 2048;
-  static constexpr int SLAB = 2048 * NP;    // one slab's G | H rows
+  static constexpr int OFF_G1 = 2048;       // two groups (NP = 1): the same two images of slots 16..31
+  static constexpr int SLAB = 2048 * NP * TAP_NG;    // one slab's G | H rows
   static constexpr int BUF = SPB * SLAB;
 };
 typedef LdsKn<1> LdsK;
 template <int PREC> using LdsKp = LdsKn<tap_np<PREC>>;
 // (split mode: every operand twice -- the registers of 2 waves per SIMD)
-constexpr int tap_bwd_k_waves(int prec) { return tap_split(prec) ? 2 : 4; }
+// (two groups: the operands and accumulators of the second group's slots likewise)
+constexpr int tap_bwd_k_waves(int prec) { return tap_split(prec) || BEVR_TAP_G2 ? 2 : 4; }
 // dwords per (kind, parity, column) of a window: rows 0 .. Sp + NRX + 7, two rows per dword
 __host__ __device__ __forceinline__ int win_dwords(int Sp) { return (Sp + NRX + 8) / 2; }
 
@@ -84,7 +86,7 @@ __device__ __forceinline__ void tap_bwd_k_body(
   constexpr bool X3 = tap_split(PREC);
   constexpr int NP = tap_np<PREC>;
 
-  const int n_ph = d.n_prob * d.heads;
+  [[maybe_unused]] const int n_ph = d.n_prob * d.heads;
   const int prob = ph / d.heads, hd = ph % d.heads;
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
@@ -95,7 +97,8 @@ __device__ __forceinline__ void tap_bwd_k_body(
   const float rx = (float)(d.Wt - 1) / (2.0f * (float)(d.S - 1));
   const int HpT = d.Hp + 1;                                   // rows of a column of the plain transposed table
   const float* tbl = table_t + (size_t)hd * d.Wp * HpT;
-  const StepBox* box = reinterpret_cast<const StepBox*>(tap_ws + tap_ws_box_offset(d)) + (size_t)prob * (d.Np / 32);
+  const int krow = tap_key_row(d, prob, hd);                  // the record row: the problem; two groups: (problem, head's group)
+  const StepBox* box = reinterpret_cast<const StepBox*>(tap_ws + tap_ws_box_offset(d)) + (size_t)krow * (d.Np / 32);
   const int NRWD = win_dwords(d.Sp);
   const int win_bytes = 4 * NCW * NRWD * 4;                   // [kind hi / lo][row parity][NCW columns][NRWD dwords]
   char* win_base = smem + 2 * L::BUF;
@@ -188,11 +191,26 @@ __device__ __forceinline__ void tap_bwd_k_body(
       item_load(1, slice_item(0, 0), f0);
       item_load(1, slice_item(0, 1), f1);
     }
-    const char* Gp = G + ((size_t)ph * Mp) * 32 + lane * 16;
-    const char* Hq = H + ((size_t)ph * Mp) * 32 + lane * 16;
+    const char* Gp = G + ((size_t)ph * Mp) * (TAP_ROW * 2) + lane * 16;
+    const char* Hq = H + ((size_t)ph * Mp) * (TAP_ROW * 2) + lane * 16;
     // slab `sl` (0 .. S nslab - 1, column-major) of the packed rows starts sl * 1024 bytes in; a step stages SPB slabs
     auto slab_index = [&](int j2, int st2, int u) { return min(j2 * nslab + min(SPB * st2 + u, nslab - 1), d.S * nslab - 1); };
     int e = 0;
+#if BEVR_TAP_G2
+    // a slab's rows are 64 bytes: 128 chunks of 16, chunk lane + 64 k = (row (lane >> 2) + 16 k, quarter lane & 3);
+    // quarters 0, 1 are the row of the first image (slots 0..15), quarters 2, 3 of the second
+    u32x4 gv[2][SPB], hv[2][SPB];
+    auto rows_load = [&](int j2, int st2) {
+#pragma unroll
+      for (int k = 0; k < 2; ++k)
+#pragma unroll
+        for (int u = 0; u < SPB; ++u) {
+          gv[k][u] = gload16(Gp + k * 1024 + (size_t)slab_index(j2, st2, u) * 2048);
+          hv[k][u] = gload16(Hq + k * 1024 + (size_t)slab_index(j2, st2, u) * 2048);
+        }
+    };
+    const int row_dst = ((lane & 3) >> 1) * L::OFF_G1 + (lane >> 2) * 32 + (lane & 1) * 16;
+#else
     u32x4 gv[NP][SPB], hv[NP][SPB];       // the rows in flight, per image
     const size_t g_lo = (size_t)n_ph * Mp * 32;     // the lo planes of G and H
     auto rows_load = [&](int j2, int st2) {
@@ -204,10 +222,20 @@ __device__ __forceinline__ void tap_bwd_k_body(
           hv[pl][u] = gload16(Hq + pl * g_lo + (size_t)slab_index(j2, st2, u) * 1024);
         }
     };
+#endif
     rows_load(0, 0);
     for (int j = 0; j < d.S; ++j) {
       for (int st = 0; st < nstep; ++st, ++e) {
         char* bb = smem + (e & 1) * L::BUF;
+#if BEVR_TAP_G2
+#pragma unroll
+        for (int k = 0; k < 2; ++k)
+#pragma unroll
+          for (int u = 0; u < SPB; ++u) {
+            *reinterpret_cast<u32x4*>(bb + u * L::SLAB + L::OFF_G + row_dst + k * 512) = gv[k][u];
+            *reinterpret_cast<u32x4*>(bb + u * L::SLAB + L::OFF_H + row_dst + k * 512) = hv[k][u];
+          }
+#else
 #pragma unroll
         for (int pl = 0; pl < NP; ++pl)
 #pragma unroll
@@ -215,6 +243,7 @@ __device__ __forceinline__ void tap_bwd_k_body(
             *reinterpret_cast<u32x4*>(bb + u * L::SLAB + pl * L::OFF_LO + L::OFF_G + lane * 16) = gv[pl][u];
             *reinterpret_cast<u32x4*>(bb + u * L::SLAB + pl * L::OFF_LO + L::OFF_H + lane * 16) = hv[pl][u];
           }
+#endif
         if constexpr (!SLOW) {
           item_store(j + 1, slice_item(st, 0), f0);
           item_store(j + 1, slice_item(st, 1), f1);
@@ -243,7 +272,12 @@ __device__ __forceinline__ void tap_bwd_k_body(
   // ---- key waves ---------------------------------------------------------------------------------------------------
   const int tile = wg * NKW + tslot;
   const bool have_tile = tile < n_tiles;            // uniform; a wave without a tile only keeps the barriers
-  const TapRec* recs = reinterpret_cast<const TapRec*>(tap_ws) + (size_t)prob * d.Np;
+  const TapRec* recs = reinterpret_cast<const TapRec*>(tap_ws) + (size_t)krow * d.Np;
+#if BEVR_TAP_G2
+  const TapPos1* pos1 = reinterpret_cast<const TapPos1*>(tap_ws + tap_ws_pos1_offset(d)) + (size_t)krow * d.Np;
+  TapOp<NP> bk1[2];          // group 1's tap slots (lanes 0..31; lanes 32..63 zero)
+  f32x4 zt1[2], zv1[2];      // Z of group 1's slots
+#endif
   const int tl = have_tile ? tile : 0;
   const StepBox sb = box[tl];
   const int da = sb.amin - a0w;                       // rows between the window's origin and this tile's chunk origin
@@ -265,6 +299,14 @@ __device__ __forceinline__ void tap_bwd_k_body(
     zt[kb] = f32x4{0.f, 0.f, 0.f, 0.f};
     zv[kb] = f32x4{0.f, 0.f, 0.f, 0.f};
     zc[kb] = f32x4{0.f, 0.f, 0.f, 0.f};
+#if BEVR_TAP_G2
+    const TapPos1 q1 = pos1[(size_t)tl * 32 + 16 * kb + li];
+    tap_weights1<PREC>(r0.ys < -50.0f ? TAP_YS_DEAD : q1.ys, q1.xs, t);
+    bk1[kb] = TapOp<NP>{};
+    if (g < 2) bk1[kb] = g == 0 ? t[0] : t[1];
+    zt1[kb] = f32x4{0.f, 0.f, 0.f, 0.f};
+    zv1[kb] = f32x4{0.f, 0.f, 0.f, 0.f};
+#endif
   }
   const int a_row = L::OFF_G + li * 32 + (g & 1) * 16;                          // row read of a staged image (lanes 0..31)
   const int t_off = (4 * g + (li >> 2)) * 32 + (lane & 3) * 8;                  // transposed read, second block + 512
@@ -314,6 +356,19 @@ __device__ __forceinline__ void tap_bwd_k_body(
     }
     const TapOp<NP> gt = tap_ld_tr<NP>(base + L::OFF_G + t_off, 512, L::OFF_LO);
     const TapOp<NP> ht = tap_ld_tr<NP>(base + L::OFF_H + t_off, 512, L::OFF_LO);
+#if BEVR_TAP_G2
+    TapOp<NP> qa1[2], ha1[2];   // the rows' slots 16..31 (lanes 0..31)
+#pragma unroll
+    for (int rb = 0; rb < 2; ++rb) {
+      qa1[rb] = ha1[rb] = TapOp<NP>{};
+      if (g < 2) {
+        qa1[rb] = tap_ld<NP>(base + L::OFF_G1 + a_row + rb * 512, L::OFF_LO);
+        ha1[rb] = tap_ld<NP>(base + L::OFF_G1 + L::OFF_H - L::OFF_G + a_row + rb * 512, L::OFF_LO);
+      }
+    }
+    const TapOp<NP> gt1 = tap_ld_tr<NP>(base + L::OFF_G1 + L::OFF_G + t_off, 512, L::OFF_LO);
+    const TapOp<NP> ht1 = tap_ld_tr<NP>(base + L::OFF_G1 + L::OFF_H + t_off, 512, L::OFF_LO);
+#endif
     bf16x8 thi = gt.p[0], tlo = gt.p[0];
     if constexpr (FIT) {
       const uint32_t* w0 = reinterpret_cast<const uint32_t*>(win_b + wth + 2 * i0);
@@ -339,10 +394,17 @@ __device__ __forceinline__ void tap_bwd_k_body(
 #pragma unroll
     for (int kb = 0; kb < 2; ++kb) {
       const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
+#if BEVR_TAP_G2
+      const f32x4 s0 = tap_mm<PREC, true>(qa[0], bk[kb], tap_mm<PREC, true>(qa1[0], bk1[kb], z4));
+      const f32x4 s1 = tap_mm<PREC, true>(qa[1], bk[kb], tap_mm<PREC, true>(qa1[1], bk1[kb], z4));
+      const f32x4 q0 = tap_mm<PREC>(ha[0], bk[kb], tap_mm<PREC>(ha1[0], bk1[kb], z4));
+      const f32x4 q1 = tap_mm<PREC>(ha[1], bk[kb], tap_mm<PREC>(ha1[1], bk1[kb], z4));
+#else
       const f32x4 s0 = tap_mm<PREC, true>(qa[0], bk[kb], z4);       // S[query 4 g + e of row block 0][key]
       const f32x4 s1 = tap_mm<PREC, true>(qa[1], bk[kb], z4);
       const f32x4 q0 = tap_mm<PREC>(ha[0], bk[kb], z4);             // dP
       const f32x4 q1 = tap_mm<PREC>(ha[1], bk[kb], z4);
+#endif
       float p[8], ds[8];
       if constexpr (!FIT) {
         const TapRec rk = stash[16 * kb + li];
@@ -403,6 +465,10 @@ __device__ __forceinline__ void tap_bwd_k_body(
       const TapOp<NP> ds8 = tap_op(dsw), p8 = tap_op(pw);
       zt[kb] = tap_mm<PREC>(gt, ds8, zt[kb]);
       zv[kb] = tap_mm<PREC>(ht, p8, zv[kb]);
+#if BEVR_TAP_G2
+      zt1[kb] = tap_mm<PREC>(gt1, ds8, zt1[kb]);
+      zv1[kb] = tap_mm<PREC>(ht1, p8, zv1[kb]);
+#endif
       if constexpr (FIT) {
         // the window's hi + lo parts against dS, small terms first (split mode: the lo image of dS against the hi part too)
         zc[kb] = mfma16<PREC>(tlo, ds8.p[0], zc[kb]);
@@ -534,6 +600,33 @@ __device__ __forceinline__ void tap_bwd_k_body(
     gy += __shfl_xor(gy, 16); gx += __shfl_xor(gx, 16); va += __shfl_xor(va, 16); vb += __shfl_xor(vb, 16);
     gy += __shfl_xor(gy, 32); gx += __shfl_xor(gx, 32); va += __shfl_xor(va, 32); vb += __shfl_xor(vb, 32);
     const int n = tile * 32 + 16 * kb + li;
+#if BEVR_TAP_G2
+    // group 1's sampling position through its own slots; dkey_y, dkey_x [row][2][Np]
+    const TapPos1 q1 = pos1[(size_t)tl * 32 + 16 * kb + li];
+    const float y1 = floorf(q1.ys), x1f = floorf(q1.xs);
+    float gy1 = 0.f, gx1 = 0.f;
+#pragma unroll
+    for (int e2 = 0; e2 < 4; ++e2) {
+      const int t = 4 * g + e2;
+      const float r = (float)(t / 3), c = (float)(t % 3);
+      const float dwy = (r == y1 + 1.0f ? 1.0f : 0.f) - (r == y1 ? 1.0f : 0.f);
+      const float dwx = (c == x1f + 1.0f ? 1.0f : 0.f) - (c == x1f ? 1.0f : 0.f);
+      const float z = g < 3 ? zt1[kb][e2] + BEVR_LOG2E * zv1[kb][e2] : 0.f;
+      gy1 += z * dwy * hat(c - q1.xs);
+      gx1 += z * hat(r - q1.ys) * dwx;
+    }
+    gy1 += __shfl_xor(gy1, 16); gx1 += __shfl_xor(gx1, 16);
+    gy1 += __shfl_xor(gy1, 32); gx1 += __shfl_xor(gx1, 32);
+    if (g == 0 && n < d.N) {
+      const size_t idx = (size_t)krow * d.Np + n;
+      atomicAdd(dkey_a + idx, va);
+      atomicAdd(dkey_b + idx, vb);
+      atomicAdd(dkey_y + idx + (size_t)krow * d.Np, gy);
+      atomicAdd(dkey_x + idx + (size_t)krow * d.Np, gx);
+      atomicAdd(dkey_y + idx + (size_t)(krow + 1) * d.Np, gy1);
+      atomicAdd(dkey_x + idx + (size_t)(krow + 1) * d.Np, gx1);
+    }
+#else
     if (g == 0 && n < d.N) {
       const size_t idx = (size_t)prob * d.Np + n;
       atomicAdd(dkey_a + idx, va);
@@ -541,6 +634,7 @@ __device__ __forceinline__ void tap_bwd_k_body(
       atomicAdd(dkey_y + idx, gy);
       atomicAdd(dkey_x + idx, gx);
     }
+#endif
   }
 }
 
@@ -559,7 +653,7 @@ __global__ __launch_bounds__(64 * (NKW + 1), tap_bwd_k_waves(PREC)) void attn_ta
                                                     d.S, slow_list TAP_DROP_ARGS);
 }
 
-#if !BEVR_DROP && !BEVR_TAP_X3
+#if !BEVR_DROP && !BEVR_TAP_X3 && !BEVR_TAP_G2
 // The list launch: every wave claims (listed tile, range of BEV columns) items from the counter list[1] until they run
 // out -- the items' cost varies with the number of unfit columns, so they are claimed, not dealt.  The list is complete
 // (the main launch precedes this one on the stream); a claim never waits, and every wave reaches the exit.  An empty
@@ -623,7 +717,7 @@ int launch(const bevr_attn_desc& d, const void* G, const void* H, const void* ta
   BEVR_TAP_LAUNCH(false, slow_list);
   rc = (int)hipGetLastError();
   if (rc) return rc;
-#if !BEVR_DROP && !BEVR_TAP_X3
+#if !BEVR_DROP && !BEVR_TAP_X3 && !BEVR_TAP_G2
   if (slow_list) {
     const size_t lds_list = LIST_WAVES * (2 * L::SLAB + 32 * sizeof(TapRec));
     const int n_wg = bevr_list_workgroups<&attn_tap_bwd_k_list_kernel<PREC>>(max_wg, 64 * LIST_WAVES, lds_list);
@@ -647,10 +741,10 @@ int run(const bevr_attn_desc* d, const void* G, const void* H, const void* tap_w
   int rc = bevr_check_desc(d);
   if (rc) return rc;
   if (!G || !H || !tap_ws || !table_t || !dkey_a || !dkey_b || !dkey_y || !dkey_x) return BEVR_E_NULL;
-  if (d->groups != 1) return BEVR_E_SHAPE;
+  if (d->groups != TAP_NG || (BEVR_TAP_G2 && (d->heads & 1))) return BEVR_E_SHAPE;
   if (!bevr_aligned16(G) || !bevr_aligned16(H) || !bevr_aligned16(tap_ws)) return BEVR_E_ALIGN;
   hipStream_t st = (hipStream_t)stream;
-#if !BEVR_DROP && !BEVR_TAP_X3
+#if !BEVR_DROP && !BEVR_TAP_X3 && !BEVR_TAP_G2
   // the split mode's kernels are attn_tap_bwd_k_x3.hip's
   if (d->precision == BEVR_PREC_BF16X3 && !slow_list)
     return bevr_tap_bwd_k_x3(*d, G, H, tap_ws, table_t, dkey_a, dkey_b, dkey_y, dkey_x, st);
@@ -662,7 +756,15 @@ int run(const bevr_attn_desc* d, const void* G, const void* H, const void* tap_w
 
 }  // namespace
 
-#if BEVR_TAP_X3 && !BEVR_DROP
+#if BEVR_TAP_G2
+// two channel groups: this translation unit is attn_tap_bwd_k_g2.hip, an entry point of its own (16-bit modes, no keep
+// mask; the slow pairs by the main grid launched again: no work list)
+extern "C" int bevr_attn_tap_g2_bwd_k(const bevr_attn_desc* d, const void* G, const void* H, const void* tap_ws,
+                                      const float* table_t, float* dkey_a, float* dkey_b, float* dkey_y, float* dkey_x,
+                                      void* stream) {
+  return run<BEVR_PREC_BF16, BEVR_PREC_F16>(d, G, H, tap_ws, table_t, dkey_a, dkey_b, dkey_y, dkey_x, nullptr, 0, stream);
+}
+#elif BEVR_TAP_X3 && !BEVR_DROP
 // the split-mode instantiations: this translation unit is attn_tap_bwd_k_x3.hip, entered from bevr_attn_tap_bwd_k
 int bevr_tap_bwd_k_x3(const bevr_attn_desc& d, const void* G, const void* H, const void* tap_ws, const float* table_t,
                       float* dkey_a, float* dkey_b, float* dkey_y, float* dkey_x, hipStream_t st) {

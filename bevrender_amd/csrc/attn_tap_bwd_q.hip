@@ -19,7 +19,9 @@ namespace {
 // (split mode: every operand twice -- the fat NB = 4 instantiation gets the registers of 2 waves per SIMD; with the keep
 // mask NB = 2 spills 84 bytes a lane at the 128 registers of 4 waves: 3)
 constexpr int tap_bwd_q_waves(int prec, int nb) {
-  return tap_split(prec) && nb == 4 ? 2 : tap_split(prec) && BEVR_DROP && nb == 2 ? 3 : 4;
+  // (two groups: two more B operands and one more accumulator per row block -- the fat instantiation as the split mode's)
+  // (NB = 2 with two groups spills 12 bytes a lane in fp16 at the 128 registers of 4 waves: 3)
+  return (tap_split(prec) || BEVR_TAP_G2) && nb == 4 ? 2 : ((tap_split(prec) && BEVR_DROP) || BEVR_TAP_G2) && nb == 2 ? 3 : 4;
 }
 template <int PREC, int NB>
 __global__ __launch_bounds__(512, tap_bwd_q_waves(PREC, NB)) void attn_tap_bwd_q_kernel(
@@ -48,9 +50,15 @@ __global__ __launch_bounds__(512, tap_bwd_q_waves(PREC, NB)) void attn_tap_bwd_q
   const float jrx = (float)j * rx;
 
   if (wave == n_wave - 1) {
-    const TapRec* recs = reinterpret_cast<const TapRec*>(tap_ws) + (size_t)prob * d.Np;
-    const StepBox* box = reinterpret_cast<const StepBox*>(tap_ws + tap_ws_box_offset(d)) + (size_t)prob * (d.Np / 32);
+    const int krow = tap_key_row(d, prob, hd);
+    const TapRec* recs = reinterpret_cast<const TapRec*>(tap_ws) + (size_t)krow * d.Np;
+    const StepBox* box = reinterpret_cast<const StepBox*>(tap_ws + tap_ws_box_offset(d)) + (size_t)krow * (d.Np / 32);
+#if BEVR_TAP_G2
+    const TapPos1* pos1 = reinterpret_cast<const TapPos1*>(tap_ws + tap_ws_pos1_offset(d)) + (size_t)krow * d.Np;
+    tap_producer<PREC>(d, smem, ring, img_bytes, rows_img, recs, box, pos1, tbl, jrx, lane);
+#else
     tap_producer<PREC>(d, smem, ring, img_bytes, rows_img, recs, box, tbl, jrx, lane);
+#endif
     return;
   }
 
@@ -59,6 +67,10 @@ __global__ __launch_bounds__(512, tap_bwd_q_waves(PREC, NB)) void attn_tap_bwd_q
   TapOp<NP> hop[NB];     // lanes 0..31 H[q][8 kg ..], lanes 32..63 zero
   f32x4 ytap[NB], ycell[NB];
   size_t mqv[NB];
+#if BEVR_TAP_G2
+  TapOp<NP> bop2[NB], hop2[NB];     // group 1: lanes 0..31 G / H[q][16 + 8 kg ..], lanes 32..63 zero
+  f32x4 ytap1[NB];
+#endif
   const size_t g_lo = (size_t)n_ph * Mp * TAP_SLOTS * 2;     // the lo planes of G and H
 #pragma unroll
   for (int nb = 0; nb < NB; ++nb) {
@@ -67,9 +79,17 @@ __global__ __launch_bounds__(512, tap_bwd_q_waves(PREC, NB)) void attn_tap_bwd_q
     mqv[nb] = mq;
     bop[nb] = hop[nb] = TapOp<NP>{};
     if (kg < 2) {
-      bop[nb] = tap_ld<NP>(G + (mq * TAP_SLOTS + 8 * kg) * 2, g_lo);
-      hop[nb] = tap_ld<NP>(H + (mq * TAP_SLOTS + 8 * kg) * 2, g_lo);
+      bop[nb] = tap_ld<NP>(G + (mq * TAP_ROW + 8 * kg) * 2, g_lo);
+      hop[nb] = tap_ld<NP>(H + (mq * TAP_ROW + 8 * kg) * 2, g_lo);
     }
+#if BEVR_TAP_G2
+    bop2[nb] = hop2[nb] = TapOp<NP>{};
+    if (kg < 2) {
+      bop2[nb] = tap_ld<NP>(G + (mq * TAP_ROW + TAP_SLOTS + 8 * kg) * 2, g_lo);
+      hop2[nb] = tap_ld<NP>(H + (mq * TAP_ROW + TAP_SLOTS + 8 * kg) * 2, g_lo);
+    }
+    ytap1[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
+#endif
     ytap[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
     ycell[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
@@ -81,9 +101,9 @@ __global__ __launch_bounds__(512, tap_bwd_q_waves(PREC, NB)) void attn_tap_bwd_q
 #pragma unroll
   for (int nb = 0; nb < NB; ++nb) {
     hrow[nb] = bevr_drop_row(drop_seed, (uint32_t)ph, (uint32_t)(j * d.Sp + min(blk0 + nb, nblk - 1) * QB + li));
-    const uint32_t c2 = *reinterpret_cast<const uint32_t*>(H + (mqv[nb] * TAP_SLOTS + TAP_CHI) * 2);
+    const uint32_t c2 = *reinterpret_cast<const uint32_t*>(H + (mqv[nb] * TAP_ROW + TAP_CHI) * 2);
     ndel[nb] = TapHalf<PREC>::lo(c2) + TapHalf<PREC>::hi(c2);
-    if constexpr (tap_split(PREC)) ndel[nb] = tap_drop_ndel4(c2, *reinterpret_cast<const uint32_t*>(H + g_lo + (mqv[nb] * TAP_SLOTS + TAP_CHI) * 2));
+    if constexpr (tap_split(PREC)) ndel[nb] = tap_drop_ndel4(c2, *reinterpret_cast<const uint32_t*>(H + g_lo + (mqv[nb] * TAP_ROW + TAP_CHI) * 2));
   }
 #endif
   const int a_off = (kg < 2 ? L::OFF_TAPS : L::OFF_CELLS) + li * 32 + (kg & 1) * 16;     // + tile * 1024 + sub * 512
@@ -130,14 +150,27 @@ __global__ __launch_bounds__(512, tap_bwd_q_waves(PREC, NB)) void attn_tap_bwd_q
     const TapOp<NP> a1 = tap_ld<NP>(base + a_off + t * 1024 + 512, L::OFF_LO);
     const TapOp<NP> wt = tap_ld_tr<NP>(base + L::OFF_TAPS + t_off + t * 1024, 512, L::OFF_LO);
     const TapOp<NP> wct = tap_ld_tr<NP>(base + L::OFF_CELLS + t_off + t * 1024, 512, L::OFF_LO);
+#if BEVR_TAP_G2
+    // group 1's image: plainly (lanes 32..63 read what lanes 0..31 do, against zeros) and transposed
+    const TapOp<NP> c0 = tap_ld<NP>(base + L::OFF_TAPS1 + li * 32 + (kg & 1) * 16 + t * 1024, L::OFF_LO);
+    const TapOp<NP> c1 = tap_ld<NP>(base + L::OFF_TAPS1 + li * 32 + (kg & 1) * 16 + t * 1024 + 512, L::OFF_LO);
+    const TapOp<NP> wt1 = tap_ld_tr<NP>(base + L::OFF_TAPS1 + t_off + t * 1024, 512, L::OFF_LO);
+#endif
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
       if (NB > 1 && blk0 + nb >= nblk) continue;
       const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
+#if BEVR_TAP_G2
+      const f32x4 s0 = tap_mm<PREC, true>(a0, bop[nb], tap_mm<PREC, true>(c0, bop2[nb], z4));
+      const f32x4 s1 = tap_mm<PREC, true>(a1, bop[nb], tap_mm<PREC, true>(c1, bop2[nb], z4));
+      const f32x4 p0 = tap_mm<PREC>(a0, hop[nb], tap_mm<PREC>(c0, hop2[nb], z4));
+      const f32x4 p1 = tap_mm<PREC>(a1, hop[nb], tap_mm<PREC>(c1, hop2[nb], z4));
+#else
       const f32x4 s0 = tap_mm<PREC, true>(a0, bop[nb], z4);
       const f32x4 s1 = tap_mm<PREC, true>(a1, bop[nb], z4);
       const f32x4 p0 = tap_mm<PREC>(a0, hop[nb], z4);
       const f32x4 p1 = tap_mm<PREC>(a1, hop[nb], z4);
+#endif
       float ds[8];
 #if BEVR_DROP
 #pragma unroll
@@ -152,6 +185,9 @@ __global__ __launch_bounds__(512, tap_bwd_q_waves(PREC, NB)) void attn_tap_bwd_q
       const TapOp<NP> ds8 = tap_pack8<PREC>(ds);
       ytap[nb] = tap_mm<PREC>(wt, ds8, ytap[nb]);
       ycell[nb] = tap_mm<PREC>(wct, ds8, ycell[nb]);
+#if BEVR_TAP_G2
+      ytap1[nb] = tap_mm<PREC>(wt1, ds8, ytap1[nb]);
+#endif
     }
   };
 
@@ -188,7 +224,10 @@ __global__ __launch_bounds__(512, tap_bwd_q_waves(PREC, NB)) void attn_tap_bwd_q
 #pragma unroll
   for (int nb = 0; nb < NB; ++nb) {
     if (blk0 + nb >= nblk) continue;
-    *reinterpret_cast<f32x4*>(dG + mqv[nb] * TAP_SLOTS + 4 * kg) = ytap[nb];
+    *reinterpret_cast<f32x4*>(dG + mqv[nb] * TAP_ROW + 4 * kg) = ytap[nb];
+#if BEVR_TAP_G2
+    *reinterpret_cast<f32x4*>(dG + mqv[nb] * TAP_ROW + TAP_SLOTS + 4 * kg) = ytap1[nb];
+#endif
   }
 }
 
@@ -221,11 +260,11 @@ int run(const bevr_attn_desc* d, const void* G, const void* H, const void* tap_w
   int rc = bevr_check_desc(d);
   if (rc) return rc;
   if (!G || !H || !tap_ws || !table_pair || !dG || !dtable) return BEVR_E_NULL;
-  if (d->groups != 1) return BEVR_E_SHAPE;
+  if (d->groups != TAP_NG || (BEVR_TAP_G2 && (d->heads & 1))) return BEVR_E_SHAPE;
   if (!bevr_aligned16(G) || !bevr_aligned16(H) || !bevr_aligned16(tap_ws) || !bevr_aligned16(table_pair) || !bevr_aligned16(dG))
     return BEVR_E_ALIGN;
   hipStream_t st = (hipStream_t)stream;
-#if !BEVR_DROP && !BEVR_TAP_X3
+#if !BEVR_DROP && !BEVR_TAP_X3 && !BEVR_TAP_G2
   // the split mode's kernels are attn_tap_bwd_q_x3.hip's
   if (d->precision == BEVR_PREC_BF16X3) return bevr_tap_bwd_q_x3(*d, G, H, tap_ws, table_pair, dG, dtable, st);
 #endif
@@ -236,7 +275,13 @@ int run(const bevr_attn_desc* d, const void* G, const void* H, const void* tap_w
 
 }  // namespace
 
-#if BEVR_TAP_X3 && !BEVR_DROP
+#if BEVR_TAP_G2
+// two channel groups: this translation unit is attn_tap_bwd_q_g2.hip, an entry point of its own (16-bit modes, no keep mask)
+extern "C" int bevr_attn_tap_g2_bwd_q(const bevr_attn_desc* d, const void* G, const void* H, const void* tap_ws,
+                                      const float* table_pair, float* dG, float* dtable, void* stream) {
+  return run<BEVR_PREC_BF16, BEVR_PREC_F16>(d, G, H, tap_ws, table_pair, dG, dtable, stream);
+}
+#elif BEVR_TAP_X3 && !BEVR_DROP
 // the split-mode instantiations: this translation unit is attn_tap_bwd_q_x3.hip, entered from bevr_attn_tap_bwd_q
 int bevr_tap_bwd_q_x3(const bevr_attn_desc& d, const void* G, const void* H, const void* tap_ws, const float* table_pair,
                       float* dG, float* dtable, hipStream_t st) {

@@ -43,7 +43,8 @@ namespace {
 // (split mode: every operand twice -- 4 waves per SIMD, the fat NB = 4 instantiation 2; with the keep mask NB = 2 spills
 // ~100 bytes a lane at the 128 registers of 4 waves: 3)
 constexpr int tap_fwd_waves(int prec, int nb) {
-  return tap_split(prec) ? (nb == 4 ? 2 : BEVR_DROP && nb == 2 ? 3 : 4) : TAP_FWD_WAVES(nb);
+  // (two groups: one more B operand, A operand and accumulator per row block -- as the split mode)
+  return tap_split(prec) || BEVR_TAP_G2 ? (nb == 4 ? 2 : BEVR_DROP && nb == 2 ? 3 : 4) : TAP_FWD_WAVES(nb);
 }
 template <int PREC, int NB, bool EXACT>
 __global__ __launch_bounds__(512, tap_fwd_waves(PREC, NB)) void attn_tap_fwd_kernel(
@@ -79,9 +80,15 @@ __global__ __launch_bounds__(512, tap_fwd_waves(PREC, NB)) void attn_tap_fwd_ker
   const float jrx = (float)j * rx;
 
   if (wave == n_wave - 1) {
-    const TapRec* recs = reinterpret_cast<const TapRec*>(tap_ws) + (size_t)prob * d.Np;
-    const StepBox* box = reinterpret_cast<const StepBox*>(tap_ws + tap_ws_box_offset(d)) + (size_t)prob * (d.Np / 32);
+    const int krow = tap_key_row(d, prob, hd);
+    const TapRec* recs = reinterpret_cast<const TapRec*>(tap_ws) + (size_t)krow * d.Np;
+    const StepBox* box = reinterpret_cast<const StepBox*>(tap_ws + tap_ws_box_offset(d)) + (size_t)krow * (d.Np / 32);
+#if BEVR_TAP_G2
+    const TapPos1* pos1 = reinterpret_cast<const TapPos1*>(tap_ws + tap_ws_pos1_offset(d)) + (size_t)krow * d.Np;
+    tap_producer<PREC>(d, smem, ring, img_bytes, rows_img, recs, box, pos1, tbl, jrx, lane);
+#else
     tap_producer<PREC>(d, smem, ring, img_bytes, rows_img, recs, box, tbl, jrx, lane);
+#endif
     return;
   }
 
@@ -92,6 +99,10 @@ __global__ __launch_bounds__(512, tap_fwd_waves(PREC, NB)) void attn_tap_fwd_ker
   f32x4 r[NB];        // R[slot 4 kg + e][q]
   float sh[NB];       // EXACT: the running maximum relative to mref
   size_t mqv[NB];
+#if BEVR_TAP_G2
+  TapOp<NP> bop2[NB];  // group 1: lanes 0..31 G[q][16 + 8 kg ..], lanes 32..63 zero (the A operand there is finite)
+  f32x4 r1[NB];        // R[slot 16 + 4 kg + e][q]
+#endif
   const size_t g_lo = (size_t)n_ph * Mp * TAP_SLOTS * 2;     // G's lo plane
 #pragma unroll
   for (int nb = 0; nb < NB; ++nb) {
@@ -99,7 +110,12 @@ __global__ __launch_bounds__(512, tap_fwd_waves(PREC, NB)) void attn_tap_fwd_ker
     const size_t mq = (size_t)ph * Mp + (size_t)j * d.Sp + blk * QB + li;
     mqv[nb] = mq;
     bop[nb] = TapOp<NP>{};
-    if (kg < 2) bop[nb] = tap_ld<NP>(G + (mq * TAP_SLOTS + 8 * kg) * 2, g_lo);
+    if (kg < 2) bop[nb] = tap_ld<NP>(G + (mq * TAP_ROW + 8 * kg) * 2, g_lo);
+#if BEVR_TAP_G2
+    bop2[nb] = TapOp<NP>{};
+    if (kg < 2) bop2[nb] = tap_ld<NP>(G + (mq * TAP_ROW + TAP_SLOTS + 8 * kg) * 2, g_lo);
+    r1[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
+#endif
     r[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
     sh[nb] = -3.0e38f;
   }
@@ -116,6 +132,10 @@ __global__ __launch_bounds__(512, tap_fwd_waves(PREC, NB)) void attn_tap_fwd_ker
   const int a_off = (kg < 2 ? L::OFF_TAPS : L::OFF_CELLS) + li * 32 + (kg & 1) * 16;     // + tile * 1024 + sub * 512
   const int t_off = L::OFF_TAPS + (4 * kg + (li >> 2)) * 32 + (lane & 3) * 8;             // + tile * 1024, second block + 512
   const int i_off = li * 32 + (kg & 1) * 16;                                             // in a table image, + block * 512
+#if BEVR_TAP_G2
+  const int a1_off = L::OFF_TAPS1 + li * 32 + (kg & 1) * 16;                             // group 1's image, as a_off / t_off
+  const int t1_off = L::OFF_TAPS1 + (4 * kg + (li >> 2)) * 32 + (lane & 3) * 8;
+#endif
   // the B operand exists once per tile slot of an emission (their chunk origins may differ); lanes 0..31 of both hold G
   TapOp<NP> bop1[NB];
 #pragma unroll
@@ -124,11 +144,20 @@ __global__ __launch_bounds__(512, tap_fwd_waves(PREC, NB)) void attn_tap_fwd_ker
 
   // one 32-key tile against one row block: S^T (two 16-key sub-tiles) -> weights -> R += w^T P
   // (kh: the tile's key hash, dropout builds)
+#if BEVR_TAP_G2
+  // (c0, c1, wt1: group 1's A operands of the two sub-tiles and its w^T)
+  auto tile = [&](const TapOp<NP>& a0, const TapOp<NP>& a1, const TapOp<NP>& wt, const TapOp<NP>& b, int nb,
+                  [[maybe_unused]] uint32_t kh, const TapOp<NP>& c0, const TapOp<NP>& c1, const TapOp<NP>& wt1) {
+    const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
+    f32x4 s0 = tap_mm<PREC, true>(a0, b, tap_mm<PREC, true>(c0, bop2[nb], z4));
+    f32x4 s1 = tap_mm<PREC, true>(a1, b, tap_mm<PREC, true>(c1, bop2[nb], z4));
+#else
   auto tile = [&](const TapOp<NP>& a0, const TapOp<NP>& a1, const TapOp<NP>& wt, const TapOp<NP>& b, int nb,
                   [[maybe_unused]] uint32_t kh) {
     const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
     f32x4 s0 = tap_mm<PREC, true>(a0, b, z4);
     f32x4 s1 = tap_mm<PREC, true>(a1, b, z4);
+#endif
     if constexpr (EXACT) {
       float tm = fmaxf(fmaxf(fmaxf(s0[0], s0[1]), fmaxf(s0[2], s0[3])), fmaxf(fmaxf(s1[0], s1[1]), fmaxf(s1[2], s1[3])));
       tm = fmaxf(tm, __shfl_xor(tm, 16));
@@ -136,6 +165,9 @@ __global__ __launch_bounds__(512, tap_fwd_waves(PREC, NB)) void attn_tap_fwd_ker
       const float mn = fmaxf(sh[nb], tm);
       const float al2 = fast_exp2(sh[nb] - mn);
       r[nb] *= al2;
+#if BEVR_TAP_G2
+      r1[nb] *= al2;
+#endif
 #if BEVR_DROP
       ls[nb] *= al2;
 #endif
@@ -156,7 +188,13 @@ __global__ __launch_bounds__(512, tap_fwd_waves(PREC, NB)) void attn_tap_fwd_ker
       asm("" : "+v"(p[k]));
     }
 #endif
+#if BEVR_TAP_G2
+    const TapOp<NP> p8 = tap_pack8<PREC>(p);
+    r[nb] = tap_mm<PREC>(wt, p8, r[nb]);
+    r1[nb] = tap_mm<PREC>(wt1, p8, r1[nb]);
+#else
     r[nb] = tap_mm<PREC>(wt, tap_pack8<PREC>(p), r[nb]);
+#endif
   };
   // a chunk's table side out of ring image `al` (lanes 32..63)
   auto ring_load = [&](TapOp<NP> (&b)[NB], int al) {
@@ -187,6 +225,13 @@ __global__ __launch_bounds__(512, tap_fwd_waves(PREC, NB)) void attn_tap_fwd_ker
     for (int k = 0; k < 4; ++k) a[k] = tap_ld<NP>(base + a_off + 512 * k, L::OFF_LO);
 #pragma unroll
     for (int t = 0; t < 2; ++t) wt[t] = tap_ld_tr<NP>(base + t_off + 1024 * t, 512, L::OFF_LO);
+#if BEVR_TAP_G2
+    TapOp<NP> c[4], wt1[2];    // the same of group 1
+#pragma unroll
+    for (int k = 0; k < 4; ++k) c[k] = tap_ld<NP>(base + a1_off + 512 * k, L::OFF_LO);
+#pragma unroll
+    for (int t = 0; t < 2; ++t) wt1[t] = tap_ld_tr<NP>(base + t1_off + 1024 * t, 512, L::OFF_LO);
+#endif
 #if BEVR_DROP
     const uint32_t kh0 = tap_drop_key0(key0 + (uint32_t)__builtin_amdgcn_readfirstlane((int)ct[3]), kg);
     const uint32_t kh1 = kh0 + 32u * 0xC2B2AE3Du;
@@ -196,8 +241,13 @@ __global__ __launch_bounds__(512, tap_fwd_waves(PREC, NB)) void attn_tap_fwd_ker
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
       if (NB > 1 && blk0 + nb >= nblk) continue;
+#if BEVR_TAP_G2
+      tile(a[0], a[1], wt[0], bop[nb], nb, kh0, c[0], c[1], wt1[0]);
+      tile(a[2], a[3], wt[1], bop1[nb], nb, kh1, c[2], c[3], wt1[1]);
+#else
       tile(a[0], a[1], wt[0], bop[nb], nb, kh0);
       tile(a[2], a[3], wt[1], bop1[nb], nb, kh1);
+#endif
     }
   }
 
@@ -206,7 +256,10 @@ __global__ __launch_bounds__(512, tap_fwd_waves(PREC, NB)) void attn_tap_fwd_ker
 #pragma unroll
   for (int nb = 0; nb < NB; ++nb) {
     if (blk0 + nb >= nblk) continue;
-    *reinterpret_cast<f32x4*>(R + mqv[nb] * TAP_SLOTS + 4 * kg) = r[nb];
+    *reinterpret_cast<f32x4*>(R + mqv[nb] * TAP_ROW + 4 * kg) = r[nb];
+#if BEVR_TAP_G2
+    *reinterpret_cast<f32x4*>(R + mqv[nb] * TAP_ROW + TAP_SLOTS + 4 * kg) = r1[nb];
+#endif
     const int row = (blk0 + nb) * QB + li;
 #if BEVR_DROP
     float lall = ls[nb];     // one cross-lane reduction: the four lane groups hold four keys of every 16 each
@@ -264,10 +317,10 @@ int run(const bevr_attn_desc* d, const void* G, const void* tap_ws, const float*
   int rc = bevr_check_desc(d);
   if (rc) return rc;
   if (!G || !tap_ws || !table_pair || !mref || !R || !flags) return BEVR_E_NULL;
-  if (d->groups != 1) return BEVR_E_SHAPE;
+  if (d->groups != TAP_NG || (BEVR_TAP_G2 && (d->heads & 1))) return BEVR_E_SHAPE;
   if (!bevr_aligned16(G) || !bevr_aligned16(tap_ws) || !bevr_aligned16(table_pair) || !bevr_aligned16(R)) return BEVR_E_ALIGN;
   hipStream_t st = (hipStream_t)stream;
-#if !BEVR_DROP && !BEVR_TAP_X3
+#if !BEVR_DROP && !BEVR_TAP_X3 && !BEVR_TAP_G2
   // the split mode's kernels are attn_tap_fwd_x3.hip's
   if (d->precision == BEVR_PREC_BF16X3) return bevr_tap_fwd_x3(*d, G, tap_ws, table_pair, mref, R, flags, st);
 #endif
@@ -278,7 +331,13 @@ int run(const bevr_attn_desc* d, const void* G, const void* tap_ws, const float*
 
 }  // namespace
 
-#if BEVR_TAP_X3 && !BEVR_DROP
+#if BEVR_TAP_G2
+// two channel groups: this translation unit is attn_tap_fwd_g2.hip, an entry point of its own (16-bit modes, no keep mask)
+extern "C" int bevr_attn_tap_g2_fwd(const bevr_attn_desc* d, const void* G, const void* tap_ws, const float* table_pair,
+                                    float* mref, float* R, int* flags, void* stream) {
+  return run<BEVR_PREC_BF16, BEVR_PREC_F16>(d, G, tap_ws, table_pair, mref, R, flags, stream);
+}
+#elif BEVR_TAP_X3 && !BEVR_DROP
 // the split-mode instantiations: this translation unit is attn_tap_fwd_x3.hip, entered from bevr_attn_tap_fwd
 int bevr_tap_fwd_x3(const bevr_attn_desc& d, const void* G, const void* tap_ws, const float* table_pair, float* mref,
                     float* R, int* flags, hipStream_t st) {

@@ -147,6 +147,9 @@ class SCADeformableAttention(nn.Module):
         promise a caller's own reference_points / split stay on the cell kernels.  In the split-bf16 mode (no fused K | V
         source) the same segment runs on the split-mode tap kernels when BEVR_TAP_X3=1 (ops.tap_supported): only the
         scattered keys are sampled and projected then.
+        With n_groups == 2 the split is kept only for that route -- the two-group tap kernels behind BEVR_TAP_GROUPS=1
+        (16-bit modes, no attention dropout; ops.tap_supported): the pinned keys are ordered per (problem, group) inside
+        ops.attention_core, not here, and there is no sparse tail.  Otherwise, and with more groups, the split is not used.
         Attention dropout (training mode, attn_drop_rate > 0): the keep mask lives in the region kernels and in the tap
         kernels.  A split that runs on the tap kernels is kept (scattered keys: region dropout kernels, pinned keys: tap
         dropout kernels, one mask); any other split is dropped and every key runs on the region kernels.  The split-bf16
@@ -166,9 +169,12 @@ class SCADeformableAttention(nn.Module):
         drop = attention_dropout(self)      # (p, seed) in training mode with attn_drop_rate > 0, else None
         Wt = self.rpe_table.shape[-1]
         pinned = split_is_pinned and self._pinned_keys_tap(S, Hi, Wi)
-        if not (cell_split is not None and cell_split < N and g == 1):
-            # groups > 1: a key is one row of K built from all groups' samples, so the groups cannot be ordered
-            # independently; the split is simply not used then
+        # groups > 1: a key is one row of K built from all groups' samples, so on the cell kernels the groups cannot be
+        # ordered independently and the split is simply not used.  The tap form has no K rows: with two groups and the
+        # two-group tap kernels available (BEVR_TAP_GROUPS, ops.tap_supported; `pinned` implies it without a mask) the
+        # split is kept, and the tap path orders the pinned segment per (problem, group) itself
+        group_tap = g == 2 and pinned and ops.tap_supported(self.precision, g, dropout=drop is not None)
+        if not (cell_split is not None and cell_split < N and (g == 1 or group_tap)):
             cell_split = None
         # the K | V source, each condition once: the fused source where the kernel covers the call; the tap segment beside
         # projected rows in the split-bf16 mode (no fused source there; with a keep mask only when the split-mode tap
@@ -187,8 +193,10 @@ class SCADeformableAttention(nn.Module):
             route = ops.attention_route(self.precision, g, S, Wt, N, cell_split, "pinned" if pinned and source != "kv" else False,
                                         drop is not None, source, C, self.n_heads)
             tap_source = "pinned" if route.tap else False
-            cell_split = cell_split if route.split < N else None
-        if cell_split is not None:
+            cell_split = cell_split if route.split < N and (g == 1 or route.tap) else None
+        if cell_split is not None and g == 1:
+            # (two groups: no per-call sort here and no sparse tail -- a tail needs one order shared by all heads; the
+            # scattered keys [0, cell_split) go through the fused K | V source with groups as without a split)
             n_tail = min(CELL_TAIL, max(0, N - cell_split - 1024))
             with torch.no_grad():
                 a, b = ops.key_coords(pos[:, cell_split:], S, Wt, N - cell_split)

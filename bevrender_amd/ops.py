@@ -551,6 +551,7 @@ class K:
     TAP_BWD_K, TAP_BWD_K_DROP = "bevr_attn_tap_bwd_k", "bevr_attn_tap_bwd_k_dropout"
     TAP_FWD_X3_DROP, TAP_BWD_Q_X3_DROP = "bevr_attn_tap_fwd_x3_dropout", "bevr_attn_tap_bwd_q_x3_dropout"
     TAP_BWD_K_X3_DROP = "bevr_attn_tap_bwd_k_x3_dropout"
+    TAP_G2_FWD, TAP_G2_BWD_Q, TAP_G2_BWD_K = "bevr_attn_tap_g2_fwd", "bevr_attn_tap_g2_bwd_q", "bevr_attn_tap_g2_bwd_k"
 
 
 @dataclass(frozen=True)
@@ -598,6 +599,9 @@ def attention_route(precision: int, groups: int, S: int, Wt: int, N: int, cell_s
     Reads the A/B switches itself (BEVR_KNORM, BEVR_MERGE_TAP, BEVR_SCATTER_DROP) or through gather_supported,
     slab_supported, slab_rows_supported, tap_supported, kv_source_supported and kv_wsplit (BEVR_KV_WSPLIT: `wsplit`, the
     one field it changes, and only for source == "kv_source").
+    BEVR_TAP_GROUPS (default TAP_GROUPS_DEFAULT: off; tap_supported; tests/test_tap_groups_routes_cpu.py): with groups == 2,
+    a 16-bit mode and no keep mask, a pinned segment is a tap segment on the two-group entry points (K.TAP_G2_*), merged
+    by "merge_views"; unset or 0, or any other call: the route as before.
     BEVR_SCATTER_DROP (default SCATTER_DROP_DEFAULT: off; tests/test_scatter_dropout_routes_cpu.py): with a keep mask, in
     the 16-bit modes, the region segment's forward is the gather kernel with the mask (K.GATHER_DROP) where
     gather_supported holds and its bwd_q the slab kernel with the mask (K.SLAB_BWD_Q_DROP) where slab_supported holds;
@@ -634,6 +638,8 @@ def attention_route(precision: int, groups: int, S: int, Wt: int, N: int, cell_s
             tap_source, split = None, N
     tap = bool(tap_source) and split < N
     if tap and (source == "kv" or not tap_supported(precision, groups, dropout=dropout) or 16 * ((S + 15) // 16) > 448):
+        # (the text is pinned, character by character, by tests/test_attention_routes_cpu.py; "groups == 1" reads: one
+        # channel group, or two where tap_supported accepts them -- BEVR_TAP_GROUPS, a 16-bit mode, no keep mask)
         raise ValueError("tap_source needs kv_source or tap_pix, groups == 1, a precision tap_supported accepts and S <= 448")
     if source == "tap_pix" and not tap:
         raise ValueError("tap_pix needs a tap segment: 0 <= cell_split < N")
@@ -680,14 +686,16 @@ def attention_route(precision: int, groups: int, S: int, Wt: int, N: int, cell_s
         segs.append(KeySegment("tap", split, N, K.TAP_FWD_X3_DROP, K.TAP_BWD_Q_X3_DROP, K.TAP_BWD_K_X3_DROP))
     elif tap and dropout:
         segs.append(KeySegment("tap", split, N, K.TAP_FWD_DROP, K.TAP_BWD_Q_DROP, K.TAP_BWD_K_DROP))
+    elif tap and groups == 2:     # tap_supported: BEVR_TAP_GROUPS, a 16-bit mode, no keep mask (csrc/attn_tap_*_g2.hip)
+        segs.append(KeySegment("tap", split, N, K.TAP_G2_FWD, K.TAP_G2_BWD_Q, K.TAP_G2_BWD_K))
     elif tap:
         segs.append(KeySegment("tap", split, N, K.TAP_FWD, K.TAP_BWD_Q, K.TAP_BWD_K))
     elif n_region < N:
         segs.append(KeySegment("cell", n_region, N, K.CELL_FWD, K.CELL_BWD_Q, K.CELL_BWD_K))
     # the static softmax reference of the gather forward needs the largest K row norm: out of the projection kernel
     kn2 = source == "kv_source" and gather is not None and os.environ.get("BEVR_KNORM", "1") != "0"
-    # (the fused merge_tap assumes a kept mass of 1: no mask)
-    fused_merge = (tap and split > 0 and not dropout and (C // heads) % 4 == 0
+    # (the fused merge_tap assumes a kept mass of 1: no mask; and forms O = Rn Vpix for 12 taps: one channel group)
+    fused_merge = (tap and split > 0 and not dropout and groups == 1 and (C // heads) % 4 == 0
                    and os.environ.get("BEVR_MERGE_TAP", "1") != "0")
     # split (hi + lo) projection weights for the fused source: off unless BEVR_KV_WSPLIT asks for them
     wsplit = source == "kv_source" and kv_wsplit()
@@ -983,7 +991,8 @@ _RUN = {K.FWD: _fwd_tile, K.FWD_DROP: _fwd_tile, K.GATHER: _fwd_gather, K.GATHER
         K.BWD_K: _bwd_k_tile, K.BWD_K_DROP: _bwd_k_tile, K.CELL_BWD_K: _bwd_k_cell,
         K.TAP_FWD: _tap_fwd, K.TAP_FWD_DROP: _tap_fwd, K.TAP_BWD_Q: _tap_bwd_q, K.TAP_BWD_Q_DROP: _tap_bwd_q,
         K.TAP_BWD_K: _tap_bwd_k, K.TAP_BWD_K_DROP: _tap_bwd_k,
-        K.TAP_FWD_X3_DROP: _tap_fwd, K.TAP_BWD_Q_X3_DROP: _tap_bwd_q, K.TAP_BWD_K_X3_DROP: _tap_bwd_k}
+        K.TAP_FWD_X3_DROP: _tap_fwd, K.TAP_BWD_Q_X3_DROP: _tap_bwd_q, K.TAP_BWD_K_X3_DROP: _tap_bwd_k,
+        K.TAP_G2_FWD: _tap_fwd, K.TAP_G2_BWD_Q: _tap_bwd_q, K.TAP_G2_BWD_K: _tap_bwd_k}
 
 
 def _run(name, o):
@@ -1243,6 +1252,10 @@ def attention_core(query: torch.Tensor, kproj: Optional[torch.Tensor], vproj: Op
     pixels of `feat` (the caller's contract: the projector-pinned keys, tap_supported) and go through the TAP kernels
     (csrc/attn_tap.h): their K and V are never formed -- the logits come from G = Q Kpix^T (12 pixels), the output from
     O = Rn Vpix, both thin GEMMs here -- and the segment is merged with the region kernels' through (O, LSE).
+    With groups == 2 (BEVR_TAP_GROUPS=1, a 16-bit mode, no dropout: tap_supported) the tap segment runs on the two-group tap
+    kernels (csrc/attn_tap_*_g2.hip, _TapAttnG2): pos (B*views*2, N, 2) holds every group's own position of every key, the
+    segment [cell_split, N) needs NO order -- each (problem, group) is cell-sorted here by its own table coordinates
+    (tap_group_order) -- and G, O are formed per group from the 12 pixels' channel-group rows (tap_group_pixels).
     tap_pix = (feat, Wkv, bkv) (with tap_source and cell_split, WITHOUT kv_source): the tap segment beside projected rows --
     the route of the split-bf16 mode (BEVR_PREC_BF16X3), which has no fused K | V source.  `kv` (or kproj / vproj) then
     holds the projected rows of the scattered keys [0, cell_split) ONLY, (B*views, cell_split, 2C); `pos` still holds all N
@@ -1331,6 +1344,12 @@ def attention_core(query: torch.Tensor, kproj: Optional[torch.Tensor], vproj: Op
     # ---- keys [0, n): region kernels; keys [n, N): tap kernels; one softmax, merged through (O, LSE) ----
     V = views
     Hi, Wi = feat.shape[1], feat.shape[2]
+    if groups == 2:
+        O_c, LSE_c = _tap_groups_segment(Qp, feat, Wkv, bkv, pos[:, n:], a[:, n:], b[:, n:], Tt, dc_replace(geom, N=N - n),
+                                         route.segments[-1], B, V)
+        if O_r is None:
+            return _unpacked(O_c, S, c, views, concat_views)
+        return _unpacked(O_r, S, c, views, concat_views, LSE_r, O_c, LSE_c)
     # the 12 pixels' K | V rows, without the bias: (B', 12, 2C); rows the image does not have are zero (zero padding)
     fpix = feat[:, :TAP_R, :TAP_C, :].float()
     fpix = F.pad(fpix, (0, 0, 0, TAP_C - fpix.shape[2], 0, TAP_R - fpix.shape[1])).reshape(Bp, TAP_N, Cc)
@@ -1359,6 +1378,58 @@ def attention_core(query: torch.Tensor, kproj: Optional[torch.Tensor], vproj: Op
     return _unpacked(O_r, S, c, views, concat_views, LSE_r, O_c, LSE_c)
 
 
+def tap_group_pixels(feat, Wkv, groups: int):
+    """The K | V rows of the top-left 4 x 3 pixels per channel group, without the bias: feat (B', Hi, Wi, C) channels-last,
+    Wkv (2C, C) -> (B', groups * 12, 2C), row g * 12 + t = Wkv[:, channels of g] f_t[channels of g] (rows the image does not
+    have are zero: zero padding).  Their sum over g is the one-group row.  Plain torch: runs on any device."""
+    Bp, Cc = feat.shape[0], feat.shape[-1]
+    cg = Cc // groups
+    fpix = feat[:, :TAP_R, :TAP_C, :].to(Wkv.dtype if Wkv.dtype == torch.float64 else torch.float32)
+    fpix = F.pad(fpix, (0, 0, 0, TAP_C - fpix.shape[2], 0, TAP_R - fpix.shape[1])).reshape(Bp, TAP_N, groups, cg)
+    Wg = Wkv.to(fpix.dtype).reshape(-1, groups, cg)
+    return torch.einsum("btgc,ogc->bgto", fpix, Wg).reshape(Bp, groups * TAP_N, -1)
+
+
+def tap_group_order(a, b, ys, xs, groups: int = 2):
+    """The key orders of a pinned segment with channel groups (include/bevrender_hip.h, "TAP entry points for TWO CHANNEL
+    GROUPS"): a, b, ys, xs (P * groups, N), row p * groups + g = group g's table coordinates / sampling position of the
+    keys of problem p in ONE shared order.  Every row gets a cell-sorted order of its own (cell_order of its a, b).
+    Returns (order (P * groups, N) long, a_o, b_o (P * groups, N), ys_o, xs_o (P * groups, groups, N)): row r's arrays
+    in row r's order, plane g' of ys_o / xs_o = group g''s position of the SAME keys.  Differentiable through the
+    gathers; plain torch: runs on any device."""
+    R, N = a.shape
+    with torch.no_grad():
+        order = cell_order(a, b)
+    a_o, b_o = a.gather(1, order), b.gather(1, order)
+    idx = order[:, None, :].expand(R, groups, N)
+
+    def planes(t):      # row p * groups + g -> the `groups` rows of its problem
+        return t.reshape(R // groups, 1, groups, N).expand(-1, groups, -1, -1).reshape(R, groups, N).gather(2, idx)
+    return order, a_o, b_o, planes(ys), planes(xs)
+
+
+def _tap_groups_segment(Qp, feat, Wkv, bkv, pos, a, b, Tt, geom, seg, B, V):
+    """attention_core's tap segment with two channel groups: pos (B' * 2, n, 2), a, b (B' * 2, n) of the pinned keys ->
+    (O_c packed (B', h, Mp, 32), LSE_c).  G and O per group by thin GEMMs under autograd, the softmax over the tap weights
+    by _TapAttnG2 on per-(problem, group) cell orders."""
+    Bp, heads, Cc = geom.n_prob, geom.heads, feat.shape[-1]
+    c = Cc // heads
+    pad_c = HEAD_DIM - c
+    T = 2 * TAP_N
+    kvp = tap_group_pixels(feat, Wkv.float(), 2)                                                          # (B', 24, 2C)
+    Kp = F.pad(kvp[..., :Cc].reshape(B, V, T, heads, c), (0, pad_c)).permute(0, 3, 4, 1, 2).reshape(B, heads, HEAD_DIM, V * T)
+    G = torch.matmul(Qp, Kp).reshape(B, heads, geom.Mp, V, T).permute(0, 3, 1, 2, 4).reshape(Bp, heads, geom.Mp, T)
+    Gb = torch.matmul(Qp[..., :c], bkv[:Cc].float().reshape(heads, c, 1)).squeeze(-1)                     # (B, h, Mp)
+    key_y = (pos[..., 0].float() + 1.0) * (0.5 * (feat.shape[1] - 1))
+    key_x = (pos[..., 1].float() + 1.0) * (0.5 * (feat.shape[2] - 1))
+    _, a_o, b_o, y_o, x_o = tap_group_order(a, b, key_y, key_x, 2)
+    Rn, LSE_c = _TapAttnG2.apply(G, a_o, b_o, y_o, x_o, Tt, geom, seg)
+    LSE_c = (LSE_c.reshape(B, V, heads, geom.Mp) + Gb[:, None]).reshape(Bp, heads, geom.Mp)
+    Vp = F.pad(kvp[..., Cc:].reshape(Bp, T, heads, c), (0, pad_c)).permute(0, 2, 1, 3)                    # (B', h, 24, 32)
+    bv = F.pad(bkv[Cc:].float().reshape(1, heads, 1, c), (0, pad_c))
+    return torch.matmul(Rn, Vp) + bv, LSE_c
+
+
 def _unpacked(O, S, c, views, concat_views, L_r=None, O_c=None, L_c=None):
     """attention_core's return value out of the packed layout: (B, S*S, views*C) with concat_views, else (B', S*S, C)."""
     return merge_views(O, S, c, views if concat_views else 1, L_r, O_c, L_c)
@@ -1377,6 +1448,7 @@ TAP_HEADROOM_F16 = 8.0                            # fp16 operands: the weights 2
 
 TAP_X3_DEFAULT = "0"                              # BEVR_TAP_X3 when unset (tap_supported)
 TAP_X3_DROP_DEFAULT = "0"                         # BEVR_TAP_X3_DROP when unset (tap_supported(..., dropout=True))
+TAP_GROUPS_DEFAULT = "0"                          # BEVR_TAP_GROUPS when unset (tap_supported: two channel groups)
 
 
 def tap_headroom(precision: int) -> float:
@@ -1559,6 +1631,95 @@ class _TapAttn(torch.autograd.Function):
         return dGo, da, db, dy, dx, dT, None, None, None
 
 
+class _TapAttnG2(torch.autograd.Function):
+    """_TapAttn for two channel groups (csrc/attn_tap_*_g2.hip; 16-bit modes, no keep mask):
+        logits S[n][q] = sum_g' sum_t w_t^g'(n) G[q][g' * 12 + t] + bias^g[n][q]  ->  Rn[q][g' * 12 + t], LSE[q].
+    G (P, h, Mp, 24) float; key_a, key_b (P * 2, N), key_y, key_x (P * 2, 2, N): tap_group_order's arrays (row p * 2 + g in
+    its own key order).  The static reference takes the SUM over the groups of max(0, max_t G^g'): each group's tap
+    weights are convex up to zero padding.  fp16 cotangent scaling and delta from the rounded H as _TapAttn, over all 24
+    taps."""
+
+    @staticmethod
+    def forward(ctx, G, key_a, key_b, key_y, key_x, Tt, geom: AttnGeom, seg: KeySegment):
+        _require_gpu(G, key_a, key_b, key_y, key_x, Tt)
+        L = _lib.lib()
+        ed = _edtype(geom.precision)
+        dev = G.device
+        P, h, Mp = geom.n_prob, geom.heads, geom.Mp
+        d = geom.desc()
+        pad = geom.Np - geom.N
+        ka, kb, ky, kx = (F.pad(t.float(), (0, pad)).contiguous() for t in (key_a, key_b, key_y, key_x))
+        ws = torch.empty(L.bevr_attn_tap_g2_ws_bytes(C.byref(d)), device=dev, dtype=torch.uint8)
+        _launch("bevr_attn_tap_g2_prep", C.byref(d), _ptr(ka), _ptr(kb), _ptr(ky), _ptr(kx), _ptr(ws), _stream())
+        Ttc = Tt.contiguous()
+        pair = torch.stack((Ttc[..., :-1], Ttc[..., 1:]), dim=-1).contiguous()
+        tmax = Ttc.amax(-1).amax(-1).clamp_min(0.0)
+        G16, Gv = _tap_operand_g2(G, ed, _neg_big(ed))
+        ub = 1.01 * (Gv[..., 0, :].amax(-1).clamp_min(0.0) + Gv[..., 1, :].amax(-1).clamp_min(0.0) + tmax[None, :, None]) + 0.01
+        mref = (-_set_offset(G16, tap_headroom(geom.precision) - ub)).contiguous()
+        R = torch.zeros(P, h, Mp, 2 * TAP_SLOTS, device=dev, dtype=torch.float32)
+        flags = torch.zeros(P * h, geom.S, device=dev, dtype=torch.int32)
+        valid = (torch.arange(Mp, device=dev) % geom.Sp) < geom.S
+        _run(seg.fwd, SimpleNamespace(g=geom, desc=d, G16=G16, ws=ws, pair=pair, mref=mref, R=R, flags=flags, lsum=(), drop=()))
+        l = torch.where(valid, R[..., 15], torch.ones_like(mref))
+        LSE = torch.where(valid, mref + torch.log2(l), torch.zeros_like(mref))
+        Rt = torch.cat((R[..., :TAP_N], R[..., TAP_SLOTS:TAP_SLOTS + TAP_N]), -1)
+        Rn = torch.where(valid[:, None], Rt / l[..., None], torch.zeros_like(Rt))
+        ctx.geom, ctx.seg = geom, seg
+        ctx.save_for_backward(G16, Rn, LSE, ws, pair, Ttc)
+        ctx.set_materialize_grads(False)
+        return Rn, LSE
+
+    @staticmethod
+    def backward(ctx, dRn, dLSE):
+        geom: AttnGeom = ctx.geom
+        G16, Rn, LSE, ws, pair, Ttc = ctx.saved_tensors
+        ed = G16.dtype
+        dev = G16.device
+        P, h, Mp = geom.n_prob, geom.heads, geom.Mp
+        valid = (torch.arange(Mp, device=dev) % geom.Sp) < geom.S
+        sdo = None
+        if ed == torch.float16:      # _TapAttn.backward: the cotangents brought to ~2^8 with a power of two
+            big = torch.zeros((), device=dev)
+            for t in (dRn, dLSE):
+                if t is not None:
+                    big = torch.maximum(big, t.abs().max())
+            sdo = torch.exp2(torch.floor(8.0 - torch.log2(big.clamp_min(1e-30))))
+            dRn, dLSE = (None if t is None else t * sdo for t in (dRn, dLSE))
+        H16, Hv = _tap_operand_g2(torch.zeros_like(Rn) if dRn is None else dRn * LN2, ed)
+        delta = (Rn * Hv.reshape(Rn.shape)).sum(-1)
+        if dLSE is not None:
+            delta = delta - dLSE
+        _set_offset(H16, -delta)
+        Gq = G16.clone()
+        _set_offset(Gq, torch.where(valid, -LSE, torch.full_like(LSE, _neg_big(ed))))
+        dG = torch.zeros(P, h, Mp, 2 * TAP_SLOTS, device=dev, dtype=torch.float32)
+        dT = torch.zeros_like(Ttc)
+        dk = [torch.zeros(2 * P, geom.Np, device=dev, dtype=torch.float32) for _ in range(2)]
+        dk += [torch.zeros(2 * P, 2, geom.Np, device=dev, dtype=torch.float32) for _ in range(2)]
+        o = SimpleNamespace(g=geom, desc=geom.desc(), Gq=Gq, H16=H16, ws=ws, pair=pair, Ttc=Ttc, dG=dG, dT=dT, dk=dk, drop=())
+        _run(ctx.seg.bwd_q, o)
+        _run(ctx.seg.bwd_k, o)
+        da, db, dy, dx = (t[..., :geom.N] for t in dk)
+        dGo = torch.cat((dG[..., :TAP_N], dG[..., TAP_SLOTS:TAP_SLOTS + TAP_N]), -1) * valid[:, None]
+        if sdo is not None:
+            inv = 1.0 / sdo
+            dGo, da, db, dy, dx, dT = dGo * inv, da * inv, db * inv, dy * inv, dx * inv, dT * inv
+        return dGo, da, db, dy, dx, dT, None, None
+
+
+def _tap_operand_g2(rows: torch.Tensor, ed, dead: float = 0.0):
+    """The 32-slot G / H operand of the two-group tap entry points from rows (..., 24) float (group g' in [12 g', 12 g' + 12)):
+    block 0 = _tap_operand of group 0's rows (slots 12, 13 the row offset: _set_offset; 14 = dead), block 1 = group 1's
+    rows in its slots 0..11, zeros behind.  Returns (operand (..., 32) of dtype ed, the rounded rows (..., 2, 12) float)."""
+    rows = rows.float()
+    op = torch.zeros(tuple(rows.shape[:-1]) + (2 * TAP_SLOTS,), device=rows.device, dtype=ed)
+    op[..., :TAP_N] = rows[..., :TAP_N]
+    op[..., TAP_SLOTS:TAP_SLOTS + TAP_N] = rows[..., TAP_N:]
+    op[..., 14] = dead
+    return op, torch.stack((op[..., :TAP_N].float(), op[..., TAP_SLOTS:TAP_SLOTS + TAP_N].float()), -2)
+
+
 def tap_supported(precision: int, groups: int, dropout: bool = False) -> bool:
     """The 16-bit operand modes (fp16 since round 5: headroom 8 and a power-of-two scale on the cotangents, see
     _TapAttn); BEVR_TAP=0 keeps the pinned keys on the cell kernels.  The split-bf16 mode (BEVR_PREC_BF16X3:
@@ -1567,8 +1728,16 @@ def tap_supported(precision: int, groups: int, dropout: bool = False) -> bool:
     MEASURED faster on the new route (tools/ab_sca_x3.py).  With attention dropout (`dropout`: the
     call has a keep mask) the split mode needs a second switch on top of that one, BEVR_TAP_X3_DROP set and not "0"
     (csrc/attn_tap_*_x3_drop.hip; default TAP_X3_DROP_DEFAULT: off); without it a call with a mask keeps every key on the
-    region dropout kernels, as before the split mode's tap kernels had a mask."""
-    if groups != 1 or os.environ.get("BEVR_TAP", "1") == "0":
+    region dropout kernels, as before the split mode's tap kernels had a mask.
+    Two channel groups (csrc/attn_tap_*_g2.hip, _TapAttnG2): the 16-bit modes without a keep mask when BEVR_TAP_GROUPS is
+    set and not "0" (default TAP_GROUPS_DEFAULT: off until the SCA block's A/B timing is on record); otherwise, and for
+    more groups, every key stays on the gather / slab / region kernels."""
+    if os.environ.get("BEVR_TAP", "1") == "0":
+        return False
+    if groups == 2:
+        return (not dropout and precision in (_lib.PREC_BF16, _lib.PREC_F16)
+                and os.environ.get("BEVR_TAP_GROUPS", TAP_GROUPS_DEFAULT) != "0")
+    if groups != 1:
         return False
     if precision == _lib.PREC_BF16X3:
         if os.environ.get("BEVR_TAP_X3", TAP_X3_DEFAULT) == "0":

@@ -70,6 +70,8 @@ extern "C" {
  *    bevr_attn_tap_fwd_x3_dropout, bevr_attn_tap_bwd_q_x3_dropout, bevr_attn_tap_bwd_k_x3_dropout (attention dropout on
  *    the tap entry points in BEVR_PREC_BF16X3; the three _dropout entry points keep returning BEVR_E_PRECISION for that
  *    mode);
+ *    bevr_attn_tap_g2_ws_bytes / _tap_g2_prep / _tap_g2_fwd / _tap_g2_bwd_q / _tap_g2_bwd_k (the tap entry points for two
+ *    channel groups, 32-slot operands; the one-group tap entry points keep returning BEVR_E_SHAPE for groups != 1);
  *    bevr_attn_gather_fwd_dropout (the gather forward with the keep mask, over a row range) and
  *    bevr_attn_slab_drop_ws_bytes / _slab_drop_prep / bevr_attn_slab_bwd_q_dropout (the slab query-side backward with
  *    the keep mask, S <= 211), both in the 16-bit modes; every other gather and slab entry point keeps its contract;
@@ -376,6 +378,52 @@ size_t bevr_attn_tap_bwd_k_ws_bytes(const bevr_attn_desc* d);
 int bevr_attn_tap_bwd_k_ws(const bevr_attn_desc* d, const void* G, const void* H, const void* tap_ws,
                            const float* table, float* dkey_a, float* dkey_b, float* dkey_y, float* dkey_x,
                            void* ws, int max_workgroups, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * TAP entry points for TWO CHANNEL GROUPS (csrc/attn_tap_*_g2.hip; descriptor groups == 2 and an even number of heads,
+ * else BEVR_E_SHAPE; BEVR_PREC_BF16 or BEVR_PREC_F16, else BEVR_E_PRECISION; no keep mask).  Added without a new ABI
+ * version: nothing a version-6 caller uses changed, and the entry points above keep returning BEVR_E_SHAPE for
+ * groups != 1.  With n_groups = 2 (model/SCA_deform_attn.py:290-321) group g' samples its C / 2 channels at its OWN
+ * position, proj_k / proj_v mix all channels, and the bias of a head uses the positions of the head's group
+ * g = head / (heads / 2).  For a pinned key n and a head of group g
+ *   logits  S[n][q] = sum_g' sum_t w_t^g'(n) G^g'[t][q] + Gb[q] + bias^g[n][q],   G^g'[t][q] = Q_q . Kpix_t^g',
+ *                     Kpix_t^g' = Wk[:, channels of g'] f_t[channels of g']   (the 12 pixels' rows, per channel group)
+ *   output  O_q     = sum_g' sum_t Rn^g'[t][q] Vpix_t^g' + bv,    R^g'[t][q] = sum_n w_t^g'(n) P[n][q],  Rn = R / R[15]
+ * A softmax does not care about the order of its keys, and a head needs (a, b) of its own group only: every
+ * (problem, group) ROW p * 2 + g has a key order of its own -- the caller's choice; cell-sorted by group g's table
+ * coordinates for speed, as above -- and holds, for the key at each index of THAT order, group g's table coordinates
+ * and the sampling positions of BOTH groups.  Head hd reads the records of row prob * 2 + hd / (heads / 2).
+ *   key_a, key_b [n_prob * 2][Np] float: row p * 2 + g = group g's table coordinates, in the row's own key order
+ *   key_y, key_x [n_prob * 2][2][Np] float: plane g' of row p * 2 + g = the sampling position in feature pixels of group
+ *       g' for the key at that index of row p * 2 + g's order (both inside the 4 x 3 pixels: the contract above, for
+ *       either group; the bounds-checking build traps a live key of either group outside them)
+ *   tap_ws: bevr_attn_tap_g2_ws_bytes(d) bytes (0: bad descriptor), written by bevr_attn_tap_g2_prep, opaque; records
+ *       and tile boxes per (problem, group) row
+ *   G   [n_prob][heads][Mp][32] E: slots 0..15 EXACTLY the one-group layout with group 0's taps (12, 13 the row offset,
+ *       14 the masked key's logit, 15 zero); slots 16..27 group 1's taps; slots 28..31 ZERO
+ *   mref, flags, table_pair, table, dtable: as for the one-group entry points.  The static reference needs the bound
+ *       sum_g' max(0, max_t G^g'[t][q]) + Gb + max(0, max table): a SUM over the groups (each group's tap weights are
+ *       convex up to zero padding), not a maximum.  Flagged columns are recomputed with an online maximum as above.
+ *   R   [n_prob][heads][Mp][32] float (written): rows 0..15 as above (row 15 the denominator), rows 16..27 group 1's
+ *       weight sums, rows 28..31 zero
+ *   H, dG [..][Mp][32] in the same layout: H slots 0..11 and 16..27 = ln2 * (dO_q . Vpix_t^g'), 12, 13 the parts of Hc,
+ *       the others zero; dG slots 0..11 and 16..27 the gradient of G, slot 15 the gradient of Gb
+ *   dkey_a, dkey_b [n_prob * 2][Np], dkey_y, dkey_x [n_prob * 2][2][Np] float, in the rows' key orders, ACCUMULATED over
+ *       the heads of the row's group (caller zeroes them): d/d key_a, key_b through the bias of those heads; plane g' of
+ *       d/d key_y, key_x through group g''s tap weights, both paths (logits and values) as bevr_attn_tap_bwd_k.  The
+ *       gradient of a key's position of group g' is the sum over BOTH rows' planes g' (after undoing the rows' orders).
+ *       (tile, column) pairs that do not fit a table chunk are taken by the main grid launched again: no work list.
+ * The second logit product is one more zero-padded depth-32 matrix product per 16 keys x 16 rows.
+ * ---------------------------------------------------------------------------------------------- */
+size_t bevr_attn_tap_g2_ws_bytes(const bevr_attn_desc* d);
+int bevr_attn_tap_g2_prep(const bevr_attn_desc* d, const float* key_a, const float* key_b, const float* key_y,
+                          const float* key_x, void* tap_ws, void* stream);
+int bevr_attn_tap_g2_fwd(const bevr_attn_desc* d, const void* G, const void* tap_ws, const float* table_pair,
+                         float* mref, float* R, int32_t* flags, void* stream);
+int bevr_attn_tap_g2_bwd_q(const bevr_attn_desc* d, const void* G, const void* H, const void* tap_ws,
+                           const float* table_pair, float* dG, float* dtable, void* stream);
+int bevr_attn_tap_g2_bwd_k(const bevr_attn_desc* d, const void* G, const void* H, const void* tap_ws,
+                           const float* table, float* dkey_a, float* dkey_b, float* dkey_y, float* dkey_x, void* stream);
 
 /* Attention dropout on the tap entry points: the three above with the keep mask of bevr_attn_*_dropout (same hash, same
  * drop_thr = round(p * 65536) < 65536, BEVR_E_SHAPE otherwise).  The pair (ph, mq, key n' of this segment) is hashed

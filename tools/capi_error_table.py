@@ -47,7 +47,20 @@ LATER = {
                         ("bevr_attn_gather_fwd_dropout", "bevr_attn_slab_drop_prep", "bevr_attn_slab_bwd_q_dropout")),
     "slab_x3_dropout": ("slab_x3_dropout_error_codes.json",
                         ("bevr_attn_slab_x3_drop_prep", "bevr_attn_slab_bwd_q_x3_dropout")),
+    "tap_groups": ("tap_groups_error_codes.json",
+                   ("bevr_attn_tap_g2_prep", "bevr_attn_tap_g2_fwd", "bevr_attn_tap_g2_bwd_q", "bevr_attn_tap_g2_bwd_k")),
 }
+# descriptor fields a group's entry points need on top of BASE to accept a call (the tap entry points for two channel
+# groups take groups == 2 only; their "groups" defect, heads=2,groups=2, is then no defect and is recorded as accepted)
+LATER_BASE = {"tap_groups": dict(groups=2)}
+
+
+def base_of(name):
+    """BASE as the entry point's group needs it"""
+    for group, (_, names) in LATER.items():
+        if name in names:
+            return dict(BASE, **LATER_BASE.get(group, {}))
+    return dict(BASE)
 
 
 def later_table(group):
@@ -74,7 +87,7 @@ class Call:
 
     def __init__(self, L, name, precision):
         self.fn, self.name = getattr(L, name), name
-        self.geom = dict(BASE, precision=precision)
+        self.geom = dict(base_of(name), precision=precision)
         self.fields, self.args, self.no_desc = {}, {}, False
         types = self.fn.argtypes
         self.pointers = [i for i, t in enumerate(types) if i and t is C.c_void_p][:-1]     # the last one is the stream
