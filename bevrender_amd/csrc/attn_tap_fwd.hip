@@ -18,6 +18,8 @@
 // that no weight can overflow); the loop carries no running maximum, no rescale and no row sum.  A row whose weights
 // all underflowed against that reference (bound looser than ~190 binades: exploding activations) is flagged per column
 // and recomputed by the EXACT instantiation (online maximum), which overwrites R and mref of the flagged columns.
+// fp16 flags a column sooner, as soon as a row's sum is under Np 2^-14 (the epilogue): under it the weights are fp16
+// subnormals whose rounding no longer averages out of the sum.
 #include "attn_tap.h"
 #include "attn_host.h"
 
@@ -252,6 +254,11 @@ __global__ __launch_bounds__(512, tap_fwd_waves(PREC, NB)) void attn_tap_fwd_ker
   }
 
   // ---- epilogue: R[q][4 kg .. 4 kg + 3]; flag the column if a row's mass is not a healthy number -----------------
+  // fp16: the weights 2^(S - mref) are rounded to fp16 before the R product -- under 2^-14 with an absolute error of up to
+  // 2^-25 (zero under 2^-25), so Np keys move a row's sum by up to Np 2^-25: a row whose sum is under Np 2^-14 (the
+  // error could exceed 2^-11 of it) flags its column as an underflowed row does.  The exact pass keeps its weights <= 1
+  // against the running maximum.  (bf16 and the split mode: 8 exponent bits, the float's own underflow is the limit)
+  const float l_min = PREC == BEVR_PREC_F16 ? (float)d.Np * 6.103515625e-05f : 7.9e-31f;
   bool bad = false;
 #pragma unroll
   for (int nb = 0; nb < NB; ++nb) {
@@ -275,7 +282,7 @@ __global__ __launch_bounds__(512, tap_fwd_waves(PREC, NB)) void attn_tap_fwd_ker
 #else
       const float l = r[nb][3];
 #endif
-      if (kg == 3 && row < d.S && !(l >= 7.9e-31f && l < 3.0e38f)) bad = true;
+      if (kg == 3 && row < d.S && !(l >= l_min && l < 3.0e38f)) bad = true;
     }
   }
   if constexpr (!EXACT) {

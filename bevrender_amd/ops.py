@@ -1441,9 +1441,10 @@ def _unpacked(O, S, c, views, concat_views, L_r=None, O_c=None, L_c=None):
 TAP_R, TAP_C, TAP_N, TAP_SLOTS = 4, 3, 12, 16     # csrc/attn_tap.h: feature rows 0..3 x columns 0..2, 16 operand slots
 TAP_HEADROOM = 64.0                               # binades between the static softmax reference and the logits' upper bound
 TAP_HEADROOM_F16 = 8.0                            # fp16 operands: the weights 2^(S - mref) are rounded to fp16 (largest value
-                                                  # 2^15.9; include/bevrender_hip.h: headroom <= 8).  Weights more than ~32
-                                                  # binades under the bound flush to zero; a row that loses ALL of them is
-                                                  # flagged and recomputed with an online maximum (the EXACT pass)
+                                                  # 2^15.9; include/bevrender_hip.h: headroom <= 8).  Weights more than ~22
+                                                  # binades under the bound are fp16 subnormals, ~33 under it zero; a row
+                                                  # whose SUM is under Np 2^-14 flags its column, which is recomputed with
+                                                  # an online maximum (the EXACT pass)
 
 
 TAP_X3_DEFAULT = "0"                              # BEVR_TAP_X3 when unset (tap_supported)

@@ -311,9 +311,15 @@ int bevr_attn_cell_bwd_k(const bevr_attn_desc* d, const void* Q, const void* Qt,
  *       product, so the headroom is bounded per precision: BEVR_PREC_BF16 <= 100 (8 exponent bits), BEVR_PREC_F16 <= 8
  *       (5 exponent bits: 2^15.9 is fp16's largest value; the row sum over up to 2^17 keys is taken in f32.  A larger fp16
  *       headroom gives inf / NaN in R -- the kernel cannot see the headroom, the limit is the caller's to keep;
- *       tools/tap_check.py runs fp16 at 8, bevrender_amd/ops.py keeps fp16 calls off these entry points).  Out: the reference R is relative to -- unchanged unless
- *       every weight of the row underflowed against the bound (looser than ~190 binades), in which case the column is
- *       recomputed with an online maximum and its rows' mref are replaced.
+ *       tools/tap_check.py and bevrender_amd/ops.py (TAP_HEADROOM_F16) run fp16 at 8).  Out: the reference R is relative
+ *       to -- unchanged unless every weight of the row underflowed against the bound (looser than ~190 binades), in which
+ *       case the column is recomputed with an online maximum and its rows' mref are replaced.
+ *       BEVR_PREC_F16 flags sooner: an fp16 weight under 2^-14 is stored with an absolute error of up to 2^-25 (zero under
+ *       2^-25), Np keys move a row's sum by up to Np 2^-25, so a column is recomputed as soon as one of its rows has a sum
+ *       R[15] under Np 2^-14 (the error could exceed 2^-11 of the sum; with headroom 8 and Np keys: a bound more than
+ *       ~22 - log2 Np binades above the row's log2-sum-exp).  The _dropout entry point applies this to the sum of ALL
+ *       weights (lsum), bevr_attn_tap_g2_fwd to its R[15].  The recompute keeps every weight <= 1 against the running
+ *       maximum.
  *   R   [n_prob][heads][Mp][16] float (written; rows 12, 13 equal row 15)   flags [n_prob*heads][S] int32, ZEROED by the
  *       caller (scratch)
  *

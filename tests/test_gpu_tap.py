@@ -218,3 +218,11 @@ def test_tap_path_with_a_loose_logit_bound_takes_the_exact_pass():
     for n, a, b in zip(["query", "pos", "table"], (query, pos, table), (cpu[0], cpu[4], cpu[5])):
         e = rel_err(a.grad.double().cpu(), b.grad)
         assert e < 3e-2, f"grad {n}: rel err {e:.3e}"
+
+
+def test_tap_path_with_a_loose_logit_bound_in_fp16_leaves_only_subnormal_weights():
+    """tools/tap_route_check.py, fp16_gap_case, with one channel group: the static bound 22 .. 33 binades above the
+    logits of at least half the rows (asserted there, on the float64 side), so that against mref every weight of such a
+    row is an fp16 subnormal -- and a row sum (~1e-5) far above the 7.9e-31 that flags an underflowed row"""
+    from tap_route_check import fp16_gap_case
+    fp16_gap_case(1, _tap_problem, _oracle_chain)

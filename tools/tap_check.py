@@ -84,9 +84,10 @@ def bias_ref(T2, a, b, S, Wt, j, mimic=None):
     return out
 
 
-def reference(G, Gb, a, b, ys, xs, T2, S, Wt, N, mimic=None):
+def reference(G, Gb, a, b, ys, xs, T2, S, Wt, N, mimic=None, with_max=False):
     """float64 definition: returns Rn (P, h, S(j), S(i), 16) normalised, LSE (P, h, S, S).
-    G (P, h, Mp, 16), Gb (P, h, Mp) as handed to the kernel (values), a, b, ys, xs (P, Np)."""
+    G (P, h, Mp, 16), Gb (P, h, Mp) as handed to the kernel (values), a, b, ys, xs (P, Np).
+    with_max: a third value, the rows' largest logit (P, h, S, S)."""
     P, h, Mp, _ = G.shape
     Sp = Mp // S
     Gd = G.double().reshape(P, h, S, Sp, 16)[:, :, :, :S]
@@ -97,6 +98,7 @@ def reference(G, Gb, a, b, ys, xs, T2, S, Wt, N, mimic=None):
         T2 = _mim(T2, mimic)
     Rn = torch.zeros(P, h, S, S, 16, dtype=torch.float64, device=G.device)
     LSE = torch.zeros(P, h, S, S, dtype=torch.float64, device=G.device)
+    MAX = torch.zeros(P, h, S, S, dtype=torch.float64, device=G.device)
     for p in range(P):
         for j in range(S):
             bia = bias_ref(T2, a[p, :N].double(), b[p, :N], S, Wt, j, mimic)                   # (h, S, N)
@@ -105,8 +107,9 @@ def reference(G, Gb, a, b, ys, xs, T2, S, Wt, N, mimic=None):
             pr = torch.exp2(lg - m)
             l = pr.sum(-1, keepdim=True)
             LSE[p, :, j] = (m + torch.log2(l))[..., 0]
+            MAX[p, :, j] = m[..., 0]
             Rn[p, :, j] = torch.einsum("hin,nt->hit", pr / l, w[p])
-    return Rn, LSE
+    return (Rn, LSE, MAX) if with_max else (Rn, LSE)
 
 
 def grad_reference(G, Gb, H, Hc, a, b, ys, xs, T2, S, Wt, N, LSE):
@@ -158,10 +161,24 @@ def draw_keys(P, S, N, Wt, spread, sort, gen):
     return a, b, ys, xs
 
 
+UNSEEN_TAP = 11      # pixel (3, 2): draw_keys' positions (ys < 1.6, xs < 0.45) give it weight 0 for every key
+
+
+def mixed_rows(big=200.0, small=4.0, every=3):
+    """A `row_scale` for make_case: `big` on the rows i % every == 0 of the odd BEV columns j, `small` elsewhere."""
+    def scale(geom):
+        m = torch.arange(geom.Mp, device=dev)
+        j, i = m // geom.Sp, m % geom.Sp
+        return torch.where((j % 2 == 1) & (i % every == 0), big, small).float()
+    return scale
+
+
 def make_case(P, h, S, N, Wt, spread=(5.0, 2.5), gscale=4.0, seed=0, prec=_lib.PREC_BF16, sort=True, n_dead_logit=False,
-              host_rng=False):
+              host_rng=False, row_scale=None, unseen=None):
     """host_rng: draw with a CPU generator (the same numbers on a machine without a GPU: draw_keys with
-    torch.Generator().manual_seed(seed) gives this case's keys there)."""
+    torch.Generator().manual_seed(seed) gives this case's keys there).
+    row_scale: geom -> (Mp,) the scale of G per query row, in place of gscale (mixed_rows).
+    unseen: the value of G's slot UNSEEN_TAP in every row -- a logit no key has, which only the static bound sees."""
     gd = "cpu" if host_rng else dev
     gen = torch.Generator(device=gd).manual_seed(seed)
     # (split mode: G stays float -- run_fwd / run_bwd_* split it as the header words it, header_split)
@@ -171,13 +188,28 @@ def make_case(P, h, S, N, Wt, spread=(5.0, 2.5), gscale=4.0, seed=0, prec=_lib.P
     pad = geom.Np - N
     a, b, ys, xs = (torch.nn.functional.pad(t, (0, pad)).contiguous() for t in (a, b, ys, xs))
     G = torch.zeros(P, h, geom.Mp, 16, device=dev)
-    G[..., :12] = torch.randn(P, h, geom.Mp, 12, device=gd, generator=gen).to(dev) * gscale
+    G[..., :12] = torch.randn(P, h, geom.Mp, 12, device=gd, generator=gen).to(dev) \
+        * (gscale if row_scale is None else row_scale(geom)[None, None, :, None])
+    if unseen is not None:
+        G[..., UNSEEN_TAP] = unseen
     valid = (torch.arange(geom.Mp, device=dev) % geom.Sp) < S
     G = G * valid[None, None, :, None]
     G[..., 14] = -1.0e30 if prec in (_lib.PREC_BF16, X3) else -60000.0
     Gb = torch.randn(P, h, geom.Mp, device=gd, generator=gen).to(dev) * valid
     T = torch.randn(h, 2 * S - 1, Wt, device=gd, generator=gen).to(dev) * 0.5
     return geom, a, b, ys, xs, G.to(ed), Gb.contiguous(), T
+
+
+def static_reference(geom, G, Gb, T, headroom):
+    """The forward's G operand (the row offset in slots 12, 13) and the static softmax reference mref it works against: an
+    upper bound of the row's logits minus the headroom.  (The forward's EXACT pass rewrites mref of the columns it flags.)"""
+    tmax = (T.float() * ops.LOG2E).amax((1, 2)).clamp_min(0)                                 # per head
+    U = G[..., :12].float().amax(-1).clamp_min(0) * 1.01 + Gb + tmax[None, :, None] * 1.01 + 0.01
+    if geom.precision == X3:
+        G, c_eff = header_split(G, Gb - (U - headroom), dead=-1.0e30)
+        return G, (Gb - c_eff).contiguous()
+    G = G.clone()
+    return G, (Gb - set_offset(G, Gb - (U - headroom))).contiguous()      # the reference the kernel works against
 
 
 def run_fwd(geom, a, b, ys, xs, G, Gb, T, headroom=64.0, timer=None):
@@ -188,14 +220,7 @@ def run_fwd(geom, a, b, ys, xs, G, Gb, T, headroom=64.0, timer=None):
     ws = torch.empty(L.bevr_attn_tap_ws_bytes(C.byref(d)), device=dev, dtype=torch.uint8)
     _lib.check(L.bevr_attn_tap_prep(C.byref(d), ops._ptr(a), ops._ptr(b), ops._ptr(ys), ops._ptr(xs), ops._ptr(ws),
                                     ops._stream()), "tap_prep")
-    tmax = (T.float() * ops.LOG2E).amax((1, 2)).clamp_min(0)                                 # per head
-    U = G[..., :12].float().amax(-1).clamp_min(0) * 1.01 + Gb + tmax[None, :, None] * 1.01 + 0.01
-    if geom.precision == X3:
-        G, c_eff = header_split(G, Gb - (U - headroom), dead=-1.0e30)
-        mref = (Gb - c_eff).contiguous()
-    else:
-        G = G.clone()
-        mref = (Gb - set_offset(G, Gb - (U - headroom))).contiguous()      # the reference the kernel works against
+    G, mref = static_reference(geom, G, Gb, T, headroom)
     R = torch.empty(geom.n_prob, geom.heads, geom.Mp, 16, device=dev, dtype=torch.float32)
     flags = torch.zeros(geom.n_prob * geom.heads, geom.S, device=dev, dtype=torch.int32)
     args = (C.byref(d), ops._ptr(G), ops._ptr(ws), ops._ptr(pair), ops._ptr(mref), ops._ptr(R),
@@ -271,12 +296,15 @@ def check_case(name, **kw):
     headroom = kw.pop("headroom", 64.0)
     from_header = kw.pop("from_header", False)
     h_cols = kw.pop("h_cols", None)       # BEV columns that carry the backward's cotangent (default: all)
+    forward_only = kw.pop("forward_only", False)   # the forward's figures alone (flags, per-row slack)
     geom, a, b, ys, xs, G, Gb, T = make_case(**kw)
     R, mref, flags, _, _ = run_fwd(geom, a, b, ys, xs, G, Gb, T, headroom)
     torch.cuda.synchronize()
     S, Sp = geom.S, geom.Sp
     Rg = R.double().reshape(geom.n_prob, geom.heads, S, Sp, 16)[:, :, :, :S]
     mr = mref.double().reshape(geom.n_prob, geom.heads, S, Sp)[:, :, :, :S]
+    # (mref as the kernel was GIVEN it: the exact pass has rewritten the flagged columns of `mref`)
+    mr0 = static_reference(geom, G, Gb, T, headroom)[1].double().reshape(geom.n_prob, geom.heads, S, Sp)[:, :, :, :S]
     l = Rg[..., 15]
     Rn_got = Rg / l[..., None]
     lse_got = mr + torch.log2(l)
@@ -286,9 +314,19 @@ def check_case(name, **kw):
     for tag, mm in (("exact", None), ("mimic", mim)):
         # (split mode: the kernels see G as hi + lo of the float, the mimic takes that pair)
         Gin = _mim(G.double(), mm).float() if mm == MIMIC_X3 else G.float()
-        Rn, LSE = reference(Gin, Gb, a, b, ys, xs, T2, S, geom.Wt, geom.N, mm)
+        Rn, LSE, MAX = reference(Gin, Gb, a, b, ys, xs, T2, S, geom.Wt, geom.N, mm, with_max=True)
         sel = [t for t in range(16) if t not in (12, 13)]
         out[tag] = ((Rn_got[..., sel] - Rn[..., sel]).abs().max().item(), (lse_got - LSE).abs().max().item())
+        # per row (P, h, j, i), from the reference alone: log2 of the row sum against the static reference the kernel was
+        # given, and the slack of the static bound = mref + headroom - the row's largest logit
+        out[tag + "_rows"] = dict(lsum_log2=(LSE - mr0).cpu(), slack=(mr0 + headroom - MAX).cpu(),
+                                  lse_err=(lse_got - LSE).abs().cpu())
+    out["flags"] = flags.reshape(geom.n_prob, geom.heads, S).cpu()
+    out["finite_G"] = bool(torch.isfinite(G.float()).all())
+    if forward_only:
+        out.update(flagged=int(flags.sum()), dead=Rn_got[..., 14].abs().max().item())
+        print(f"{name:28s} flagged {out['flagged']}  Rn err mimic {out['mimic'][0]:.2e}  LSE err mimic {out['mimic'][1]:.2e}")
+        return out
     print(f"{name:28s} flagged {int(flags.sum())}  Rn err exact {out['exact'][0]:.2e} mimic {out['mimic'][0]:.2e}   "
           f"LSE err exact {out['exact'][1]:.2e} mimic {out['mimic'][1]:.2e}  dead-slot max {Rn_got[..., 14].abs().max().item():.1e}")
     # ---- backward, query side: H, Hc random; LSE of the float64 reference

@@ -29,9 +29,10 @@ def tap_w32(ys, xs, dtype=torch.float64):
 TAPS = list(range(12)) + list(range(16, 28))        # the 24 tap slots of a 32-slot row
 
 
-def reference(G, Gb, a, b, ys, xs, T2, S, Wt, N, mimic=None):
+def reference(G, Gb, a, b, ys, xs, T2, S, Wt, N, mimic=None, with_max=False):
     """float64 definition.  G (P, h, Mp, 32), Gb (P, h, Mp) values; a, b (2P, Np), ys, xs (2P, 2, Np) the rows' arrays.
-    Returns Rn (P, h, S(j), S(i), 32) normalised, LSE (P, h, S, S).  Head hd reads row p * 2 + hd // (h / 2)."""
+    Returns Rn (P, h, S(j), S(i), 32) normalised, LSE (P, h, S, S).  Head hd reads row p * 2 + hd // (h / 2).
+    with_max: a third value, the rows' largest logit (P, h, S, S)."""
     P, h, Mp, _ = G.shape
     Sp = Mp // S
     hg = h // NG
@@ -43,6 +44,7 @@ def reference(G, Gb, a, b, ys, xs, T2, S, Wt, N, mimic=None):
         T2 = tc._mim(T2, mimic)
     Rn = torch.zeros(P, h, S, S, 32, dtype=torch.float64, device=G.device)
     LSE = torch.zeros(P, h, S, S, dtype=torch.float64, device=G.device)
+    MAX = torch.zeros(P, h, S, S, dtype=torch.float64, device=G.device)
     for p in range(P):
         for g in range(NG):
             r, hs = p * NG + g, slice(g * hg, (g + 1) * hg)
@@ -53,8 +55,9 @@ def reference(G, Gb, a, b, ys, xs, T2, S, Wt, N, mimic=None):
                 pr = torch.exp2(lg - m)
                 l = pr.sum(-1, keepdim=True)
                 LSE[p, hs, j] = (m + torch.log2(l))[..., 0]
+                MAX[p, hs, j] = m[..., 0]
                 Rn[p, hs, j] = torch.einsum("hin,nt->hit", pr / l, w[r])
-    return Rn, LSE
+    return (Rn, LSE, MAX) if with_max else (Rn, LSE)
 
 
 def grad_reference(G, Gb, H, Hc, a, b, ys, xs, T2, S, Wt, N, LSE):
@@ -85,14 +88,17 @@ def grad_reference(G, Gb, H, Hc, a, b, ys, xs, T2, S, Wt, N, LSE):
     return dG, T2l.grad, al.grad, bl.grad, yl.grad, xl.grad
 
 
-def make_case(P, h, S, N, Wt, spread=(5.0, 2.5), gscale=4.0, seed=0, prec=_lib.PREC_BF16, sort=True):
+def make_case(P, h, S, N, Wt, spread=(5.0, 2.5), gscale=4.0, seed=0, prec=_lib.PREC_BF16, sort=True, host_rng=False,
+              row_scale=None, unseen=None):
     """The two groups' positions are drawn independently; every row p * 2 + g is cell-sorted by its own group's table
-    coordinates with `sort` (ops.tap_group_order), else all rows keep the drawn order."""
-    gen = torch.Generator(device=dev).manual_seed(seed)
+    coordinates with `sort` (ops.tap_group_order), else all rows keep the drawn order.
+    host_rng, row_scale, unseen: as tap_check.make_case (unseen: slot tap_check.UNSEEN_TAP of group 0's block)."""
+    gd = "cpu" if host_rng else dev
+    gen = torch.Generator(device=gd).manual_seed(seed)
     ed = torch.bfloat16 if prec == _lib.PREC_BF16 else torch.float16
     geom = ops.AttnGeom(n_prob=P, q_div=1, heads=h, groups=NG, S=S, N=N, Wt=Wt, precision=prec)
     per = [tc.draw_keys(P, S, N, Wt, spread, False, gen) for _ in range(NG)]
-    a, b, ys, xs = (torch.stack([per[g][k] for g in range(NG)], 1).reshape(P * NG, N) for k in range(4))
+    a, b, ys, xs = (torch.stack([per[g][k] for g in range(NG)], 1).reshape(P * NG, N).to(dev) for k in range(4))
     if sort:
         _, a, b, ys, xs = ops.tap_group_order(a, b, ys, xs, NG)
     else:
@@ -100,12 +106,15 @@ def make_case(P, h, S, N, Wt, spread=(5.0, 2.5), gscale=4.0, seed=0, prec=_lib.P
     pad = geom.Np - N
     a, b, ys, xs = (torch.nn.functional.pad(t, (0, pad)).contiguous() for t in (a, b, ys, xs))
     G = torch.zeros(P, h, geom.Mp, 32, device=dev)
-    G[..., TAPS] = torch.randn(P, h, geom.Mp, 24, device=dev, generator=gen) * gscale
+    G[..., TAPS] = torch.randn(P, h, geom.Mp, 24, device=gd, generator=gen).to(dev) \
+        * (gscale if row_scale is None else row_scale(geom)[None, None, :, None])
+    if unseen is not None:
+        G[..., tc.UNSEEN_TAP] = unseen
     valid = (torch.arange(geom.Mp, device=dev) % geom.Sp) < S
     G = G * valid[None, None, :, None]
     G[..., 14] = -1.0e30 if prec == _lib.PREC_BF16 else -60000.0
-    Gb = torch.randn(P, h, geom.Mp, device=dev, generator=gen) * valid
-    T = torch.randn(h, 2 * S - 1, Wt, device=dev, generator=gen) * 0.5
+    Gb = torch.randn(P, h, geom.Mp, device=gd, generator=gen).to(dev) * valid
+    T = torch.randn(h, 2 * S - 1, Wt, device=gd, generator=gen).to(dev) * 0.5
     return geom, a, b, ys, xs, G.to(ed), Gb.contiguous(), T
 
 
@@ -118,18 +127,22 @@ def prep(geom, a, b, ys, xs):
     return ws
 
 
+def static_reference(geom, G, Gb, T, headroom):
+    """tap_check.static_reference for two groups: the bound is a SUM over the groups."""
+    tmax = (T.float() * ops.LOG2E).amax((1, 2)).clamp_min(0)
+    U = (G[..., :12].float().amax(-1).clamp_min(0) + G[..., 16:28].float().amax(-1).clamp_min(0)) * 1.01 + Gb \
+        + tmax[None, :, None] * 1.01 + 0.01
+    G = G.clone()
+    return G, (Gb - tc.set_offset(G, Gb - (U - headroom))).contiguous()
+
+
 def run_fwd(geom, a, b, ys, xs, G, Gb, T, headroom=64.0):
     L = _lib.lib()
     d = geom.desc()
     Tt = ops.pack_table(T.float(), geom)
     pair = torch.stack((Tt[..., :-1], Tt[..., 1:]), dim=-1).contiguous()
     ws = prep(geom, a, b, ys, xs)
-    tmax = (T.float() * ops.LOG2E).amax((1, 2)).clamp_min(0)
-    # the bound is a SUM over the groups
-    U = (G[..., :12].float().amax(-1).clamp_min(0) + G[..., 16:28].float().amax(-1).clamp_min(0)) * 1.01 + Gb \
-        + tmax[None, :, None] * 1.01 + 0.01
-    G = G.clone()
-    mref = (Gb - tc.set_offset(G, Gb - (U - headroom))).contiguous()
+    G, mref = static_reference(geom, G, Gb, T, headroom)
     R = torch.empty(geom.n_prob, geom.heads, geom.Mp, 32, device=dev, dtype=torch.float32)
     flags = torch.zeros(geom.n_prob * geom.heads, geom.S, device=dev, dtype=torch.int32)
     _lib.check(L.bevr_attn_tap_g2_fwd(C.byref(d), ops._ptr(G), ops._ptr(ws), ops._ptr(pair), ops._ptr(mref), ops._ptr(R),
@@ -188,12 +201,15 @@ def check_case(name, **kw):
     errors against the float64 definition on the given operands / on the operands as the kernels round them, and the
     gradients' relative errors (of the largest entry)."""
     headroom = kw.pop("headroom", 64.0)
+    forward_only = kw.pop("forward_only", False)   # the forward's figures alone (flags, per-row slack)
     geom, a, b, ys, xs, G, Gb, T = make_case(**kw)
     R, mref, flags, ws, pair = run_fwd(geom, a, b, ys, xs, G, Gb, T, headroom)
     torch.cuda.synchronize()
     P, h, S, Sp, N = geom.n_prob, geom.heads, geom.S, geom.Sp, geom.N
     Rg = R.double().reshape(P, h, S, Sp, 32)[:, :, :, :S]
     mr = mref.double().reshape(P, h, S, Sp)[:, :, :, :S]
+    # (mref as the kernel was GIVEN it: the exact pass has rewritten the flagged columns of `mref`)
+    mr0 = static_reference(geom, G, Gb, T, headroom)[1].double().reshape(P, h, S, Sp)[:, :, :, :S]
     l = Rg[..., 15]
     Rn_got = Rg / l[..., None]
     lse_got = mr + torch.log2(l)
@@ -202,10 +218,18 @@ def check_case(name, **kw):
     out = {}
     sel = TAPS + [14, 15, 28, 29, 30, 31]
     for tag, mm in (("exact", None), ("mimic", mim)):
-        Rn, LSE = reference(G.float(), Gb, a, b, ys, xs, T2, S, geom.Wt, N, mm)
+        Rn, LSE, MAX = reference(G.float(), Gb, a, b, ys, xs, T2, S, geom.Wt, N, mm, with_max=True)
         out[tag] = ((Rn_got[..., sel] - Rn[..., sel]).abs().max().item(), (lse_got - LSE).abs().max().item())
+        out[tag + "_rows"] = dict(lsum_log2=(LSE - mr0).cpu(), slack=(mr0 + headroom - MAX).cpu(),
+                                  lse_err=(lse_got - LSE).abs().cpu())    # tap_check.check_case
         if mm is None:
             LSE_exact = LSE
+    out["flags"] = flags.reshape(P, h, S).cpu()
+    out["finite_G"] = bool(torch.isfinite(G.float()).all())
+    if forward_only:
+        out.update(flagged=int(flags.sum()), dead=Rn_got[..., 14].abs().max().item())
+        print(f"{name:24s} flagged {out['flagged']}  Rn err mimic {out['mimic'][0]:.2e}  LSE err mimic {out['mimic'][1]:.2e}")
+        return out
     print(f"{name:24s} flagged {int(flags.sum())}  Rn err exact {out['exact'][0]:.2e} mimic {out['mimic'][0]:.2e}   "
           f"LSE err exact {out['exact'][1]:.2e} mimic {out['mimic'][1]:.2e}")
     H, Hc = draw_cotangent(geom, G.dtype)
