@@ -255,12 +255,15 @@ def _gen():
     return _GEN[0]
 
 
-def _whole_model(mode, monkeypatch, wsplit):
+def _whole_model(mode, monkeypatch, wsplit, env=None):
     """test_full_bevrender_conditioned's procedure (tests/test_gpu_full_model.py) on the new fixture.  Returns
-    (launched, e_out, lim_out, rows) with rows = (ok, line, err, lim) per parameter in backward order."""
+    (launched, e_out, lim_out, rows) with rows = (ok, line, err, lim) per parameter in backward order.
+    env: further switches of the run (tests/test_gpu_all_switches.py); BEVR_KV_WSPLIT is `wsplit`'s whatever it says."""
     from bevrender_amd.model.bevrender import BEVRender
     gw, z = _gen()
     g = gw.mgf
+    for name, value in (env or {}).items():
+        monkeypatch.setenv(name, value)
     monkeypatch.setenv("BEVR_KV_WSPLIT", "1" if wsplit else "0")
     launched = set()
 
