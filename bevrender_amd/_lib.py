@@ -37,6 +37,7 @@ SYMBOLS = [
     "bevr_attn_tap_g2_ws_bytes", "bevr_attn_tap_g2_prep", "bevr_attn_tap_g2_fwd", "bevr_attn_tap_g2_bwd_q",
     "bevr_attn_tap_g2_bwd_k",
     "bevr_attn_slab_x3_drop_ws_bytes", "bevr_attn_slab_x3_drop_prep", "bevr_attn_slab_bwd_q_x3_dropout",
+    "bevr_attn_slab_x3_rows_ws_bytes", "bevr_attn_slab_x3_rows_prep", "bevr_attn_slab_bwd_q_x3_rows",
     "bevr_offset_head_fwd", "bevr_offset_head_bwd", "bevr_key_positions_fwd", "bevr_key_positions_bwd", "bevr_kv_project", "bevr_layernorm_fwd", "bevr_layernorm_bwd", "bevr_merge_views_fwd", "bevr_merge_views_bwd", "bevr_merge_tap_fwd", "bevr_merge_tap_bwd", "bevr_attn_bwd_prep", "bevr_pack_kv", "bevr_unpack_dkv",
 ]
 
@@ -138,6 +139,9 @@ def lib() -> C.CDLL:
         L.bevr_attn_slab_x3_drop_ws_bytes.argtypes = [dp]
         L.bevr_attn_slab_x3_drop_prep.argtypes = [dp, fp, fp, vp, vp, vp]
         L.bevr_attn_slab_bwd_q_x3_dropout.argtypes = L.bevr_attn_slab_bwd_q_dropout.argtypes
+        L.bevr_attn_slab_x3_rows_ws_bytes.argtypes = [dp]
+        L.bevr_attn_slab_x3_rows_prep.argtypes = [dp, fp, fp, vp, vp, vp]
+        L.bevr_attn_slab_bwd_q_x3_rows.argtypes = L.bevr_attn_slab_bwd_q_rows.argtypes
         L.bevr_sample_fwd.argtypes = [fp, fp, fp] + [ip] * 5 + [vp]
         L.bevr_sample_bwd.argtypes = [fp] * 5 + [ip] * 5 + [vp]
         L.bevr_sample_fwd_bf16.argtypes = [vp, fp, fp] + [ip] * 5 + [vp]
@@ -171,7 +175,7 @@ def lib() -> C.CDLL:
             fn = getattr(L, name)
             if name in ("bevr_attn_key_ws_bytes", "bevr_attn_tap_ws_bytes", "bevr_attn_tap_g2_ws_bytes", "bevr_attn_slab_ws_bytes",
                         "bevr_attn_slab_rows_ws_bytes", "bevr_attn_slab_x3_ws_bytes", "bevr_attn_slab_drop_ws_bytes",
-                        "bevr_attn_slab_x3_drop_ws_bytes",
+                        "bevr_attn_slab_x3_drop_ws_bytes", "bevr_attn_slab_x3_rows_ws_bytes",
                         "bevr_attn_bwd_k_ws_bytes", "bevr_attn_tap_bwd_k_ws_bytes"):
                 fn.restype = C.c_size_t
             elif name not in ("bevr_strerror",):

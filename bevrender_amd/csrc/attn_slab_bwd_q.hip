@@ -57,6 +57,10 @@
 //
 // BEVR_SLAB_X3 = 1 and BEVR_DROP = 1 (attn_slab_bwd_q_x3_drop.hip): the same mask on the split-bf16 body, staged and taken
 // the same way; bevr_attn_slab_x3_drop_ws_bytes / _slab_x3_drop_prep / bevr_attn_slab_bwd_q_x3_dropout.
+//
+// BEVR_SLAB_ROWS = 1 and BEVR_SLAB_X3 = 1 (attn_slab_bwd_q_x3_rows.hip): the split-bf16 body over a band of row blocks,
+// S <= 448, on the same two pitches (7 and 6 owned columns of 16-byte cells); bevr_attn_slab_x3_rows_ws_bytes /
+// _slab_x3_rows_prep / bevr_attn_slab_bwd_q_x3_rows.  No keep mask on either band kernel.
 #ifndef BEVR_SLAB_ROWS
 #define BEVR_SLAB_ROWS 0
 #endif
@@ -270,7 +274,18 @@ __global__ __launch_bounds__(256) void slab_ranges_kernel(bevr_attn_desc d, cons
 // LDS-only barrier is not enough here: the producer's global loads are consumed by its own LDS stores before the barrier
 #define SLAB_BARRIER() __syncthreads()
 
-#if BEVR_SLAB_X3
+#if BEVR_SLAB_ROWS && BEVR_SLAB_X3
+// the split-bf16 body over a band of row blocks: attn_slab_bwd_q_x3.hip compiled with BEVR_SLAB_ROWS (RP, row0, n_rb_band
+// as the 16-bit band kernel below takes them)
+template <int PREC, int RP>
+__global__ __launch_bounds__(STHREADS, 1) void attn_slab_bwd_q_kernel(
+    bevr_attn_desc d, const char* __restrict__ Q, const char* __restrict__ Ks, const char* __restrict__ Vs,
+    const SlabKey* __restrict__ skeys, const int* __restrict__ kbeg, const int* __restrict__ kend,
+    const int4* __restrict__ items, int* __restrict__ cnt, const char* __restrict__ table_pair,
+    const char* __restrict__ dO, const float* __restrict__ LSE, const float* __restrict__ delta,
+    const float* __restrict__ grad_scale, float* __restrict__ dQ, float* __restrict__ dtable, int n_slab, int sw, int R
+    BEVR_DROP_PARAMS, int row0, int n_rb_band);
+#elif BEVR_SLAB_X3
 // the split-bf16 body: defined in attn_slab_bwd_q_x3.hip, behind this file's launch and entry points
 template <int PREC>
 __global__ __launch_bounds__(STHREADS, 1) void attn_slab_bwd_q_kernel(
@@ -809,11 +824,19 @@ int launch(const bevr_attn_desc& d, const void* Q, const void* Ks, const void* V
   return (int)hipGetLastError();
 }
 
+// the modes this translation unit holds the kernels of
+#if BEVR_SLAB_X3
+__host__ __device__ constexpr bool slab_prec_x3(int prec) { return prec == BEVR_PREC_BF16X3; }
+#define SLAB_PREC_OK slab_prec_x3
+#else
+#define SLAB_PREC_OK is16
+#endif
 #if BEVR_SLAB_ROWS
 // any S up to 448: a small S runs on the 832 pitch like any other (its window is shorter than the pitch, as S < 200's is
-// at 448)
+// at 448).  Split-bf16: 16-byte cells on the same two pitches -- 7 owned columns at 832 (9 x 832 x 16 + 2 x 18 464 + 64 =
+// 156 800 bytes of LDS), 6 at 960 (159 872)
 bool slab_shape_ok(const bevr_attn_desc& d) {
-  return is16(d.precision) && d.S <= SLAB_ROWS_MAX_S && slab_rows(d.S) <= slab_pitch(d.S) && SLAB_CH <= 64 &&
+  return SLAB_PREC_OK(d.precision) && d.S <= SLAB_ROWS_MAX_S && slab_rows(d.S) <= slab_pitch(d.S) && SLAB_CH <= 64 &&
          slab_lds_bytes(d.S, slab_width(d.S, slab_pitch(d.S)), slab_pitch(d.S)) <= 160 * 1024;
 }
 // a band of row blocks: starts on a block, at most SNRB blocks, whole blocks unless it ends the column (no sum is formed
@@ -823,38 +846,32 @@ bool slab_band_ok(const bevr_attn_desc& d, int row0, int n_rows) {
   if (row0 > d.S - n_rows) return false;
   return n_rows % SQROWS == 0 || row0 == d.S - n_rows;
 }
+#else
+bool slab_shape_ok(const bevr_attn_desc& d) {
+  return SLAB_PREC_OK(d.precision) && slab_n_rb(d.S) <= SNRB && slab_rows(d.S) <= SLAB_RP && SLAB_CH <= 64 &&
+         slab_lds_bytes(d.S, slab_width(d.S)) <= 160 * 1024;
+}
+#endif
+// the workspace entry points' names; the masked units have a preparation of their own: it writes SlabKey::pad, and the
+// code of the unmasked units' stays what it is
+#if BEVR_SLAB_ROWS && BEVR_SLAB_X3
+#define SLAB_WS_BYTES bevr_attn_slab_x3_rows_ws_bytes
+#define SLAB_PREP bevr_attn_slab_x3_rows_prep
+#elif BEVR_SLAB_ROWS
 #define SLAB_WS_BYTES bevr_attn_slab_rows_ws_bytes
 #define SLAB_PREP bevr_attn_slab_rows_prep
-#define SLAB_PREC_OK is16
-#elif BEVR_SLAB_X3
-__host__ __device__ constexpr bool slab_prec_x3(int prec) { return prec == BEVR_PREC_BF16X3; }
-bool slab_shape_ok(const bevr_attn_desc& d) {
-  return slab_prec_x3(d.precision) && slab_n_rb(d.S) <= SNRB && slab_rows(d.S) <= SLAB_RP && SLAB_CH <= 64 &&
-         slab_lds_bytes(d.S, slab_width(d.S)) <= 160 * 1024;
-}
-#if BEVR_DROP
-// a preparation of this unit's own, as the 16-bit masked unit's: it writes SlabKey::pad
+#elif BEVR_SLAB_X3 && BEVR_DROP
 #define SLAB_WS_BYTES bevr_attn_slab_x3_drop_ws_bytes
 #define SLAB_PREP bevr_attn_slab_x3_drop_prep
-#else
+#elif BEVR_SLAB_X3
 #define SLAB_WS_BYTES bevr_attn_slab_x3_ws_bytes
 #define SLAB_PREP bevr_attn_slab_x3_prep
-#endif
-#define SLAB_PREC_OK slab_prec_x3
-#else
-#define SLAB_PREC_OK is16
-bool slab_shape_ok(const bevr_attn_desc& d) {
-  return is16(d.precision) && slab_n_rb(d.S) <= SNRB && slab_rows(d.S) <= SLAB_RP && SLAB_CH <= 64 &&
-         slab_lds_bytes(d.S, slab_width(d.S)) <= 160 * 1024;
-}
-#if BEVR_DROP
-// a preparation of this unit's own: it writes SlabKey::pad, and bevr_attn_slab_prep's code stays what it is
+#elif BEVR_DROP
 #define SLAB_WS_BYTES bevr_attn_slab_drop_ws_bytes
 #define SLAB_PREP bevr_attn_slab_drop_prep
 #else
 #define SLAB_WS_BYTES bevr_attn_slab_ws_bytes
 #define SLAB_PREP bevr_attn_slab_prep
-#endif
 #endif
 
 // The contract of the three slab bwd_q entry points.  PRECS: the modes this translation unit holds the kernels of;
@@ -922,7 +939,15 @@ extern "C" int SLAB_PREP(const bevr_attn_desc* d, const float* key_a, const floa
   return (int)hipGetLastError();
 }
 
-#if BEVR_SLAB_ROWS
+#if BEVR_SLAB_ROWS && BEVR_SLAB_X3
+extern "C" int bevr_attn_slab_bwd_q_x3_rows(const bevr_attn_desc* d, const void* Q, const void* Ks, const void* Vs,
+                                            const void* slab_ws_, const float* table_pair, const void* dO,
+                                            const float* LSE, const float* delta, const float* grad_scale, float* dQ,
+                                            float* dtable, int row0, int n_rows, void* stream) {
+  return run<BEVR_PREC_BF16X3>(d, Q, Ks, Vs, slab_ws_, table_pair, dO, LSE, delta, grad_scale, dQ, dtable, row0, n_rows,
+                               stream);
+}
+#elif BEVR_SLAB_ROWS
 extern "C" int bevr_attn_slab_bwd_q_rows(const bevr_attn_desc* d, const void* Q, const void* Ks, const void* Vs,
                                          const void* slab_ws_, const float* table_pair, const void* dO, const float* LSE,
                                          const float* delta, const float* grad_scale, float* dQ, float* dtable, int row0,

@@ -34,6 +34,10 @@
 // bevr_attn_bwd_q_dropout, as the 16-bit slab kernel has it (attn_slab_bwd_q.hip) -- the original key index from
 // SlabKey::pad staged as a hash word per emission (2 x 256 bytes more LDS: 159 360, still 15 columns), the row part of the
 // hash per column, one FMA per pair on the dP accumulator ahead of a half's key-row loop: bevr_attn_slab_bwd_q_x3_dropout.
+// BEVR_SLAB_ROWS = 1 (attn_slab_bwd_q_x3_rows.hip, a translation unit of its own once more): S <= 448 in row bands, as the
+// 16-bit band kernel -- the row pitch a template parameter (832: 7 owned columns, 156 800 bytes of LDS; 960: 6 columns,
+// 159 872), the window at its full height, worker wave w on row block row0 / 31 + w, a worker beyond the band idle at
+// every barrier: bevr_attn_slab_bwd_q_x3_rows.  No keep mask there.
 //
 // No padding of a uniform row stride can do the same: a stride of 4 m dwords needs m odd for the fragment reads and the
 // eight 8-dword blocks of a transposed read tile the banks only if every row starts on a multiple of 8 dwords.
@@ -48,19 +52,31 @@ __device__ __forceinline__ int slab_x3_swz(int r) {
   return ((g << 1) | (g >> 2)) & 7;
 }
 
+// BEVR_SLAB_ROWS: RP the row pitch, row0 (a multiple of SQROWS) the first BEV row of the launch's band, n_rb_band <= SNRB its
+// row blocks: worker wave w owns row block row0 / SQROWS + w of the column (attn_slab_bwd_q.hip)
+#if BEVR_SLAB_ROWS
+template <int PREC, int RP>
+#else
 template <int PREC>
+#endif
 __global__ __launch_bounds__(STHREADS, 1) void attn_slab_bwd_q_kernel(
     bevr_attn_desc d, const char* __restrict__ Q, const char* __restrict__ Ks, const char* __restrict__ Vs,
     const SlabKey* __restrict__ skeys, const int* __restrict__ kbeg, const int* __restrict__ kend,
     const int4* __restrict__ items, int* __restrict__ cnt, const char* __restrict__ table_pair,
     const char* __restrict__ dO, const float* __restrict__ LSE, const float* __restrict__ delta,
     const float* __restrict__ grad_scale, float* __restrict__ dQ, float* __restrict__ dtable, int n_slab, int sw, int R
-    BEVR_DROP_PARAMS) {
+    BEVR_DROP_PARAMS
+#if BEVR_SLAB_ROWS
+    , int row0, int n_rb_band
+#endif
+    ) {
   static_assert(PREC == BEVR_PREC_BF16X3, "the split-bf16 body");
   typedef SlabLds L;
   extern __shared__ __attribute__((aligned(256))) char lds[];
   // layout: vals (f32x2) | cells (u64) | staging x 2 | item slot
+#if !BEVR_SLAB_ROWS
   constexpr int RP = SLAB_RP;
+#endif
   constexpr int ROWB = 128;                          // bytes of an operand row, in memory and staged
   static_assert(SKROW == ROWB && sizeof(SlabCK) == 32, "staging layout");
   const int ncell = (sw + 2) * RP;
@@ -73,8 +89,12 @@ __global__ __launch_bounds__(STHREADS, 1) void attn_slab_bwd_q_kernel(
   // uniform for the compiler too: the producer / worker branch is a scalar branch, not two masked passes of every wave
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const bool producer = wave == SNWORK;
-  const int rb = wave;                               // worker: row block
+  const int rb = wave;                               // worker: row block (BEVR_SLAB_ROWS: of the launch's band)
+#if BEVR_SLAB_ROWS
+  const int n_rb = n_rb_band;
+#else
   const int n_rb = slab_n_rb(d.S);
+#endif
   const int Mp = d.S * d.Sp;
   const int Hq = d.Hp + 1;
   const float rx = (float)(d.Wt - 1) / (2.0f * (float)(d.S - 1));
@@ -263,7 +283,11 @@ __global__ __launch_bounds__(STHREADS, 1) void attn_slab_bwd_q_kernel(
       asm volatile("" : "+v"(lane));
       const int lq = lane & 31, hi = lane >> 5;
       if (wave >= 4) __builtin_amdgcn_s_setprio(1);   // the younger wave of a SIMD (attn_slab_bwd_q.hip)
+#if BEVR_SLAB_ROWS
+      const int i0 = row0 + __builtin_amdgcn_readfirstlane(rb) * SQROWS;     // uniform: a scalar register
+#else
       const int i0 = rb * SQROWS;
+#endif
       const int qrow = i0 + lq;
       const bool live = lq < SQROWS && qrow < d.S;
       const int rowoff8 = (i0 + lq) * 8;

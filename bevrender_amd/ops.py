@@ -542,6 +542,7 @@ class K:
     BWD_Q, BWD_Q_DROP, SLAB_BWD_Q = "bevr_attn_bwd_q", "bevr_attn_bwd_q_dropout", "bevr_attn_slab_bwd_q"
     SLAB_BWD_Q_ROWS = "bevr_attn_slab_bwd_q_rows"
     SLAB_BWD_Q_X3 = "bevr_attn_slab_bwd_q_x3"
+    SLAB_BWD_Q_X3_ROWS = "bevr_attn_slab_bwd_q_x3_rows"
     SLAB_BWD_Q_DROP = "bevr_attn_slab_bwd_q_dropout"
     SLAB_BWD_Q_X3_DROP = "bevr_attn_slab_bwd_q_x3_dropout"
     BWD_K, BWD_K_DROP = "bevr_attn_bwd_k", "bevr_attn_bwd_k_dropout"
@@ -597,7 +598,7 @@ def attention_route(precision: int, groups: int, S: int, Wt: int, N: int, cell_s
     sample inside the tap grid?" (a reduction and a host sync at the caller): called at most once, and only for
     tap_source=True with dropout and a split that would otherwise be kept.  Raises attention_core's routing ValueErrors.
     Reads the A/B switches itself (BEVR_KNORM, BEVR_MERGE_TAP, BEVR_SCATTER_DROP) or through gather_supported,
-    slab_supported, slab_rows_supported, tap_supported, kv_source_supported and kv_wsplit (BEVR_KV_WSPLIT: `wsplit`, the
+    slab_supported, slab_rows_supported, slab_x3_rows_supported, tap_supported, kv_source_supported and kv_wsplit (BEVR_KV_WSPLIT: `wsplit`, the
     one field it changes, and only for source == "kv_source").
     BEVR_TAP_GROUPS (default TAP_GROUPS_DEFAULT: off; tap_supported; tests/test_tap_groups_routes_cpu.py): with groups == 2,
     a 16-bit mode and no keep mask, a pinned segment is a tap segment on the two-group entry points (K.TAP_G2_*), merged
@@ -677,6 +678,8 @@ def attention_route(precision: int, groups: int, S: int, Wt: int, N: int, cell_s
                 fwd = {None: K.FWD, "whole": K.GATHER, "bands": K.GATHER_ROWS}[gather]
             if slab_rows_supported(precision, S, Wt):       # off unless BEVR_SLAB_ROWS asks for it
                 bwd_q = K.SLAB_BWD_Q_ROWS
+            elif slab_x3_rows_supported(precision, S, Wt):  # off unless BEVR_SLAB_X3=2 asks for it
+                bwd_q = K.SLAB_BWD_Q_X3_ROWS
             elif precision == _lib.PREC_BF16X3:             # off unless BEVR_SLAB_X3 asks for it
                 bwd_q = K.SLAB_BWD_Q_X3 if slab_supported(precision, S, Wt) else K.BWD_Q
             else:
@@ -758,7 +761,8 @@ def slab_supported(precision, S, Wt=None) -> bool:
     (A/B timing, tests).  Same results up to the order of the float atomics and one rounding of the tap weights.
     The split-bf16 mode (BEVR_PREC_BF16X3: csrc/attn_slab_bwd_q_x3.hip, bevr_attn_slab_bwd_q_x3) under the same rules when
     BEVR_SLAB_X3 is set and not 0; the switch's default is SLAB_X3_DEFAULT: off, that mode's earlier routing (the
-    query-tile kernel), until the pinned route table changes with it.  With a keep mask the same answer decides, together
+    query-tile kernel), until the pinned route table changes with it (its value 2 adds row bands above S = 211:
+    slab_x3_rows_supported).  With a keep mask the same answer decides, together
     with scatter_drop, between bevr_attn_slab_bwd_q_dropout / bevr_attn_slab_bwd_q_x3_dropout and the query-tile kernel
     with the mask (attention_route)."""
     mode = os.environ.get("BEVR_SLAB", "1")
@@ -784,7 +788,8 @@ def slab_rows_supported(precision, S, Wt=None) -> bool:
     decides: unset or 0 -- never (the default: every call keeps the route it has; config 5 measured 20 % faster with
     it, profiles/r12_slab_rows.txt, and the default changes together with the pinned route table); 1 -- the sides the one-band kernel does not reach, 212 <= S <= 448, in the 16-bit modes, under slab_supported's
     other rules (BEVR_SLAB=0 turns every slab route off; SCA-wide tables only, unless BEVR_SLAB=2); 2 -- every S <= 448
-    and every table width, ahead of the one-band kernel (tests, A/B timing)."""
+    and every table width, ahead of the one-band kernel (tests, A/B timing).  The 16-bit modes only: the split-bf16
+    mode's band kernel is slab_x3_rows_supported's (BEVR_SLAB_X3=2)."""
     mode = os.environ.get("BEVR_SLAB_ROWS", "0")
     if mode not in ("1", "2") or precision not in (_lib.PREC_BF16, _lib.PREC_F16) or S > SLAB_ROWS_MAX_S:
         return False
@@ -792,6 +797,25 @@ def slab_rows_supported(precision, S, Wt=None) -> bool:
         return True
     slab = os.environ.get("BEVR_SLAB", "1")
     return S > 211 and slab != "0" and (slab == "2" or Wt is None or Wt - 1 >= 4 * (S - 1))
+
+
+def slab_x3_rows_supported(precision, S, Wt=None) -> bool:
+    """Does the query-side backward over scattered keys of the split-bf16 mode run on its slab kernel IN ROW BANDS
+    (csrc/attn_slab_bwd_q_x3_rows.hip, bevr_attn_slab_bwd_q_x3_rows: one launch per band of slab_bands, S <= 448)?  No new
+    switch: it is the VALUE 2 of BEVR_SLAB_X3 -- 0 or unset: no split slab kernel; 1: the one-band kernel, S <= 211
+    (slab_supported); 2: that, plus row bands for the sides it does not reach, 212 <= S <= 448, under slab_supported's other
+    rules (BEVR_SLAB=0 turns every slab route off; SCA-wide tables only, unless BEVR_SLAB=2).  BEVR_SLAB_ROWS=2 on top,
+    as for the 16-bit band kernel: every S <= 448 and every table width, ahead of the one-band kernel (tests, A/B
+    timing).  Opt-in: at config 5's geometry it measured 438 ms against the query-tile kernel's 1 155 ms per SCA call
+    (profiles/slab_x3_rows.txt), and the default changes together with the pinned route table.  No keep mask."""
+    if precision != _lib.PREC_BF16X3 or os.environ.get("BEVR_SLAB_X3", SLAB_X3_DEFAULT) != "2" or S > SLAB_ROWS_MAX_S:
+        return False
+    slab = os.environ.get("BEVR_SLAB", "1")
+    if slab == "0":
+        return False
+    if os.environ.get("BEVR_SLAB_ROWS", "0") == "2":
+        return True
+    return S > 211 and (slab == "2" or Wt is None or Wt - 1 >= 4 * (S - 1))
 
 
 def slab_bands(S, max_blocks=None):
@@ -921,7 +945,10 @@ def _bwd_q_slab_drop(name, o):
 def _bwd_q_slab_rows(name, o):
     g = o.g
     # one sort, one gather and one prep for all bands; a band's launch resets the work list's counter itself
-    Ks, Vs, sws = _slab_operands(o, "bevr_attn_slab_rows_ws_bytes", "bevr_attn_slab_rows_prep")
+    if name == K.SLAB_BWD_Q_X3_ROWS:     # split rows in float containers, the split band kernel's slab width
+        Ks, Vs, sws = _slab_operands(o, "bevr_attn_slab_x3_rows_ws_bytes", "bevr_attn_slab_x3_rows_prep")
+    else:
+        Ks, Vs, sws = _slab_operands(o, "bevr_attn_slab_rows_ws_bytes", "bevr_attn_slab_rows_prep")
     for row0, n_rows in slab_bands(g.S):      # (the timer's name is the slab route's, whichever entry point runs it)
         _launch(name, C.byref(o.desc), _ptr(o.Qe), _ptr(Ks), _ptr(Vs), _ptr(sws), _ptr(o.pair), _ptr(o.dOe), _ptr(o.LSE),
                 _ptr(o.delta), _ptr(o.gscale), _ptr(o.dQ), _ptr(o.dT), row0, n_rows, _stream(),
@@ -987,7 +1014,7 @@ _RUN = {K.FWD: _fwd_tile, K.FWD_DROP: _fwd_tile, K.GATHER: _fwd_gather, K.GATHER
         K.GATHER_X3: _fwd_gather, K.GATHER_DROP: _fwd_gather_drop, K.CELL_FWD: _fwd_cell,
         K.BWD_Q: _bwd_q_tile, K.BWD_Q_DROP: _bwd_q_tile, K.CELL_BWD_Q: _bwd_q_tile, K.SLAB_BWD_Q: _bwd_q_slab,
         K.SLAB_BWD_Q_ROWS: _bwd_q_slab_rows, K.SLAB_BWD_Q_X3: _bwd_q_slab, K.SLAB_BWD_Q_DROP: _bwd_q_slab_drop,
-        K.SLAB_BWD_Q_X3_DROP: _bwd_q_slab_drop,
+        K.SLAB_BWD_Q_X3_DROP: _bwd_q_slab_drop, K.SLAB_BWD_Q_X3_ROWS: _bwd_q_slab_rows,
         K.BWD_K: _bwd_k_tile, K.BWD_K_DROP: _bwd_k_tile, K.CELL_BWD_K: _bwd_k_cell,
         K.TAP_FWD: _tap_fwd, K.TAP_FWD_DROP: _tap_fwd, K.TAP_BWD_Q: _tap_bwd_q, K.TAP_BWD_Q_DROP: _tap_bwd_q,
         K.TAP_BWD_K: _tap_bwd_k, K.TAP_BWD_K_DROP: _tap_bwd_k,

@@ -78,7 +78,10 @@ extern "C" {
  *    bevr_kv_project_w2 (bevr_kv_project with the weights as two E planes, hi + lo; bevr_kv_project keeps its
  *    contract);
  *    bevr_attn_slab_x3_drop_ws_bytes / _slab_x3_drop_prep / bevr_attn_slab_bwd_q_x3_dropout (the slab query-side backward
- *    with the keep mask in BEVR_PREC_BF16X3, S <= 211; every other slab entry point keeps its contract). */
+ *    with the keep mask in BEVR_PREC_BF16X3, S <= 211; every other slab entry point keeps its contract);
+ *    bevr_attn_slab_x3_rows_ws_bytes / _slab_x3_rows_prep / bevr_attn_slab_bwd_q_x3_rows (the slab query-side backward in
+ *    BEVR_PREC_BF16X3 over a band of BEV rows of every column: BEV sides up to 448; every other slab entry point keeps
+ *    its contract). */
 #define BEVR_ABI_VERSION 6
 
 enum {
@@ -617,6 +620,31 @@ int bevr_attn_slab_x3_prep(const bevr_attn_desc* d, const float* key_a, const fl
 int bevr_attn_slab_bwd_q_x3(const bevr_attn_desc* d, const void* Q, const void* Ks, const void* Vs, const void* slab_ws,
                             const float* table_pair, const void* dO, const float* LSE, const float* delta,
                             const float* grad_scale, float* dQ, float* dtable, void* stream);
+/* bevr_attn_slab_bwd_q_x3 for any 2 <= S <= 448 (S < 2 is no side of any descriptor: BEVR_E_SHAPE from the descriptor check,
+ * as everywhere), over the BEV rows [row0, row0 + n_rows) of every BEV column
+ * (csrc/attn_slab_bwd_q_x3_rows.hip: the split-bf16 kernel with the taller slab columns and the band of row blocks of
+ * bevr_attn_slab_bwd_q_rows).  The slab again keeps every table row the whole column can reach, so the bands of a column
+ * are independent launches that add into the same dQ (disjoint rows) and dtable; all of them together are
+ * bevr_attn_slab_bwd_q_x3's result where that one exists (S <= 211), up to the order of the float atomics.  With 16-byte
+ * cells the slab owns 7 table columns up to S = 403 and 6 above; every band fills the slabs and streams the sorted
+ * K / V rows again.  No keep mask.
+ *   bevr_attn_slab_x3_rows_ws_bytes / _slab_x3_rows_prep: as bevr_attn_slab_ws_bytes / _slab_prep, for this kernel's slab
+ *           width (0 / BEVR_E_SHAPE for S > 448, 0 / BEVR_E_PRECISION for any mode but BEVR_PREC_BF16X3); not
+ *           interchangeable with the other slab workspaces.  ONE prep serves all bands of a call (launched one after
+ *           another on a stream: a launch resets the work list's item counter itself, see slab_ws above).
+ *   bevr_attn_slab_bwd_q_x3_rows: operands of bevr_attn_slab_bwd_q_x3 (128-byte split rows, the f32 pair table, gscale
+ *           folded as there), then (row0, n_rows) as bevr_attn_slab_bwd_q_rows takes them.  Checks in that entry point's
+ *           order: NULL, precision (BEVR_E_PRECISION for any mode but BEVR_PREC_BF16X3), shape (2 <= S <= 448, and row0 >= 0,
+ *           row0 % 31 == 0, 1 <= n_rows <= 217, row0 + n_rows <= S, n_rows % 31 == 0 unless row0 + n_rows == S; else
+ *           BEVR_E_SHAPE), alignment.  dQ of rows outside the range is not touched.  bevr_attn_slab_bwd_q_rows keeps
+ *           answering BEVR_E_PRECISION to this mode and bevr_attn_slab_bwd_q_x3 BEVR_E_SHAPE to S > 211. */
+size_t bevr_attn_slab_x3_rows_ws_bytes(const bevr_attn_desc* d);
+int bevr_attn_slab_x3_rows_prep(const bevr_attn_desc* d, const float* key_a, const float* key_b, const int32_t* order,
+                                void* slab_ws, void* stream);
+int bevr_attn_slab_bwd_q_x3_rows(const bevr_attn_desc* d, const void* Q, const void* Ks, const void* Vs,
+                                 const void* slab_ws, const float* table_pair, const void* dO, const float* LSE,
+                                 const float* delta, const float* grad_scale, float* dQ, float* dtable, int row0,
+                                 int n_rows, void* stream);
 /* bevr_attn_slab_bwd_q with the keep mask of bevr_attn_bwd_q_dropout (csrc/attn_slab_bwd_q_drop.hip), 16-bit modes,
  * S <= 211.  The keys arrive sorted by b, and the mask is of the key's index in the CALLER's order, n = order[pg][t] for
  * sorted position t: the workspace carries that index, so it has entry points of its own.

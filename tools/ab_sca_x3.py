@@ -12,8 +12,11 @@ the scattered keys' query-side backward on bevr_attn_slab_bwd_q_x3 (BEVR_SLAB_X3
 on the split-mode tap dropout kernels (BEVR_TAP_X3_DROP=1: bevr_attn_tap_*_x3_dropout beside the region dropout kernels on
 the scattered keys) against the parent's routing (the switch unset: every key sampled, projected and sent through the
 region dropout kernels).  Each step draws its own mask seed; the routes' work does not depend on it.
+--slab-rows: the block at config 5's geometry (S = 400, 128 x 352 features) with BEVR_TAP_X3=1 and BEVR_GATHER_X3=1 on both
+sides, the scattered keys' query-side backward on the row-band slab kernel bevr_attn_slab_bwd_q_x3_rows (BEVR_SLAB_X3=2)
+against BEVR_SLAB_X3=1, which at this side is the query-tile kernel.
 
-    B=8 ITERS=5 python tools/ab_sca_x3.py [--gather | --slab | --drop P] [out.json]"""
+    B=8 ITERS=5 python tools/ab_sca_x3.py [--gather | --slab | --slab-rows | --drop P] [out.json]"""
 import json
 import math
 import os
@@ -50,6 +53,8 @@ def ring_rig(V, img_w, img_h):
 def main():
     B, iters = int(os.environ.get("B", "8")), max(5, int(os.environ.get("ITERS", "5")))
     S, D, V, C, h, img_w, img_h = 200, 5, 6, 64, 2, 704, 256
+    if "--slab-rows" in sys.argv[1:]:      # config 5's geometry: BEV 400, 6 cameras 512 x 1408
+        S, img_w, img_h = 400, 1408, 512
     Hi, Wi = img_h // 4, img_w // 4
     T, K = ring_rig(V, img_w, img_h)
     proj = BEV2CameraProjector(imu_to_rgb={0: T}, K={0: K}, vehicle_type_code=0, img_width=img_w, img_height=img_h,
@@ -70,8 +75,11 @@ def main():
     q = torch.randn(B, C, S, S, generator=gen).to(DEV).requires_grad_(True)
     x = torch.randn(B * V, C, Hi, Wi, generator=gen).to(DEV).requires_grad_(True)
     cot = torch.randn(B, C, S, S, generator=gen).to(DEV)
-    argv = [a for a in argv if a not in ("--gather", "--slab")]
-    if drop_p > 0.0:
+    argv = [a for a in argv if a not in ("--gather", "--slab", "--slab-rows")]
+    if "--slab-rows" in sys.argv[1:]:
+        on = {"BEVR_TAP_X3": "1", "BEVR_GATHER_X3": "1"}
+        new, routes = "slab_x3_rows", (("slab_x3_rows", dict(on, BEVR_SLAB_X3="2")), ("parent_route", dict(on, BEVR_SLAB_X3="1")))
+    elif drop_p > 0.0:
         # (the parent's route: the switch UNSET, as a process that never heard of it)
         new, routes = "tap_x3_drop", (("tap_x3_drop", {"BEVR_TAP_X3": "1", "BEVR_TAP_X3_DROP": "1"}),
                                       ("parent_route", {"BEVR_TAP_X3": "1", "BEVR_TAP_X3_DROP": None}))
@@ -113,14 +121,15 @@ def main():
                 times[tag].append(ms)
     for tag, sw in routes:       # one more step of each with per-kernel events
         step(tag, sw, True)
-    res = {"what": "SCA block forward + backward, bf16x3, S=200, 6 views, B=%d%s; routes alternating in one process"
-                   % (B, ", training mode, attention dropout p=%g" % drop_p if drop_p > 0.0 else ""),
+    res = {"what": "SCA block forward + backward, bf16x3, S=%d, 6 views, B=%d%s; routes alternating in one process"
+                   % (S, B, ", training mode, attention dropout p=%g" % drop_p if drop_p > 0.0 else ""),
            "routes": {tag: sw for tag, sw in routes}, "iters": iters}
     for tag, v in times.items():
         res[tag] = {"median_ms": round(statistics.median(v), 1), "min_ms": round(min(v), 1), "max_ms": round(max(v), 1),
                     "all_ms": [round(t, 1) for t in v]}
     res["ratio_new_over_parent"] = round(res[new]["median_ms"] / res["parent_route"]["median_ms"], 3)
     res["kernels_ms_one_step"] = kernels
+    res["max_memory_allocated_GiB"] = round(torch.cuda.max_memory_allocated() / 2 ** 30, 1)      # of the device's 288
     print(json.dumps(res, indent=1))
     if argv:
         with open(argv[0], "w") as f:

@@ -49,6 +49,7 @@ LATER = {
                         ("bevr_attn_slab_x3_drop_prep", "bevr_attn_slab_bwd_q_x3_dropout")),
     "tap_groups": ("tap_groups_error_codes.json",
                    ("bevr_attn_tap_g2_prep", "bevr_attn_tap_g2_fwd", "bevr_attn_tap_g2_bwd_q", "bevr_attn_tap_g2_bwd_k")),
+    "slab_x3_rows": ("slab_x3_rows_error_codes.json", ("bevr_attn_slab_x3_rows_prep", "bevr_attn_slab_bwd_q_x3_rows")),
 }
 # descriptor fields a group's entry points need on top of BASE to accept a call (the tap entry points for two channel
 # groups take groups == 2 only; their "groups" defect, heads=2,groups=2, is then no defect and is recorded as accepted)

@@ -5,7 +5,12 @@ HIP events around each launch (ops.KERNEL_TIMER) inside a forward + backward of 
 route, then rounds of 7 calls per route in both orders; per route and order the median with min and max.  The query and
 table gradients of the two routes are compared at the timed size.
 
-    python tools/time_slab_x3.py [out.txt]"""
+--bev S: another BEV side.  Above 211 the slab route is the row-band kernel (bevr_attn_slab_bwd_q_x3_rows, BEVR_SLAB_X3=2)
+and a figure is the SUM of a call's band launches (ops.slab_bands(S)); --keys, --batch and --views size the launch
+(config 5, S = 400: about 144 000 scattered keys per view).
+
+    python tools/time_slab_x3.py [out.txt] [--bev S --keys N --batch B --views V]"""
+import argparse
 import os
 import statistics
 import sys
@@ -20,8 +25,8 @@ DEV = "cuda"
 ROUTES = {"slab_x3": ("1", "bevr_attn_slab_bwd_q"), "tile": ("0", "bevr_attn_bwd_q")}      # switch, timer name
 
 
-def inputs(gen):
-    S, C, h, D, N, B, V = 200, 64, 2, 5, 36000, 2, 6
+def inputs(gen, S=200, N=36000, B=2, V=6):
+    C, h, D = 64, 2, 5
     Wt = 2 * S * D - 1
     base = (torch.rand(1, N, 2, generator=gen) * 2 - 1) * 0.95
     order = torch.from_numpy(ops.kd_key_order(base[0].double().numpy(), S, Wt))
@@ -34,7 +39,7 @@ def inputs(gen):
     return [t.to(DEV) for t in (query, k, v, pos, table)], cot.to(DEV), h, V, N, B * V
 
 
-def call(ins, cot, h, V, route):
+def call(ins, cot, h, V, route, launches=1):
     sw, timer = ROUTES[route]
     os.environ["BEVR_SLAB_X3"] = sw
     leaves = [t.detach().requires_grad_(i in (0, 4)) for i, t in enumerate(ins)]      # the query-side gradients alone
@@ -42,32 +47,46 @@ def call(ins, cot, h, V, route):
     out = ops.attention_core(*leaves, heads=h, groups=1, views=V, precision=_lib.PREC_BF16X3)
     out.backward(cot)
     rec = ops.KERNEL_TIMER.stop()
-    assert timer in rec and rec[timer]["n"] == 1, sorted(rec)
+    assert timer in rec and rec[timer]["n"] == (launches if route == "slab_x3" else 1), sorted(rec)
     assert ("bevr_attn_bwd_q" in rec) == (route == "tile"), sorted(rec)
     return rec[timer]["ms"], leaves[0].grad, leaves[4].grad
 
 
 def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("out", nargs="?")
+    ap.add_argument("--bev", type=int, default=200)
+    ap.add_argument("--keys", type=int, default=36000)
+    ap.add_argument("--batch", type=int, default=2)
+    ap.add_argument("--views", type=int, default=6)
+    a = ap.parse_args()
+    S = a.bev
+    launches = 1
+    if S > 211:      # the row-band kernel: the switch's value 2, one launch per band
+        ROUTES["slab_x3"] = ("2", "bevr_attn_slab_bwd_q")
+        launches = len(ops.slab_bands(S))
     gen = torch.Generator().manual_seed(13)
     lines = []
-    ins, cot, h, V, N, n_prob = inputs(gen)
-    g = {r: call(ins, cot, h, V, r)[1:] for r in ROUTES}          # warm-up, and the gradients
+    ins, cot, h, V, N, n_prob = inputs(gen, S, a.keys, a.batch, a.views)
+    g = {r: call(ins, cot, h, V, r, launches)[1:] for r in ROUTES}          # warm-up, and the gradients
     eq = (g["slab_x3"][0] - g["tile"][0]).abs().max().item() / g["tile"][0].abs().max().item()
     et = (g["slab_x3"][1] - g["tile"][1]).abs().max().item() / g["tile"][1].abs().max().item()
-    lines.append(f"SCA: S=200 N={N} problems={n_prob} heads={h}; slab_x3 against query-tile: dQ {eq:.3e} d(table) {et:.3e}")
+    lines.append(f"SCA: S={S} N={N} problems={n_prob} heads={h} slab launches per call={launches}; slab_x3 against "
+                 f"query-tile: dQ {eq:.3e} d(table) {et:.3e}")
     del g
     for first, second in (("slab_x3", "tile"), ("tile", "slab_x3")):
         ms = {first: [], second: []}
         for _ in range(7):
             for r in (first, second):
-                ms[r].append(call(ins, cot, h, V, r)[0])
+                ms[r].append(call(ins, cot, h, V, r, launches)[0])
         med = {r: statistics.median(v) for r, v in ms.items()}
         for r in (first, second):
             lines.append(f"SCA order {first} first: {r:8s} median {med[r]:8.2f} ms  min {min(ms[r]):8.2f}  max {max(ms[r]):8.2f}")
         lines.append(f"SCA order {first} first: slab_x3 / tile = {med['slab_x3'] / med['tile']:.3f}")
+    lines.append(f"SCA: max memory allocated {torch.cuda.max_memory_allocated() / 2 ** 30:.1f} GiB")
     print("\n".join(lines))
-    if len(sys.argv) > 1:
-        with open(sys.argv[1], "w") as f:
+    if a.out:
+        with open(a.out, "w") as f:
             f.write("\n".join(lines) + "\n")
 
 
