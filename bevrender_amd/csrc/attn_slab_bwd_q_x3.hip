@@ -1,9 +1,10 @@
 // Slab query-side backward in BEVR_PREC_BF16X3 (split-bf16 products at f32 tolerance), S <= 211: bevr_attn_slab_bwd_q_x3.
 //
-// attn_slab_bwd_q.hip compiled with BEVR_SLAB_X3 = 1 gives the constants, the workspace, the preparation kernels, the launch
-// and the entry points; the kernel body below is this file's own -- a separate translation unit so that the 16-bit kernels
-// stay what they are.  The scheme is the 16-bit kernel's (persistent workgroups, work items from an atomic counter, a
-// producer wave one emission ahead, one worker wave per 31-row block, keys sorted by table column); what differs:
+// attn_slab.h compiled with BEVR_SLAB_X3 = 1 gives the constants, the workspace, the preparation kernels, the scaffold of
+// the kernel, the launch and the entry points; the kernel body below is this file's own -- a separate translation unit so
+// that the 16-bit kernels stay what they are.  The scheme is the 16-bit kernel's (persistent workgroups, work items from an
+// atomic counter, a producer wave one emission ahead, one worker wave per 31-row block, keys sorted by table column); what
+// differs:
 //
 //   * operands.  Q, dO and the sorted K / V rows are the mode's 128-byte split rows (bevr_common.h: per 16-element half
 //     hi(e0..7) | hi(e8..15) | lo(e0..7) | lo(e8..15)); S^T = K Q, dP^T = V dO and dQ += dS K are three-term split products,
@@ -30,19 +31,15 @@
 //     (bit 0 of (r >> 1) is bit 1 of f), so the rows read positions C ^ F, C ^ F, C ^ F ^ 2, C ^ F ^ 2 at bank offsets 0, 32, 0,
 //     32: C ^ 2 is the other plane's chunk set, disjoint from C -- 32 lanes x 2 dwords cover the 64 banks once;
 //   - the producer's stores: 8 contiguous lanes write the 8 chunks of ONE row, a permutation of its 128 bytes: 32 banks once.
-// BEVR_DROP = 1 (attn_slab_bwd_q_x3_drop.hip, a translation unit of its own again): the keep mask of
-// bevr_attn_bwd_q_dropout, as the 16-bit slab kernel has it (attn_slab_bwd_q.hip) -- the original key index from
-// SlabKey::pad staged as a hash word per emission (2 x 256 bytes more LDS: 159 360, still 15 columns), the row part of the
-// hash per column, one FMA per pair on the dP accumulator ahead of a half's key-row loop: bevr_attn_slab_bwd_q_x3_dropout.
-// BEVR_SLAB_ROWS = 1 (attn_slab_bwd_q_x3_rows.hip, a translation unit of its own once more): S <= 448 in row bands, as the
-// 16-bit band kernel -- the row pitch a template parameter (832: 7 owned columns, 156 800 bytes of LDS; 960: 6 columns,
-// 159 872), the window at its full height, worker wave w on row block row0 / 31 + w, a worker beyond the band idle at
-// every barrier: bevr_attn_slab_bwd_q_x3_rows.  No keep mask there.
+// BEVR_DROP = 1 and BEVR_SLAB_ROWS = 1 (the stub units attn_slab_bwd_q_x3_drop.hip, attn_slab_bwd_q_x3_rows.hip): attn_slab.h.
 //
 // No padding of a uniform row stride can do the same: a stride of 4 m dwords needs m odd for the fragment reads and the
 // eight 8-dword blocks of a transposed read tile the banks only if every row starts on a multiple of 8 dwords.
 #define BEVR_SLAB_X3 1
-#include "attn_slab_bwd_q.hip"
+#include "attn_slab.h"
+
+// phase clocks: the slots of attn_slab_bwd_q.hip, under a tag of this body's own
+BEVR_PROF_DEFINE(slab_x3, 48)
 
 namespace {
 
@@ -52,38 +49,16 @@ __device__ __forceinline__ int slab_x3_swz(int r) {
   return ((g << 1) | (g >> 2)) & 7;
 }
 
-// BEVR_SLAB_ROWS: RP the row pitch, row0 (a multiple of SQROWS) the first BEV row of the launch's band, n_rb_band <= SNRB its
-// row blocks: worker wave w owns row block row0 / SQROWS + w of the column (attn_slab_bwd_q.hip)
-#if BEVR_SLAB_ROWS
-template <int PREC, int RP>
-#else
-template <int PREC>
-#endif
-__global__ __launch_bounds__(STHREADS, 1) void attn_slab_bwd_q_kernel(
-    bevr_attn_desc d, const char* __restrict__ Q, const char* __restrict__ Ks, const char* __restrict__ Vs,
-    const SlabKey* __restrict__ skeys, const int* __restrict__ kbeg, const int* __restrict__ kend,
-    const int4* __restrict__ items, int* __restrict__ cnt, const char* __restrict__ table_pair,
-    const char* __restrict__ dO, const float* __restrict__ LSE, const float* __restrict__ delta,
-    const float* __restrict__ grad_scale, float* __restrict__ dQ, float* __restrict__ dtable, int n_slab, int sw, int R
-    BEVR_DROP_PARAMS
-#if BEVR_SLAB_ROWS
-    , int row0, int n_rb_band
-#endif
-    ) {
+SLAB_KERNEL_SIGNATURE {
   static_assert(PREC == BEVR_PREC_BF16X3, "the split-bf16 body");
   typedef SlabLds L;
   extern __shared__ __attribute__((aligned(256))) char lds[];
-  // layout: vals (f32x2) | cells (u64) | staging x 2 | item slot
 #if !BEVR_SLAB_ROWS
   constexpr int RP = SLAB_RP;
 #endif
   constexpr int ROWB = 128;                          // bytes of an operand row, in memory and staged
   static_assert(SKROW == ROWB && sizeof(SlabCK) == 32, "staging layout");
-  const int ncell = (sw + 2) * RP;
-  f32x2* vals = reinterpret_cast<f32x2*>(lds);
-  unsigned long long* cells = reinterpret_cast<unsigned long long*>(lds + (size_t)ncell * 8);
-  char* stage = reinterpret_cast<char*>(cells) + (size_t)ncell * 8;
-  int* item_slot = reinterpret_cast<int*>(stage + 2 * L::BUF);
+  const SlabMem<f32x2> m = slab_carve<f32x2, RP>(lds, sw);
 
   const int tid = threadIdx.x;
   // uniform for the compiler too: the producer / worker branch is a scalar branch, not two masked passes of every wave
@@ -96,7 +71,6 @@ __global__ __launch_bounds__(STHREADS, 1) void attn_slab_bwd_q_kernel(
   const int n_rb = slab_n_rb(d.S);
 #endif
   const int Mp = d.S * d.Sp;
-  const int Hq = d.Hp + 1;
   const float rx = (float)(d.Wt - 1) / (2.0f * (float)(d.S - 1));
   const int n_items = cnt[0];
   const int hpg = d.heads / d.groups;
@@ -112,38 +86,13 @@ __global__ __launch_bounds__(STHREADS, 1) void attn_slab_bwd_q_kernel(
 
   for (;;) {
     // ---- next work item -------------------------------------------------------------------------------------------
-    SLAB_BARRIER();                                   // everybody is done with the previous item's slot and slab
-    if (tid == 0) item_slot[0] = atomicAdd(cnt + 1, 1);
-    SLAB_BARRIER();
-    const int it = __builtin_amdgcn_readfirstlane(item_slot[0]);
-    if (it >= n_items) break;                         // uniform: every wave leaves here
-    const int4 item = items[it];
-    const int ph = __builtin_amdgcn_readfirstlane(item.x), slab = __builtin_amdgcn_readfirstlane(item.y),
-              chunk = __builtin_amdgcn_readfirstlane(item.z);
-    const int prob = ph / d.heads, hd = ph % d.heads;
-    const int pg = prob * d.groups + hd / hpg;
-    const int qb = prob / d.q_div;
-    const int x0 = slab_xmin(d) + slab * sw;
-    const int j0 = chunk * SLAB_CH, j1 = min(d.S, j0 + SLAB_CH);
-    const char* tbl = table_pair + (size_t)hd * d.Wp * d.Hp * 8;
-    float* dtb = dtable + (size_t)hd * d.Wp * Hq;
+    const int i = slab_claim(tid, m, cnt);
+    if (i >= n_items) break;                          // uniform: every wave leaves here
+    const SlabItem it = slab_item(items, i, d, hpg, sw, table_pair, dtable);
     PROF_T_DRAIN(ti0);
 
-    // ---- the slab: values in, cells cleared -----------------------------------------------------------------------
-    for (int u = tid; u < (sw + 1) * RP; u += STHREADS) {
-      const int c = u / RP, w = u - c * RP;
-      const int xc = x0 + c + d.x_off;                // padded table column
-      const int yr = w - SLAB_ROW0 + d.y_off;         // padded table row
-      f32x2 v = {0.f, 0.f};
-      if (w < R && yr >= 0 && yr < d.Hp && xc >= 0 && xc < d.Wp)   // tiny S: the window is taller than the padded table
-        v = *reinterpret_cast<const f32x2*>(tbl + ((size_t)xc * d.Hp + yr) * 8);
-      vals[RP + u] = v;
-      cells[RP + u] = 0ull;
-    }
-    for (int u = tid; u < RP; u += STHREADS) {        // the kill column: a finite -big
-      vals[u] = f32x2{BEVR_NEG_BIG, BEVR_NEG_BIG};
-      cells[u] = 0ull;
-    }
+    // ---- the slab: values in as they are, cells cleared; the kill column: a finite -big ----------------------------
+    slab_fill<RP>(tid, m, d, it, sw, R, [](f32x2 v) { return v; }, f32x2{BEVR_NEG_BIG, BEVR_NEG_BIG});
     SLAB_BARRIER();
     PROF_T_DRAIN(ti1);
     PROF_ADD(12, ti1 - ti0);     // slab in
@@ -156,59 +105,40 @@ __global__ __launch_bounds__(STHREADS, 1) void attn_slab_bwd_q_kernel(
       // here and not hoisted to the kernel's entry, where it would occupy the workers' registers too -- and vice versa
       int lane = tid & 63;
       asm volatile("" : "+v"(lane));
-      const SlabKey* kp = skeys + (size_t)pg * d.N;
-      const char* Kh = Ks + (size_t)ph * d.N * ROWB;
-      const char* Vh = Vs + (size_t)ph * d.N * ROWB;
-      // the chunk's key runs: lane c holds column j0 + c
-      const size_t rbase = ((size_t)pg * n_slab + slab) * d.S;
-      const int my_beg = j0 + lane < j1 ? kbeg[rbase + j0 + lane] : 0;
-      const int my_end = j0 + lane < j1 ? kend[rbase + j0 + lane] : 0;
-      // emission iterator: (column index c, first key k0) of the next emission to LOAD
-      int lc = 0, lk = 0, lend = 0;
-      auto seek = [&]() {       // from column index lc on: the first column with a non-empty run; lc == j1 - j0: none left
-        while (lc < j1 - j0) {
-          const int b = __builtin_amdgcn_readlane(my_beg, lc), e = __builtin_amdgcn_readlane(my_end, lc);
-          if (b < e) { lk = b; lend = e; return; }
-          ++lc;
-        }
-      };
-      seek();
+      const SlabKey* kp = skeys + (size_t)it.pg * d.N;
+      const char* Kh = Ks + (size_t)it.ph * d.N * ROWB;
+      const char* Vh = Vs + (size_t)it.ph * d.N * ROWB;
+      SlabRuns runs;
+      runs.start(lane, kbeg, kend, d, it, n_slab);
       u32x4 kv[16];             // 64 keys x 8 chunks of K, then of V: chunk id lane + 64 q <-> key id / 8, chunk id % 8
       SlabKey sk = {0, 0.f, 0.f, 0};
       // (initialised: an array first written under a condition is, for the compiler, the previous ITEM's, and 64 registers
       // stayed live through the workers' path)
 #pragma unroll
       for (int q = 0; q < 16; ++q) kv[q] = u32x4{0u, 0u, 0u, 0u};
-      int cur_c = -1, cur_k = 0, cur_end = 0;
       bool have = false;
-      auto issue = [&]() {      // loads of the emission at (lc, lk); then step the iterator
-        have = lc < j1 - j0;
+      auto issue = [&]() {      // loads of the emission at the iterator; then step the iterator
+        have = runs.more();
         if (!have) return;
-        cur_c = lc; cur_k = lk; cur_end = lend;
+        runs.take();
         const int kmax = d.N - 1;
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
           const int cid = lane + 64 * q;
-          const int key = min(cur_k + (cid >> 3), kmax);
+          const int key = min(runs.k0 + (cid >> 3), kmax);
           kv[q] = *reinterpret_cast<const u32x4*>(Kh + (size_t)key * ROWB + (cid & 7) * 16);
           kv[8 + q] = *reinterpret_cast<const u32x4*>(Vh + (size_t)key * ROWB + (cid & 7) * 16);
         }
-        sk = kp[min(cur_k + lane, kmax)];
-        lk += SEK;
-        if (lk >= lend) { ++lc; seek(); }
+        sk = kp[min(runs.k0 + lane, kmax)];
+        runs.step();
       };
       issue();
       int e = 0;
-      int prev_c = -1;
       while (have) {
-        char* bb = stage + (e & 1) * L::BUF;
-        const int c = cur_c, k0 = cur_k, kend_c = cur_end;
-        const int j = j0 + c;
+        char* bb = m.stage + (e & 1) * L::BUF;
+        const SlabRuns::Emission em = runs.emission();
+        const int j = it.j0 + em.c;
         const float jrx = (float)j * rx;
-        // is this the column's last emission?  (the iterator already points at the next one)
-        const bool last = !(lc < j1 - j0) || lc != c;
-        const bool first = c != prev_c;
-        prev_c = c;
         PROF_T_DRAIN(tp0);
         const SlabKey sk_e = sk;
         // ---- K and V rows, chunks swizzled: straight out of the load registers (a copy of 16 x 4 registers, as the 16-bit
@@ -228,7 +158,7 @@ __global__ __launch_bounds__(STHREADS, 1) void attn_slab_bwd_q_kernel(
           const float tx = jrx + sk_e.b;
           const float xf = floorf(tx);
           const int X = (int)xf;
-          const bool live = (k0 + lane < kend_c) && X >= x0 && X < x0 + sw;
+          const bool live = (em.k0 + lane < em.kend) && X >= it.x0 && X < it.x0 + sw;
           // The column fraction without the rounding of jrx + b (|tx| reaches ~1000 table columns: half an ulp is 3e-5 of a
           // column, as much again as the error jrx itself carries): the integer comes off the LARGER term first -- exact,
           // both are on that term's grid and the difference is no larger -- and the sum of two terms of nearly equal size
@@ -243,7 +173,7 @@ __global__ __launch_bounds__(STHREADS, 1) void attn_slab_bwd_q_kernel(
             ck.w10 = fx * (1.0f - fy);
             ck.w11 = fx * fy;
             ck.row = sk_e.A + SLAB_ROW0;
-            ck.cell = ((X - x0 + 1) * RP + ck.row) * 8;       // BYTE offset of the first tap's value entry
+            ck.cell = ((X - it.x0 + 1) * RP + ck.row) * 8;    // BYTE offset of the first tap's value entry
           } else {          // masked: first tap in the kill column => P = 0, dS = 0
             ck.w00 = 1.f;
             ck.w01 = ck.w10 = ck.w11 = 0.f;
@@ -256,14 +186,7 @@ __global__ __launch_bounds__(STHREADS, 1) void attn_slab_bwd_q_kernel(
           // the keys arrive sorted by b: the mask is of the ORIGINAL index (SlabKey::pad, this unit's prep)
           *reinterpret_cast<unsigned*>(bb + L::OFF_KN + lane * 4) = (unsigned)sk_e.pad * 0xC2B2AE3Du;
 #endif
-          // per half: any live key; any live key whose rows leave the window for some row block (the clamped body)
-          const bool far = live && (sk_e.A + SLAB_ROW0 < 0 || sk_e.A > d.S - 1 + SLAB_PADR);
-          const unsigned long long lm = __ballot(live), fm = __ballot(far);
-          const unsigned hb = ((unsigned)lm != 0u ? 1u : 0u) | ((unsigned)(lm >> 32) != 0u ? 2u : 0u) |
-                              ((unsigned)fm != 0u ? 4u : 0u) | ((unsigned)(fm >> 32) != 0u ? 8u : 0u);
-          if (lane == 0)
-            *reinterpret_cast<u32x4*>(bb + L::OFF_CT) =
-                u32x4{(unsigned)((first ? SF_FIRST : 0) | (last ? SF_LAST : 0)) | (hb << 8), (unsigned)j, 0u, 0u};
+          slab_post(bb, lane, live, live && slab_far(d, sk_e.A), em, j);
         }
         ++e;
         PROF_T_DRAIN(tp2);
@@ -273,7 +196,7 @@ __global__ __launch_bounds__(STHREADS, 1) void attn_slab_bwd_q_kernel(
         PROF_ADD(2, tp3 - tp2);      // producer: waiting for the workers
         PROF_ADD(3, 1);
       }
-      if (lane == 0) *reinterpret_cast<u32x4*>(stage + (e & 1) * L::BUF + L::OFF_CT) = u32x4{(unsigned)SF_DONE, 0u, 0u, 0u};
+      slab_post_done(m.stage + (e & 1) * L::BUF, lane);
       SLAB_BARRIER();
       __builtin_amdgcn_s_setprio(0);
     } else {
@@ -291,9 +214,9 @@ __global__ __launch_bounds__(STHREADS, 1) void attn_slab_bwd_q_kernel(
       const int qrow = i0 + lq;
       const bool live = lq < SQROWS && qrow < d.S;
       const int rowoff8 = (i0 + lq) * 8;
-      const char* Qh = Q + ((size_t)(qb * d.heads + hd) * Mp) * ROWB;
-      const char* dOh = dO + ((size_t)ph * Mp) * ROWB;
-      const unsigned cells_off = (unsigned)(reinterpret_cast<char*>(cells) - lds);
+      const char* Qh = Q + ((size_t)(it.qb * d.heads + it.hd) * Mp) * ROWB;
+      const char* dOh = dO + ((size_t)it.ph * Mp) * ROWB;
+      const unsigned cells_off = m.cells_off;
       // this lane's four chunks of a staged row (lane = key row lq of a half, its 16-element half `hi`): hi plane of k-step
       // 0 and 1, lo plane of k-step 0 and 1
       const int fsw = slab_x3_swz(lq);
@@ -320,10 +243,10 @@ __global__ __launch_bounds__(STHREADS, 1) void attn_slab_bwd_q_kernel(
         const size_t mq = (size_t)j * d.Sp + min(qrow, d.S - 1);
         qf.load(Qh + mq * ROWB, hi);
         dof.load(dOh + mq * ROWB, hi);
-        lse_r = LSE[(size_t)ph * Mp + mq];
-        dlt_r = delta[(size_t)ph * Mp + mq];
+        lse_r = LSE[(size_t)it.ph * Mp + mq];
+        dlt_r = delta[(size_t)it.ph * Mp + mq];
 #if BEVR_DROP
-        hrow = bevr_drop_row(drop_seed, (uint32_t)ph, (uint32_t)(j * d.Sp + qrow));
+        hrow = bevr_drop_row(drop_seed, (uint32_t)it.ph, (uint32_t)(j * d.Sp + qrow));
 #endif
         jcur = j;
       };
@@ -347,7 +270,7 @@ __global__ __launch_bounds__(STHREADS, 1) void attn_slab_bwd_q_kernel(
         // dq[r]: query i0 + crow(r, hi), channel lq (dq_product): a wave instruction adds two 128-byte rows
         // (one lane-dependent pointer and one row bound, made here: as 16 hoisted 64-bit offsets and 16 hoisted lane masks
         // they stayed in registers for the whole kernel)
-        float* base = dQ + ((size_t)ph * Mp + (size_t)jcur * d.Sp + i0 + 4 * hi) * 32 + lq;
+        float* base = dQ + ((size_t)it.ph * Mp + (size_t)jcur * d.Sp + i0 + 4 * hi) * 32 + lq;
         int nrow = min(SQROWS, d.S - i0) - 4 * hi;      // rows crow(r, 0) < nrow of this lane half are queries
         asm volatile("" : "+v"(nrow));
 #pragma unroll
@@ -514,30 +437,27 @@ __global__ __launch_bounds__(STHREADS, 1) void attn_slab_bwd_q_kernel(
         SLAB_BARRIER();
         PROF_T_DRAIN(tw1);
         PROF_ADD(0, tw1 - tw0);      // worker: barrier wait
-        const char* bb = stage + (e & 1) * L::BUF;
-        const u32x4 ct = *reinterpret_cast<const u32x4*>(bb + L::OFF_CT);
-        const unsigned flags = (unsigned)__builtin_amdgcn_readfirstlane((int)ct[0]);
-        const unsigned jword = (unsigned)__builtin_amdgcn_readfirstlane((int)ct[1]);
-        if (flags & SF_DONE) break;
+        const char* bb = m.stage + (e & 1) * L::BUF;
+        const SlabCtl ct = slab_read_ctl(bb);
+        if (ct.done()) break;
         if (active) {
-          const int j = (int)(jword & 0xffffu);
           // (no prefetch of the next column's rows into the registers of Q and dO, as the 16-bit kernel has it: the
           // conditional reload of 32 registers kept the old and the new rows live across the products and the kernel
           // spilled; a column's ~9 emissions at the benchmark shape wait for these loads once)
-          if (flags & SF_FIRST) {
-            issue_column(j);
+          if (ct.first()) {
+            issue_column(ct.j());
             finish_column();
           }
-          const unsigned hb = flags >> 8;          // bits 0, 1: the halves with a live key; bits 2, 3: with a far one
+          const unsigned hb = ct.halves();
           if (hb & 3u) {
             if (hb & 12u) process(bb, std::true_type{});
             else process(bb, std::false_type{});
           }
-          if (flags & SF_LAST) flush_dq();
+          if (ct.last()) flush_dq();
         }
         PROF_T_DRAIN(tw2);
         PROF_ADD(1, tw2 - tw1);      // worker: the emission
-        PROF_ADD(2, (flags >> 8) & 1u);
+        PROF_ADD(2, ct.halves() & 1u);
         PROF_ADD(3, 1);
         ++e;
       }
@@ -546,14 +466,7 @@ __global__ __launch_bounds__(STHREADS, 1) void attn_slab_bwd_q_kernel(
     // ---- flush the slab: every cell once ----------------------------------------------------------------------------
     SLAB_BARRIER();
     PROF_T_DRAIN(tf0);
-    for (int u = tid; u < (sw + 1) * RP; u += STHREADS) {
-      const int c = u / RP, w = u - c * RP;
-      const unsigned long long v = w < R ? cells[RP + u] : 0ull;
-      if (v != 0ull) {
-        const int xc = x0 + c + d.x_off, yr = w - SLAB_ROW0 + d.y_off;
-        if (xc >= 0 && xc < d.Wp && yr >= 0 && yr < Hq) atomicAdd(dtb + (size_t)xc * Hq + yr, AccCell::to_float(v) * ginv);
-      }
-    }
+    slab_flush<RP>(tid, m, d, it, sw, R, ginv);
     PROF_T_DRAIN(tf1);
     PROF_ADD(13, tf1 - tf0);     // slab out
   }

@@ -6,7 +6,7 @@
 // BEVR_GATHER_ROWS, BEVR_SLAB_ROWS: a kernel's source compiled a second time), which would define the array and its reader
 // again (BEVR_SLAB_X3 is not one of them: attn_slab_bwd_q_x3.hip has a kernel body of its own and its own tag, slab_x3).
 // Include it after those four have their defaults (bevr_common.h, attn_tap.h, attn_gather_fwd.hip,
-// attn_slab_bwd_q.hip).
+// attn_slab.h).
 //
 //   BEVR_PROF_DEFINE(tag, n)      file scope: the n counters and their reader
 //   PROF_ACC(n)                   kernel body: the wave's accumulator

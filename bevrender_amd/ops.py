@@ -917,42 +917,35 @@ def _slab_operands(o, ws_bytes, prep):
     return Ks, Vs, sws
 
 
+# a slab bwd_q entry point's workspace pair (the "ws_bytes" / "prep" of its slab width; a masked one's prep also carries the
+# keys' indices in the caller's order, what the mask hashes) and what follows its operands: nothing, the keep mask (the
+# cotangent is the unscaled one, D enters in the kernel) or the (row0, n_rows) of one launch per band of slab_bands
+_SLAB = {
+    K.SLAB_BWD_Q: ("bevr_attn_slab_ws_bytes", "bevr_attn_slab_prep", None),
+    K.SLAB_BWD_Q_X3: ("bevr_attn_slab_x3_ws_bytes", "bevr_attn_slab_x3_prep", None),
+    K.SLAB_BWD_Q_DROP: ("bevr_attn_slab_drop_ws_bytes", "bevr_attn_slab_drop_prep", "drop"),
+    K.SLAB_BWD_Q_X3_DROP: ("bevr_attn_slab_x3_drop_ws_bytes", "bevr_attn_slab_x3_drop_prep", "drop"),
+    K.SLAB_BWD_Q_ROWS: ("bevr_attn_slab_rows_ws_bytes", "bevr_attn_slab_rows_prep", "bands"),
+    K.SLAB_BWD_Q_X3_ROWS: ("bevr_attn_slab_x3_rows_ws_bytes", "bevr_attn_slab_x3_rows_prep", "bands")}
+
+
 def _bwd_q_slab(name, o):
     g = o.g
-    if name == K.SLAB_BWD_Q_X3:     # split rows in float containers: sorted and gathered as they stand
-        Ks, Vs, sws = _slab_operands(o, "bevr_attn_slab_x3_ws_bytes", "bevr_attn_slab_x3_prep")
-    else:
-        Ks, Vs, sws = _slab_operands(o, "bevr_attn_slab_ws_bytes", "bevr_attn_slab_prep")
-    # (the timer's name is the slab route's, whichever entry point runs it)
-    _launch(name, C.byref(o.desc), _ptr(o.Qe), _ptr(Ks), _ptr(Vs), _ptr(sws), _ptr(o.pair), _ptr(o.dOe), _ptr(o.LSE),
-            _ptr(o.delta), _ptr(o.gscale), _ptr(o.dQ), _ptr(o.dT), _stream(), flops=_attn_flops(g, 3), tag=_call_tag(g),
-            timer=K.SLAB_BWD_Q)
-
-
-def _bwd_q_slab_drop(name, o):
-    """the slab bwd_q with the keep mask: the workspace of its own prep carries the keys' indices in the caller's order
-    (what the mask hashes); the cotangent is the unscaled one, D enters in the kernel"""
-    g = o.g
-    if name == K.SLAB_BWD_Q_X3_DROP:     # split rows in float containers, the split kernel's slab width
-        Ks, Vs, sws = _slab_operands(o, "bevr_attn_slab_x3_drop_ws_bytes", "bevr_attn_slab_x3_drop_prep")
-    else:
-        Ks, Vs, sws = _slab_operands(o, "bevr_attn_slab_drop_ws_bytes", "bevr_attn_slab_drop_prep")
-    _launch(name, C.byref(o.desc), _ptr(o.Qe), _ptr(Ks), _ptr(Vs), _ptr(sws), _ptr(o.pair), _ptr(o.dOe), _ptr(o.LSE),
-            _ptr(o.delta), _ptr(o.gscale), _ptr(o.dQ), _ptr(o.dT), *o.drop, _stream(), flops=_attn_flops(g, 3),
-            tag=_call_tag(g))
-
-
-def _bwd_q_slab_rows(name, o):
-    g = o.g
+    ws_bytes, prep, tail = _SLAB[name]
     # one sort, one gather and one prep for all bands; a band's launch resets the work list's counter itself
-    if name == K.SLAB_BWD_Q_X3_ROWS:     # split rows in float containers, the split band kernel's slab width
-        Ks, Vs, sws = _slab_operands(o, "bevr_attn_slab_x3_rows_ws_bytes", "bevr_attn_slab_x3_rows_prep")
-    else:
-        Ks, Vs, sws = _slab_operands(o, "bevr_attn_slab_rows_ws_bytes", "bevr_attn_slab_rows_prep")
-    for row0, n_rows in slab_bands(g.S):      # (the timer's name is the slab route's, whichever entry point runs it)
+    # (split-bf16: split rows in float containers, sorted and gathered as they stand)
+    Ks, Vs, sws = _slab_operands(o, ws_bytes, prep)
+    drop = o.drop if tail == "drop" else ()
+    # (the timer's name is the slab route's, whichever entry point runs it; a masked launch keeps its own)
+    timer = name if tail == "drop" else K.SLAB_BWD_Q
+    for rows in (slab_bands(g.S) if tail == "bands" else [()]):      # rows = (row0, n_rows)
+        flops = _attn_flops(g, 3) * rows[1] / g.S if rows else _attn_flops(g, 3)
         _launch(name, C.byref(o.desc), _ptr(o.Qe), _ptr(Ks), _ptr(Vs), _ptr(sws), _ptr(o.pair), _ptr(o.dOe), _ptr(o.LSE),
-                _ptr(o.delta), _ptr(o.gscale), _ptr(o.dQ), _ptr(o.dT), row0, n_rows, _stream(),
-                flops=_attn_flops(g, 3) * n_rows / g.S, tag=_call_tag(g), timer=K.SLAB_BWD_Q)
+                _ptr(o.delta), _ptr(o.gscale), _ptr(o.dQ), _ptr(o.dT), *rows, *drop, _stream(), flops=flops,
+                tag=_call_tag(g), timer=timer)
+
+
+_bwd_q_slab_drop = _bwd_q_slab_rows = _bwd_q_slab      # (the names the route tables' tests know the masked and band launches by)
 
 
 def _bwd_k(name, o, *keys):
@@ -1013,8 +1006,8 @@ def _tap_bwd_k(name, o):
 _RUN = {K.FWD: _fwd_tile, K.FWD_DROP: _fwd_tile, K.GATHER: _fwd_gather, K.GATHER_ROWS: _fwd_gather,
         K.GATHER_X3: _fwd_gather, K.GATHER_DROP: _fwd_gather_drop, K.CELL_FWD: _fwd_cell,
         K.BWD_Q: _bwd_q_tile, K.BWD_Q_DROP: _bwd_q_tile, K.CELL_BWD_Q: _bwd_q_tile, K.SLAB_BWD_Q: _bwd_q_slab,
-        K.SLAB_BWD_Q_ROWS: _bwd_q_slab_rows, K.SLAB_BWD_Q_X3: _bwd_q_slab, K.SLAB_BWD_Q_DROP: _bwd_q_slab_drop,
-        K.SLAB_BWD_Q_X3_DROP: _bwd_q_slab_drop, K.SLAB_BWD_Q_X3_ROWS: _bwd_q_slab_rows,
+        K.SLAB_BWD_Q_ROWS: _bwd_q_slab, K.SLAB_BWD_Q_X3: _bwd_q_slab, K.SLAB_BWD_Q_DROP: _bwd_q_slab,
+        K.SLAB_BWD_Q_X3_DROP: _bwd_q_slab, K.SLAB_BWD_Q_X3_ROWS: _bwd_q_slab,
         K.BWD_K: _bwd_k_tile, K.BWD_K_DROP: _bwd_k_tile, K.CELL_BWD_K: _bwd_k_cell,
         K.TAP_FWD: _tap_fwd, K.TAP_FWD_DROP: _tap_fwd, K.TAP_BWD_Q: _tap_bwd_q, K.TAP_BWD_Q_DROP: _tap_bwd_q,
         K.TAP_BWD_K: _tap_bwd_k, K.TAP_BWD_K_DROP: _tap_bwd_k,
